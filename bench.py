@@ -14,16 +14,28 @@ uniform-random int64 keys that are already resident in HBM when the timed region
           start-up (flash_hash_join_amd/distributed.py, csrc/fj_dist.hip) - for configs[4] the BUILD
           BROADCAST (the probe rows stay, every rank's partitioned build rows travel to every peer over
           xGMI, 6 bytes per key); north_star's all-to-all of radix partitions, the OWNER SHUFFLE, is
-          measured beside it in the same line (`alt_strategy`, with its own roofline block and wire bytes).
+          measured beside it under --full (`alt_strategy`, with its own roofline block and wire bytes).
           FJ_DIST_STRATEGY=broadcast|shuffle|scatter pins the timed form.  `python bench.py --gpus N` without
           a torchrun environment starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
           child process (before anything touches the GPU) and relays its output and exit code.
 
 value = probes processed by all ranks / wall time of the K timed steps (max over ranks), in
-G probes/s, end to end (build side included).  The probe-phase-only rate, the build time, the
-roofline of the dominant kernel (probe-side partition pass) and the CPU baseline (the oracle's
-restatement of the reference algorithm on this box's host cores, bounded sample; at N > 1: rank 0
-runs the config-3-size join, labelled as such) ride along in the same JSON line.
+G probes/s, end to end (build side included); ms_per_step = that wall time / K.  The probe-phase-only
+rate, the build time and the roofline of the dominant kernel (probe-side partition pass), all taken
+from the timed steps themselves, ride along in the same JSON line.
+
+--full adds what takes runs of its own: the CPU baseline (the oracle's restatement of the reference
+algorithm on this box's host cores, bounded sample; at N > 1: rank 0 runs the config-3-size join,
+labelled as such), the NumPy entry with its PCIe copies (`host_entry`, N = 1) and, at N > 1, the
+other multi-GPU form as `alt_strategy`.  A plain run sets up, warms up, times and prints.
+
+--dump-outputs DIR writes what the last timed step returned, for output-for-output comparisons of two
+builds (the inputs are a pure function of the arguments): match_count.npy (float64, one element; at N > 1
+the global count, written by rank 0) and, for the materialising workloads, a fixed sample of the pairs - those
+whose key's upper 32 bits fall below a threshold set by the pair count, at most 2^20 of them in (key,
+value) order, each uint64 split into exact float64 halves: pairs_{key,value}_{hi,lo}.npy (rank 0's pairs
+at N > 1).  A materialising step asked for its pairs hands them back (the last timed step then includes
+that copy).
 """
 from __future__ import annotations
 
@@ -227,6 +239,32 @@ def dist_roofline(strategy: str, part_ms, launches: int, units: float, wire_chun
             "avg_launch_ms": round(avg_ms, 4), "launches_timed": launches, "traffic": None}
 
 
+DUMP_MAX_PAIRS = 1 << 20         # 4 float64 arrays: 32 MB at most
+
+
+def dump_outputs(out_dir: str, count: int, pairs) -> None:
+    """--dump-outputs: the match count and, for a materialising step, a sample of its pairs that does not depend on their order
+    (the join's output order is unspecified): the pairs whose key's upper 32 bits fall below a threshold that keeps ~2^20 of
+    them, in (key, value) order, truncated to 2^20.  uint64 values are split into hi / lo halves, each exact in float64."""
+    import numpy as np
+    from flash_hash_join_amd import api
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "match_count.npy"), np.array([count], dtype=np.float64))
+    if not pairs:
+        return
+    k, v = pairs
+    n = int(k.numel())
+    if n > DUMP_MAX_PAIRS:
+        cut = (DUMP_MAX_PAIRS << 32) // n                      # keys are multiples of an odd 64-bit constant: top bits ~uniform
+        sel = ((k >> 32) & 0xFFFFFFFF) < cut
+        k, v = k[sel], v[sel]
+    k, v = api.sort_pairs(k, v)
+    for name, x in (("key", k[:DUMP_MAX_PAIRS]), ("value", v[:DUMP_MAX_PAIRS])):
+        u = x.cpu().numpy().view(np.uint64)
+        np.save(os.path.join(out_dir, f"pairs_{name}_hi.npy"), (u >> np.uint64(32)).astype(np.float64))
+        np.save(os.path.join(out_dir, f"pairs_{name}_lo.npy"), (u & np.uint64(0xFFFFFFFF)).astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -235,11 +273,17 @@ def main() -> None:
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3 (BASELINE configs[2]) at --gpus 1, c5 (configs[4], 125M x 1.25B rows per GPU) at --gpus > 1")
     ap.add_argument("--scale", type=float, default=1.0, help="scale the row counts (debugging)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-entry", action="store_true", help="skip the PCIe-inclusive measurement of the NumPy entry")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baseline, NumPy entry (N = 1), the other multi-GPU form (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-entry", action="store_true", help="with --full: skip the PCIe-inclusive measurement of the NumPy entry")
     ap.add_argument("--selfcheck-timeout", type=float, default=240.0, help="N > 1: seconds the pre-flight may take before the run is declared stuck")
     ap.add_argument("--selfcheck-corrupt", action="store_true", help=argparse.SUPPRESS)      # test hook: rank 0 flips one received bit in the pre-flight exchange
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload is None:
         args.workload = "c3" if args.gpus == 1 else "c5"
 
@@ -435,16 +479,22 @@ def main() -> None:
             if materialize and lt["emit_ms"] > 0:
                 kern.setdefault("emitting join kernel (second pass of a materialising join)", []).append((lt["emit_ms"], 8 * (S if L else P) + 16 * B + 16.0 * exp_local))
 
-    def step(record: bool) -> int:
+    last_pairs = []                 # --dump-outputs, materialising workloads: the (keys, values) the last timed step returned
+
+    def step(record: bool, want_pairs: bool = False) -> int:
         nonlocal part_launches
         if world == 1 and not force_dist:
-            res = api.join_device(algo, bloom, materialize, bk, bv, pk, return_arrays=False)
+            res = api.join_device(algo, bloom, materialize, bk, bv, pk, return_arrays=want_pairs)
+            if want_pairs:
+                last_pairs[:] = res[2:]
         else:
             t = {}
             # a materialising step writes its pairs inside the timed region (return_arrays: the pairs this rank keeps; dropped at once)
             res = distributed_join(bk, bv, pk, materialize=bool(materialize), bloom=bool(bloom), engine=engine, timings=t, transport=transport, force_exchange=force_dist,
                                    return_arrays=bool(materialize))
             if materialize:
+                if want_pairs:
+                    last_pairs[:] = res[2:]
                 res = (res[0], res[1])
             if t.get("prefilter_sampled_survivors") is not None:       # (warm-up steps included: "auto" samples once per shape, then remembers)
                 dsampled.update(survivors=t["prefilter_sampled_survivors"], below=t.get("prefilter_below"))
@@ -490,8 +540,8 @@ def main() -> None:
     sync()
     t0 = time.perf_counter()
     bad = 0
-    for _ in range(args.steps):
-        got = step(True)
+    for i in range(args.steps):
+        got = step(True, want_pairs=bool(args.dump_outputs and materialize and i == args.steps - 1))
         bad += int(got != exp_total)               # every timed step is checked against the closed-form count
     sync()
     elapsed = time.perf_counter() - t0
@@ -502,6 +552,9 @@ def main() -> None:
         elapsed = float(e.item())
 
     lt = api.last_timings()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, got, last_pairs)
+    last_pairs.clear()
     ms_per_step = elapsed / args.steps * 1e3
     value = np_total * args.steps / elapsed / 1e9
     mean = lambda xs: (sum(xs) / len(xs)) if xs else 0.0
@@ -612,7 +665,7 @@ def main() -> None:
     }
     if roof_all:
         out["roofline_kernels"] = roof_all
-    if rank == 0 and world == 1 and not args.no_host_entry and not force_dist:
+    if args.full and rank == 0 and world == 1 and not args.no_host_entry and not force_dist:
         try:
             del bk, bv, pk
         except NameError:
@@ -626,7 +679,7 @@ def main() -> None:
         out["xgmi_all_to_all"] = link
     if selfcheck is not None:
         out["self_check"] = selfcheck
-    if (world > 1 or force_dist) and not materialize and timed_strategy in ("broadcast", "shuffle"):
+    if args.full and (world > 1 or force_dist) and not materialize and timed_strategy in ("broadcast", "shuffle"):
         # the OTHER form of the step - the owner shuffle (north_star's all-to-all of radix partitions) when the broadcast was timed, and
         # the other way round - as a second, labelled measurement with its own roofline block and wire bytes; never `value`
         main = dlast.get("strategy", timed_strategy)
@@ -663,7 +716,7 @@ def main() -> None:
                                    "note": "not `value`: the other form of the multi-GPU step, measured beside the timed one"}
         except Exception as ex:
             out["alt_strategy"] = {"strategy": alt, "error": repr(ex)}
-    if rank == 0 and not args.no_cpu_baseline and not force_dist:
+    if args.full and rank == 0 and not args.no_cpu_baseline and not force_dist:
         try:
             # N = 1: the full workload on the host when it fits (the oracle needs ~2.5x the input bytes), else a 1/10 sample.
             # N > 1: rank 0 runs the config-3-size join (100M x 1B) and the block says so ("c5's CPU column is the

@@ -317,3 +317,34 @@ def test_bench_launches_its_own_ranks_when_asked_for_several_gpus(monkeypatch):
     assert "127.0.0.1" in cmd and cmd[-6:] == ["--gpus", "8", "--steps", "3", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert bench.WORKLOADS["c5"][:2] == (125_000_000, 1_250_000_000)
+
+
+def test_bench_dump_of_pairs_is_a_fixed_order_free_sample(tmp_path):
+    """bench.py --dump-outputs: the match count as float64, and a sample of a materialising step's pairs that is the same whatever
+    order the join emitted them in, at most DUMP_MAX_PAIRS of them, every uint64 split into two float64 halves that are exact."""
+    import torch
+    import bench
+    from flash_hash_join_amd import datagen
+    n = 3 * bench.DUMP_MAX_PAIRS + 12345
+    keys, _ = datagen.probe_numpy(n, n, seed=5, hit_bp=10000)
+    vals = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    perm = np.random.default_rng(0).permutation(n)
+    outs = []
+    for order in (np.arange(n), perm):
+        d = tmp_path / f"o{len(outs)}"
+        bench.dump_outputs(str(d), n, [torch.from_numpy(keys[order].view(np.int64)), torch.from_numpy(vals[order].view(np.int64))])
+        outs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = outs
+    assert sorted(a) == ["match_count.npy", "pairs_key_hi.npy", "pairs_key_lo.npy", "pairs_value_hi.npy", "pairs_value_lo.npy"]
+    assert a["match_count.npy"].dtype == np.float64 and a["match_count.npy"].tolist() == [float(n)]
+    assert all(a[f].dtype == np.float64 and np.array_equal(a[f], b[f]) for f in a)
+    m = a["pairs_key_hi.npy"].size
+    assert 0.9 * bench.DUMP_MAX_PAIRS < m <= bench.DUMP_MAX_PAIRS and sum(x.nbytes for x in a.values()) <= 64 << 20
+    k = (a["pairs_key_hi.npy"].astype(np.uint64) << np.uint64(32)) | a["pairs_key_lo.npy"].astype(np.uint64)
+    v = (a["pairs_value_hi.npy"].astype(np.uint64) << np.uint64(32)) | a["pairs_value_lo.npy"].astype(np.uint64)
+    cut = (bench.DUMP_MAX_PAIRS << 32) // n
+    sel = (keys >> np.uint64(32)) < np.uint64(cut)
+    o = np.lexsort((vals[sel], keys[sel]))
+    assert np.array_equal(k, keys[sel][o][:m]) and np.array_equal(v, vals[sel][o][:m])
+    bench.dump_outputs(str(tmp_path / "count"), 7, [])
+    assert os.listdir(tmp_path / "count") == ["match_count.npy"]

@@ -157,6 +157,37 @@ def test_bench_line_at_one_gpu_is_self_consistent(fj):
     assert abs(d["value"] - 1e9 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.01 * d["value"]
 
 
+def test_bench_dumps_what_its_last_timed_step_returned(fj, tmp_path):
+    """`python bench.py --dump-outputs DIR` on a materialising workload (c3_mat at 1/100: 1M x 10M rows, 5M pairs): the count and
+    the fixed sample of the pairs equal what the generator's closed form says the join must return; a plain run leaves out what
+    --full measures."""
+    import subprocess
+    import sys
+    import bench
+    from conftest import ROOT
+    from conftest import product_env
+    from flash_hash_join_amd import datagen
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3_mat", "--scale", "0.01", "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT, env=product_env())
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and not {"cpu_baseline", "cpu_baseline_c1", "host_entry"} & set(d), sorted(d)
+    nb, npk = 1_000_000, 10_000_000
+    pk, exp = datagen.probe_numpy(npk, nb, seed=1, hit_bp=5000)
+    with np.errstate(over="ignore"):
+        r = pk * np.uint64(pow(0x9E3779B97F4A7C15, -1, 1 << 64))            # build row i has key (i + 1) * M, value i
+    hit = (r >= 1) & (r <= nb)
+    keys, vals = pk[hit], r[hit] - np.uint64(1)
+    assert np.load(tmp_path / "match_count.npy").tolist() == [float(exp)] == [float(hit.sum())] == [float(d["config"]["matches"])]
+    sel = (keys >> np.uint64(32)) < np.uint64((bench.DUMP_MAX_PAIRS << 32) // keys.size)
+    o = np.lexsort((vals[sel], keys[sel]))
+    ek, ev = keys[sel][o][:bench.DUMP_MAX_PAIRS], vals[sel][o][:bench.DUMP_MAX_PAIRS]
+    for name, x in (("key", ek), ("value", ev)):
+        hi, lo = np.load(tmp_path / f"pairs_{name}_hi.npy"), np.load(tmp_path / f"pairs_{name}_lo.npy")
+        assert hi.dtype == lo.dtype == np.float64 and hi.size == x.size > 0
+        assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), x), name
+
+
 def test_against_c_oracle_on_fresh_random_inputs(fj, oracle, scalar_mode):
     rng = np.random.default_rng(2024)
     for nb, npk in [(1, 1), (2, 3), (255, 1000), (4096, 50000), (4097, 50000), (30000, 1), (123457, 654321)]:
@@ -954,7 +985,7 @@ def test_bench_multi_rank_branch_with_ranks_sharing_this_gpu(fj):
     env = product_env(FJ_BENCH_SHARE_GPU="1")               # (the bench runs on the PRODUCT library)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                   # exactly one JSON line, from rank 0
@@ -982,7 +1013,7 @@ def test_bench_multi_rank_branch_with_ranks_sharing_this_gpu(fj):
     s_ = socket.socket(); s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]; s_.close()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=900, env=dict(env, FJ_DIST_STRATEGY="shuffle"), cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, env=dict(env, FJ_DIST_STRATEGY="shuffle"), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["config"]["parallelism"].startswith("owner-shuffle") and d["phases"]["shuffle_form"].startswith("chunks (fj_dist_join over a callback transport")

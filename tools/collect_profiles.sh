@@ -18,7 +18,7 @@ python tools/trace_timeline.py gpurun_out/stats_${TAG}_c3 > $O/c3_timeline.txt 2
 python tools/trace_timeline.py gpurun_out/stats_${TAG}_c4 > $O/c4_timeline.txt 2>&1
 python tools/trace_timeline.py gpurun_out/stats_${TAG}_c3_mat > $O/c3_mat_timeline.txt 2>&1
 python tools/traffic_json.py $O/c3_pmc_summary.txt $O/traffic_latest.json > /dev/null 2>&1
-timeout 900 python bench.py 2>&1 | tail -1 > $O/c3_bench.json
+timeout 900 python bench.py --full 2>&1 | tail -1 > $O/c3_bench.json
 : > $O/other_workloads.jsonl
 for w in c2 c2_hbm_table c4 c4_scalar_bloom c4_adaptive c4_hbm_table_bloom c3_adaptive c3_mat small rep8 c5_rep8 c5; do
   timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-host-entry 2>&1 | tail -1 >> $O/other_workloads.jsonl
