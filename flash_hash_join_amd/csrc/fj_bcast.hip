@@ -442,6 +442,44 @@ int layout_of(size_t nb_total, size_t nkeys, Layout* L, bool with_vals = false) 
 
 }  // namespace
 
+namespace fjh {
+
+// emit_pending's broadcast case: the probe rows of every partition against the runs of the step's sources (source i's region of
+// nkeys[i] keys, laid out by fj_bcast_pack on its rank, starts off[i] bytes into base), at offsets scanned from the per-item counts
+int bcast_emit_launch(fj_ctx* c, const Pending& pd, u64* d_ok, u64* d_ov, hipStream_t s) {
+    Layout L0;
+    if (layout_of(pd.nb_total, 0, &L0)) return 1;
+    DenseMatArgs a{};
+    a.probe = pd.lds.probe; a.items = pd.lds.items; a.toff = pd.toff; a.part_lo = 0; a.part_hi = L0.nparts;
+    a.base = (const unsigned char*)pd.src.base; a.nsrc = (u32)pd.src.n; a.bits = L0.bits; a.mid_bytes = L0.mid_bytes;
+    for (int i = 0; i < pd.src.n; ++i) {
+        Layout L;
+        if (layout_of(pd.nb_total, (size_t)pd.src.nkeys[i], &L, true)) return 1;
+        const uint64_t o = pd.src.off[i];
+        a.offs_off[i] = o; a.lo_off[i] = o + L.lo_off; a.mid_off[i] = o + L.mid_off; a.val_off[i] = o + L.val_off;
+    }
+    a.part_count = pd.lds.part_count; a.total = &c->d_sc->total; a.err = &c->d_sc->err;
+    void* p;
+    if (get_buf(c, W_OUT_OFF, ((size_t)pd.nitems + 1) * 8, &p)) return 1;
+    HIPCHK(fj_launch_scan_u32_to_u64(pd.lds.part_count, (u64*)p, pd.nitems, s));
+    a.out_off = (const u64*)p; a.out_keys = d_ok; a.out_vals = d_ov;
+    HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, 4, s));
+    const u32 lds = DM_SLOTS * 8 * 2 + DM_NBK * 4 + 16;
+    HIPCHK(fj_set_max_lds_once(reinterpret_cast<const void*>(fj_dense_mat_join), lds));
+    hipLaunchKernelGGL(fj_dense_mat_join, dim3(c->num_cus), dim3(DM_NT), lds, s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// [p, p + bytes) is about to be freed (a communicator's broadcast buffer): a pending broadcast result whose regions lie there goes with it
+void drop_bcast_result_in(fj_ctx* c, const void* p, size_t bytes) {
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    const char* b = (const char*)c->pend.src.base;
+    if (c->pend.valid && c->pend.kind == Pending::BCAST && b >= (const char*)p && b < (const char*)p + bytes) drop_pending(c);
+}
+
+}  // namespace fjh
+
 extern "C" {
 
 int fj_bcast_plan(size_t nb_total, int* bits, uint32_t* nparts, int* mid_bytes) {
@@ -475,17 +513,15 @@ int fj_bcast_piece_span(size_t nb_total, size_t nkeys, size_t k_lo, size_t k_hi,
 // pieces: the region will travel in that many pieces of consecutive partitions; fj_bcast_pack_bounds blocks until their key
 // boundaries are known.
 int fj_bcast_pack(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, size_t nb, size_t nb_total, void* d_region, int pieces, int with_vals_in, void* stream) {
-    if (!c) return set_err("fj_bcast_pack: null context");
     if ((nb && !d_keys) || !d_region || (((uintptr_t)d_keys | (uintptr_t)d_vals | (uintptr_t)d_region) & 15)) return set_err("fj_bcast_pack: null or misaligned pointer");
     if (pieces < 1 || pieces > 16) return set_err("fj_bcast_pack: pieces must be 1..16");
-    if (c->st.active) return set_err("fj_bcast_pack: a stream join is open on this context");
     const bool with_vals = with_vals_in != 0;                  // a materialising join: the values travel as a fourth part of the region
     if (with_vals && nb && !d_vals) return set_err("fj_bcast_pack: a materialising join needs the build values");
     Layout L;
     if (layout_of(nb_total, nb, &L, with_vals)) return 1;
     FJ_ENTER(c);
+    if (begin_step(c, "fj_bcast_pack")) return 1;
     hipStream_t s = (hipStream_t)stream;
-    c->pend.valid = false;
     BcastState& bc = c->bc;
     bc = BcastState();
     bc.nb_total = nb_total; bc.pieces = pieces; bc.plan = make_plan(nb_total, 64); bc.with_vals = with_vals;
@@ -529,8 +565,8 @@ int fj_bcast_pack(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, siz
 // blocks until the pack has run: h_bounds[q] = index of the first key of piece q in this rank's region, h_bounds[pieces] = nb
 int fj_bcast_pack_bounds(fj_ctx* c, uint64_t* h_bounds) {
     if (!c || !h_bounds) return set_err("fj_bcast_pack_bounds: null argument");
-    if (!c->bc.packed) return set_err("fj_bcast_pack_bounds: no pack in flight");
     FJ_ENTER(c);
+    if (!c->bc.packed) return set_err("fj_bcast_pack_bounds: no pack in flight");
     HIPCHK(hipEventSynchronize(c->pk_ev));
     const u32* b = reinterpret_cast<const u32*>(c->pk_h);
     const u32 err = *reinterpret_cast<const u32*>(c->pk_h + 32);
@@ -542,11 +578,10 @@ int fj_bcast_pack_bounds(fj_ctx* c, uint64_t* h_bounds) {
 
 // This rank's probe rows through both passes of the global plan (asynchronous); they stay where they are.
 int fj_bcast_probe(fj_ctx* c, const uint64_t* d_pk, size_t np, size_t nb_total, void* stream) {
-    if (!c) return set_err("fj_bcast_probe: null context");
     if ((np && !d_pk) || ((uintptr_t)d_pk & 15)) return set_err("fj_bcast_probe: null or misaligned pointer");
+    FJ_ENTER(c);
     BcastState& bc = c->bc;
     if (!bc.packed || bc.nb_total != nb_total) return set_err("fj_bcast_probe: fj_bcast_pack of the same step comes first");
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
     bc.np = np;
     if (np) {
@@ -563,41 +598,16 @@ int fj_bcast_probe(fj_ctx* c, const uint64_t* d_pk, size_t np, size_t nb_total, 
     return 0;
 }
 
-// join the probe rows of partitions [part_lo, part_hi) against the runs of nsrc sources: source i's region (of nkeys[i] keys,
-// laid out by fj_bcast_pack on its rank) starts region_off[i] bytes into d_base
-static int dense_mat_args(fj_ctx* c, const void* d_base, int nsrc, const uint64_t* region_off, const uint64_t* nkeys, DenseMatArgs* a) {
-    BcastState& bc = c->bc;
-    Layout L0;
-    if (layout_of(bc.nb_total, 0, &L0)) return 1;
-    *a = DenseMatArgs();
-    a->probe = bc.ja.probe; a->items = bc.ja.items; a->toff = bc.pit.toff;
-    a->base = (const unsigned char*)d_base; a->nsrc = (u32)nsrc; a->bits = L0.bits; a->mid_bytes = L0.mid_bytes;
-    for (int i = 0; i < nsrc; ++i) {
-        Layout L;
-        if (layout_of(bc.nb_total, (size_t)nkeys[i], &L, true)) return 1;
-        if (region_off[i] & 15) return set_err("fj_bcast_join: region offsets must be multiples of 16");
-        a->offs_off[i] = region_off[i]; a->lo_off[i] = region_off[i] + L.lo_off; a->mid_off[i] = region_off[i] + L.mid_off; a->val_off[i] = region_off[i] + L.val_off;
-    }
-    a->part_count = bc.ja.part_count; a->total = &c->d_sc->total; a->err = &c->d_sc->err;
-    return 0;
-}
-static u32 dense_mat_lds() { return DM_SLOTS * 8 * 2 + DM_NBK * 4 + 16; }
-
 int fj_bcast_join(fj_ctx* c, const void* d_base, int nsrc, const uint64_t* region_off, const uint64_t* nkeys, uint32_t part_lo, uint32_t part_hi, void* stream) {
-    if (!c) return set_err("fj_bcast_join: null context");
+    if (!d_base || nsrc < 1 || nsrc > (int)FJ_WIDE_MAXSRC || !region_off || !nkeys) return set_err("fj_bcast_join: 1..%u sources", FJ_WIDE_MAXSRC);
+    FJ_ENTER(c);
     BcastState& bc = c->bc;
     if (!bc.probed) return set_err("fj_bcast_join: fj_bcast_probe of the same step comes first");
-    if (!d_base || nsrc < 1 || nsrc > (int)FJ_WIDE_MAXSRC || !region_off || !nkeys) return set_err("fj_bcast_join: 1..%u sources", FJ_WIDE_MAXSRC);
     Layout L0;
     if (layout_of(bc.nb_total, 0, &L0)) return 1;
     if (part_lo > part_hi || part_hi > L0.nparts) return set_err("fj_bcast_join: partitions [%u, %u) of %u", part_lo, part_hi, L0.nparts);
     if (bc.np == 0 || part_lo == part_hi) return 0;
-    FJ_ENTER(c);
     const u32 cus = c->reserve_cus < c->num_cus ? c->num_cus - c->reserve_cus : 1u;
-    if (bc.with_vals) {      // a materialising step is counted like a counting one; fj_emit_pairs needs to find the regions again (they stay where they are)
-        bc.mat_base = d_base; bc.mat_nsrc = nsrc;
-        for (int i = 0; i < nsrc; ++i) { bc.mat_off[i] = region_off[i]; bc.mat_nk[i] = nkeys[i]; }
-    }
     FjWideArgs w{};
     w.toff = bc.pit.toff; w.part_lo = part_lo; w.part_hi = part_hi;
     w.base = (const unsigned char*)d_base; w.nsrc = (u32)nsrc; w.bits = L0.bits; w.mid_bytes = L0.mid_bytes; w.pmask = fj_wide_pmask((int)L0.bits, 64);
@@ -611,67 +621,43 @@ int fj_bcast_join(fj_ctx* c, const void* d_base, int nsrc, const uint64_t* regio
         if (region_off[i] & 15) return set_err("fj_bcast_join: region offsets must be multiples of 16");
         w.offs_off[i] = region_off[i]; w.lo_off[i] = region_off[i] + L.lo_off; w.mid_off[i] = region_off[i] + L.mid_off;
     }
+    bc.src.base = d_base; bc.src.n = nsrc;          // (the pairs of a materialising step are written from these regions, where they lie)
+    for (int i = 0; i < nsrc; ++i) { bc.src.off[i] = region_off[i]; bc.src.nkeys[i] = nkeys[i]; }
     HIPCHK(fj_launch_count_join_wide(bc.ja, w, true, cus, (hipStream_t)stream));
     return 0;
 }
 
-// the pairs of the materialising step that fj_bcast_finish just counted: (probe key, build value) of this rank's probe rows, out_capacity >= the count
-int fj_bcast_emit(fj_ctx* c, uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, void* stream) {
-    if (!c) return set_err("fj_bcast_emit: null context");
-    BcastState& bc = c->bc;
-    if (!bc.mat_ready) return set_err("fj_emit_pairs: no materialising build-broadcast step is pending on this context");
-    if (bc.mat_count > out_capacity) return set_err("fj_emit_pairs: output capacity %zu < %llu pairs", out_capacity, (unsigned long long)bc.mat_count);
-    FJ_ENTER(c);
-    hipStream_t s = (hipStream_t)stream;
-    bc.mat_ready = false;
-    if (bc.mat_count == 0) return 0;
-    if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("output buffers must be 8-byte aligned");
-    void* p;
-    if (get_buf(c, W_OUT_OFF, ((size_t)bc.mat_items + 1) * 8, &p)) return 1;
-    HIPCHK(fj_launch_scan_u32_to_u64(bc.ja.part_count, (u64*)p, bc.mat_items, s));
-    DenseMatArgs a;
-    if (dense_mat_args(c, bc.mat_base, bc.mat_nsrc, bc.mat_off, bc.mat_nk, &a)) return 1;
-    Layout L0;
-    if (layout_of(bc.nb_total, 0, &L0)) return 1;
-    a.part_lo = 0; a.part_hi = L0.nparts;
-    a.out_off = (const u64*)p; a.out_keys = d_out_keys; a.out_vals = d_out_vals;
-    HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, 4, s));
-    HIPCHK(fj_set_max_lds_once(reinterpret_cast<const void*>(fj_dense_mat_join), dense_mat_lds()));
-    hipLaunchKernelGGL(fj_dense_mat_join, dim3(c->num_cus), dim3(DM_NT), dense_mat_lds(), s, a);
-    HIPCHK(hipGetLastError());
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_STAT_RETRY) return set_err("internal error: a partition the counting kernel accepted does not fit the pair writer's table (fj_bcast_emit)");
-    return 0;
-}
-
 int fj_bcast_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* timings) {
-    if (!c) return set_err("fj_bcast_finish: null context");
+    FJ_ENTER(c);
     BcastState& bc = c->bc;
     if (!bc.probed) return set_err("fj_bcast_finish: no broadcast join in flight");
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     const u32 err = c->h_sc->err;
-    const int npass = bc.plan.npass, bits = bc.plan.bits, evc = bc.evc;
-    const bool mat = bc.with_vals;
-    if (!mat || (err & (FJ_ERR_POOL | FJ_STAT_RETRY | FJ_ERR_LDS_FULL))) bc = BcastState();
-    else { bc.packed = bc.probed = false; bc.mat_ready = true; bc.mat_count = c->h_sc->total; bc.mat_items = bc.pit.items_cap; }      // (the emit reads the regions and the probe partitions where they lie)
+    const Plan plan = bc.plan;
+    const int evc = bc.evc;
+    if (bc.with_vals && !(err & (FJ_ERR_POOL | FJ_STAT_RETRY | FJ_ERR_LDS_FULL))) {
+        // a materialising step: its pairs are written by fj_emit_pairs, from the regions and the probe partitions where they lie
+        drop_pending(c);
+        Pending& pd = c->pend;
+        pd.valid = true; pd.kind = Pending::BCAST; pd.count = c->h_sc->total; pd.nitems = bc.pit.items_cap;
+        pd.lds = bc.ja; pd.toff = bc.pit.toff; pd.src = bc.src; pd.nb_total = bc.nb_total;
+    }
+    bc = BcastState();
     if (err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
     end_plan(c);
     // a final partition beyond the LDS table (> ~8000 build keys in all: build-side skew): the caller takes another form
     if (err & (FJ_STAT_RETRY | FJ_ERR_LDS_FULL)) return set_err("build broadcast: a final partition does not fit the LDS table (skewed build keys)");
     if (out_count) *out_count = c->h_sc->total;
     fj_timings t; memset(&t, 0, sizeof t);
-    t.path = 0; t.passes = npass; t.radix_bits = bits; t.partitions = 1ull << bits; t.sampled_hit_bp = -1;
-    for (int i = 0; i < evc && i < 4; ++i) t.probe_part_kernel_ms[i] = ev_ms(c, E_PK0 + 2 * i, E_PK0 + 2 * i + 1);
-    t.build_phase_ms = ev_ms(c, E_START, E_BUILD); t.join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t.probe_phase_ms = ev_ms(c, E_BUILD, E_JOIN); t.total_ms = ev_ms(c, E_START, E_JOIN);
+    t.sampled_hit_bp = -1;
+    plan_timings(c, plan, 1ull << plan.bits, evc, &t);
     if (timings) *timings = t;
     last_timings() = t;
     return 0;
 }
 
-void fj_bcast_abort(fj_ctx* c) { if (c) { c->bc = BcastState(); } }
+void fj_bcast_abort(fj_ctx* c) { if (c) { std::lock_guard<std::recursive_mutex> lock(c->mu); c->bc = BcastState(); } }
 
 }  // extern "C"

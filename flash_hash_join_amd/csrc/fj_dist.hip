@@ -458,10 +458,16 @@ struct fj_dist_comm {
     // the CU reserve, measured: successful steps so far; this rank's probe-side pass time (ms) of the step that ran with / without it
     // (per join shape: a step of other sizes - a pre-flight check in front of the real joins - starts the measurement afresh)
     int rs_step = 0; double rs_with_ms = 0.0, rs_without_ms = 0.0; unsigned long long rs_nb = 0, rs_np = 0;
+    // a pending broadcast result of the HIP engine's context (its regions are in `bcast`) goes before the buffer.  (A shuffle step's
+    // result lies in the context's own pools: the receive buffers feed the second pass, and every plan of that form has one.)
+    void release(DBuf& b) {
+        if (b.p && hip) fjh::drop_bcast_result_in(hip->ctx, b.p, b.bytes);
+        if (b.p) { eng->release(b.p); b = DBuf(); }
+    }
     int grow(DBuf& b, size_t bytes) {
         if (bytes == 0) bytes = 16;
         if (b.bytes >= bytes) return 0;
-        if (b.p) { eng->release(b.p); b.p = nullptr; b.bytes = 0; }
+        release(b);
         const size_t want = (bytes + 4095) & ~(size_t)4095;
         b.p = eng->alloc(want);
         if (!b.p) return derr("fj_dist: allocating %zu bytes of device memory failed", want);
@@ -469,9 +475,9 @@ struct fj_dist_comm {
         return 0;
     }
     void free_all() {
-        for (auto* arr : {pool_k, pool_d}) for (int i = 0; i < 2; ++i) if (arr[i].p) { eng->release(arr[i].p); arr[i] = DBuf(); }
-        for (auto* arr : {recv_k, recv_d}) for (int i = 0; i <= MAX_PIECES; ++i) if (arr[i].p) { eng->release(arr[i].p); arr[i] = DBuf(); }
-        for (DBuf* b : {&pool_v, &recv_v, &filt, &bcast}) if (b->p) { eng->release(b->p); *b = DBuf(); }
+        for (auto* arr : {pool_k, pool_d}) for (int i = 0; i < 2; ++i) release(arr[i]);
+        for (auto* arr : {recv_k, recv_d}) for (int i = 0; i <= MAX_PIECES; ++i) release(arr[i]);
+        for (DBuf* b : {&pool_v, &recv_v, &filt, &bcast}) release(*b);
     }
 };
 

@@ -47,9 +47,11 @@ struct DeviceGuard {
 #define FJ_ON_DEVICE(dev)                                                                                   \
     fjh::DeviceGuard dev_guard_(dev);                                                                            \
     if (dev_guard_.err != hipSuccess) return fjh::set_err("selecting HIP device %d failed: %s", (int)(dev), hipGetErrorString(dev_guard_.err))
-// Entry of a C-ABI call on context c: calls on one context are serialised (the workspace, the scratch words and the events
-// are per context; fj_join_host re-enters through fj_join_device / fj_stream_*: a recursive lock), then the device guard.
+// Entry of a C-ABI call on context c: a null context is refused; calls on one context are serialised (the workspace, the scratch
+// words and the events are per context; fj_join_host re-enters through fj_join_device / fj_stream_*: a recursive lock), then the
+// device guard.  What the call reads or writes of the context's state comes after it.
 #define FJ_ENTER(c)                                                                                         \
+    if (!(c)) return fjh::set_err("%s: null context", __func__);                                             \
     std::lock_guard<std::recursive_mutex> ctx_lock_((c)->mu);                                                \
     FJ_ON_DEVICE((c)->device)
 
@@ -91,10 +93,16 @@ struct Buf { void* p = nullptr; size_t bytes = 0; };
 
 enum Ev { E_START = 0, E_BUILD, E_PPART, E_JOIN, E_EMIT0, E_EMIT1, E_SB0, E_SB1, E_BF0, E_BF1, E_H0, E_H1, E_H2, E_PK0, E_NEV = E_PK0 + 8 };
 
+// the regions of a build-broadcast step (csrc/fj_bcast.hip): source i's region of nkeys[i] keys starts off[i] bytes into base
+struct BcastSources { const void* base = nullptr; int n = 0; uint64_t off[FJ_WIDE_MAXSRC] = {}, nkeys[FJ_WIDE_MAXSRC] = {}; };
+
+// The one record of a materialising join that was counted and whose pairs fj_emit_pairs has not written yet (emit_pending consumes
+// it; begin_step drops it: what it points at is about to be overwritten)
 struct Pending {
+    enum Kind { LDS, HBM_TABLE, MANY, BCAST };
     bool valid = false;
-    int path = 0;
-    FjLdsJoinArgs lds{};
+    Kind kind = LDS;
+    FjLdsJoinArgs lds{};                 // LDS, MANY; BCAST: the probe partitions, items and per-item counts of the step
     FjGtArgs gt{};
     u32 nitems = 0, gt_grid = 0;
     u64 count = 0;
@@ -104,6 +112,8 @@ struct Pending {
     // duplicate build keys seen by the counting pass: the emitting pass must pick the FIRST occurrence's value
     bool has_dups = false;
     const u64* bk = nullptr; const u64* bv = nullptr; size_t nb = 0; int top_bits = 64;
+    // BCAST: the regions the step was counted against (they stay where they are), the first item of every partition, the plan's total build side
+    BcastSources src; const u32* toff = nullptr; size_t nb_total = 0;
 };
 
 // caller-provided output buffers large enough for ANY result (>= probe rows): the materialising join may run in one pass
@@ -171,10 +181,10 @@ struct BcastState {             // fj_bcast_*: one step of the multi-GPU build-b
     size_t nb_total = 0, nb = 0, np = 0;
     int pieces = 1, evc = 0;
     fjh::Plan plan; fjh::PassIter pit; FjLdsJoinArgs ja{};
-    // a materialising step (the regions carry the build values): counted by fj_bcast_join, the pairs written by fj_emit_pairs afterwards
-    bool with_vals = false, mat_ready = false;
-    const void* mat_base = nullptr; int mat_nsrc = 0; uint64_t mat_off[FJ_WIDE_MAXSRC] = {}, mat_nk[FJ_WIDE_MAXSRC] = {};
-    u64 mat_count = 0; u32 mat_items = 0;
+    // a materialising step (the regions carry the build values): counted by fj_bcast_join against `src`; fj_bcast_finish hands
+    // what the pairs need to the context's pending slot, and fj_emit_pairs writes them
+    bool with_vals = false;
+    fjh::BcastSources src;
 };
 
 struct fj_ctx {
@@ -253,8 +263,11 @@ int run_passes(fj_ctx* c, PassIter& it, const u64* keys, const u64* vals, hipStr
 int clear_plan_scalars(fj_ctx* c, hipStream_t s);
 void begin_plan(fj_ctx* c);
 void end_plan(fj_ctx* c);
+void drop_pending(fj_ctx* c);
+int begin_step(fj_ctx* c, const char* who);
 int read_scalars(fj_ctx* c, hipStream_t s);
 float ev_ms(fj_ctx* c, int a, int b);
+void plan_timings(fj_ctx* c, const Plan& plan, u64 partitions, int evc, fj_timings* t);
 int stamps_begin(unsigned long long** dbg, hipStream_t s);
 int stamps_report(const char* label, const unsigned long long* dbg, u32 nitems, hipStream_t s);
 
@@ -268,6 +281,11 @@ int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, 
                 size_t probe_piece_rows = 0);
 int stream_append_build(fj_ctx* c, const u64* d_bk, size_t n, hipStream_t s);
 int stream_flush_build(fj_ctx* c, StreamState& st, hipStream_t s);
+int stream_abort(fj_ctx* c);
+
+// ---- build broadcast (fj_bcast.hip) ----
+int bcast_emit_launch(fj_ctx* c, const Pending& pd, u64* d_ok, u64* d_ov, hipStream_t s);
+void drop_bcast_result_in(fj_ctx* c, const void* p, size_t bytes);
 
 // ---- host-buffer entry (fj_hostentry.hip) ----
 fj_ctx*& host_ctx();                      // the internal context of fj_join_host (null before its first call)

@@ -188,10 +188,9 @@ int fj_join_host(int algo, int bloom, int materialize,
     }
     fj_ctx* c = host_ctx();
     FJ_ENTER(c);
-    if (c->st.active) {            // an earlier streamed call failed between stream_open and fj_stream_finish: nobody else can
-        HIPCHK(hipDeviceSynchronize());   // abort a stream join on this internal context, so drop it here
-        c->st.active = false;
-    }
+    // an earlier streamed call failed between stream_open and fj_stream_finish: nobody else can abort a stream join on this
+    // internal context, so drop it here
+    if (stream_abort(c) || begin_step(c, "fj_join_host")) return 1;
     void *dbk, *dbv, *dpk;
     if (get_buf(c, W_H_BK, nb * 8, &dbk) || get_buf(c, W_H_BV, nb * 8, &dbv) || get_buf(c, W_H_PK, np * 8, &dpk)) return 1;
     // pieces: >= 16 MiB (the ring's DMA and memcpy run at full rate), at most 48 of them for the probe side (the streamed

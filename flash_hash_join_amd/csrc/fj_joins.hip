@@ -8,15 +8,17 @@ namespace fjh {
 static int skew_side(fj_ctx* c, PassIter& it, int side, bool vals, const FjChunkSet& in, const std::vector<u32>& off, u64 chunks, int S, int bits_left,
                      int slot, int tiles_slot, u32* d_nt, hipStream_t s);
 
+// The pairs of the pending result (fj_emit_pairs).  A call refused by the checks up front leaves the result pending for another
+// attempt; once the launches are queued the result is consumed, whatever the device then reports.
 int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_timings* t) {
     Pending& pd = c->pend;
     if (!pd.valid) return set_err("fj_emit_pairs: no counted materialising join is pending on this context");
     if (pd.count > cap) return set_err("fj_emit_pairs: output capacity %zu < %llu pairs", cap, (unsigned long long)pd.count);
+    if (pd.count > 0 && (((uintptr_t)d_ok | (uintptr_t)d_ov) & 7)) return set_err("output buffers must be 8-byte aligned");
     HIPCHK(hipEventRecord(c->ev[E_EMIT0], s));
     if (pd.count > 0) {
-        if (((uintptr_t)d_ok | (uintptr_t)d_ov) & 7) return set_err("output buffers must be 8-byte aligned");
         void* p;
-        if (pd.path == 0) {
+        if (pd.kind == Pending::LDS) {
             if (pd.has_dups) {
                 // duplicate build keys: the reference's radix path keeps the FIRST occurrence (stable partition +
                 // insert_local, hash_join.cpp:125).  Re-partition the build side with row indices as payload; the
@@ -67,35 +69,39 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
                 pd.lds2.dedup = pd.has_dups ? 1u : 0u; pd.lds2.orig_vals = pd.has_dups ? pd.bv : nullptr; pd.lds2.dbg = nullptr;
                 HIPCHK(fj_launch_lds_emit_retry(pd.lds2, s, false));  // (the tagged emit kernel over every item of the set: a few hundred items)
             }
-        } else if (pd.path == 2) {           // many-to-many: count per item -> scan -> emit
+        } else if (pd.kind == Pending::MANY) {      // many-to-many: count per item -> scan -> emit
             if (get_buf(c, W_OUT_OFF, ((size_t)pd.nitems + 1) * 8, &p)) return 1;
             HIPCHK(fj_launch_scan_u32_to_u64(pd.lds.part_count, (u64*)p, pd.nitems, s));
             pd.lds.out_off = (const u64*)p; pd.lds.out_keys = d_ok; pd.lds.out_vals = d_ov;
             HIPCHK(fj_launch_mm_join(pd.lds, true, s));
-        } else {
+        } else if (pd.kind == Pending::HBM_TABLE) {
             if (get_buf(c, W_OUT_OFF, ((size_t)pd.gt_grid + 1) * 8, &p)) return 1;
             HIPCHK(fj_launch_scan_u32_to_u64(pd.gt.wg_count, (u64*)p, pd.gt_grid, s));
             pd.gt.out_off = (const u64*)p; pd.gt.out_keys = d_ok; pd.gt.out_vals = d_ov;
             HIPCHK(fj_launch_gt_probe(pd.gt, true, pd.gt_grid, s));
+        } else {                                    // a build-broadcast step: the pair writer over the regions (csrc/fj_bcast.hip)
+            if (bcast_emit_launch(c, pd, d_ok, d_ov, s)) return 1;
         }
     }
+    pd.valid = false;
     HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
     if (pd.count > 0) {
         // the emitting kernel can still refuse an item (a table that the counting pass's stricter cuckoo table accepted should
         // never do so, but nothing else enforces that): unwritten output rows must not be handed back with status 0
         if (read_scalars(c, s)) return 1;
-        if (pd.path == 0 && (c->h_sc->err & FJ_STAT_EMIT_RETRY)) {
+        if (pd.kind == Pending::LDS && (c->h_sc->err & FJ_STAT_EMIT_RETRY)) {
             // the cuckoo emit kernel marked items whose table overflowed its stash: those are redone on the tagged table
             HIPCHK(fj_launch_lds_emit_retry(pd.lds, s));
             HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
             if (read_scalars(c, s)) return 1;
             if (t) t->lds_retries += 1;
         }
-        if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_POOL)) { pd.valid = false; return set_err("fj_emit_pairs: the emitting pass could not place every partition in LDS (device error word 0x%x)", c->h_sc->err); }
+        if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_POOL)) return set_err("fj_emit_pairs: the emitting pass could not place every partition in LDS (device error word 0x%x)", c->h_sc->err);
+        if (pd.kind == Pending::BCAST && (c->h_sc->err & FJ_STAT_RETRY))
+            return set_err("internal error: a partition the counting kernel accepted does not fit the pair writer's table (fj_emit_pairs)");
     }
     HIPCHK(hipStreamSynchronize(s));
     if (t) { t->emit_ms = ev_ms(c, E_EMIT0, E_EMIT1); t->total_ms += t->emit_ms; t->probe_phase_ms += t->emit_ms; }
-    pd.valid = false;
     return 0;
 }
 
@@ -133,10 +139,7 @@ int join_global(fj_ctx* c, int bloom, int materialize, const u64* bk, const u64*
     t->join_ms = ev_ms(c, E_PPART, E_JOIN);
     t->probe_phase_ms = t->join_ms;
     t->total_ms = ev_ms(c, E_START, E_JOIN);
-    c->pend.valid = false;
-    if (materialize) {
-        c->pend.valid = true; c->pend.path = 1; c->pend.gt = a; c->pend.gt_grid = grid; c->pend.count = *out_count;
-    }
+    if (materialize) { c->pend.valid = true; c->pend.kind = Pending::HBM_TABLE; c->pend.gt = a; c->pend.gt_grid = grid; c->pend.count = *out_count; }
     return 0;
 }
 
@@ -261,7 +264,6 @@ int skew_join(fj_ctx* c, const FjLdsJoinArgs& ja, const Plan& plan, int top_bits
 // launch the per-partition join over the final chunk sets, read back count + error word, fill the timings
 int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& plan, size_t np, const PassIter& pit, hipStream_t s,
                     fj_timings* t, int evc, u64* out_count, bool* lds_full, int top_bits, SingleOut* so) {
-    c->pend.has_second = false; c->pend.dups_main = false;
     ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;      // (an owner of a shuffled join holds a slice of the plan's partitions)
     const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
     void* p;
@@ -303,16 +305,9 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
         if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
         if (!(c->h_sc->err & (FJ_STAT_DUPS | FJ_STAT_EMIT_RETRY | FJ_ERR_LDS_FULL | FJ_ERR_OUTCAP))) {
             end_plan(c);
-            t->path = 0; t->passes = plan.npass; t->radix_bits = plan.bits; t->partitions = ja.nparts; t->lds_retries = 0;
-            t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-            t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-            t->probe_phase_ms = ev_ms(c, E_BUILD, E_JOIN);
-            t->total_ms = ev_ms(c, E_START, E_JOIN);
-            for (int i = 0; i < evc && i < 4; ++i) t->probe_part_kernel_ms[i] = ev_ms(c, E_PK0 + 2 * i, E_PK0 + 2 * i + 1);
-            t->bloom_level = plan.bloom_level;
-            if (plan.bloom_level > 0) { t->filter_ms = ev_ms(c, E_BF0, E_BF1); t->filter_survivors = c->h_sc->bloom_survivors; }
+            plan_timings(c, plan, ja.nparts, evc, t);
+            t->lds_retries = 0;
             *out_count = c->h_sc->total;
-            c->pend.valid = false;
             so->done = true;
             return 0;
         }
@@ -384,23 +379,11 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
     }
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
     end_plan(c);                              // every prepared pass ran its bookkeeping: the self-cleaning buffers are clean
-    t->path = 0; t->passes = plan.npass; t->radix_bits = plan.bits; t->partitions = ja.nparts;
-    // one-shot joins: build_phase_ms = the build relation's passes, probe_phase_ms = first probe-side pass .. end of the join
-    // (disjoint intervals of one stream).  Streamed joins overwrite both in fj_stream_finish.
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = ev_ms(c, E_BUILD, E_JOIN);
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
-    for (int i = 0; i < evc && i < 4; ++i) t->probe_part_kernel_ms[i] = ev_ms(c, E_PK0 + 2 * i, E_PK0 + 2 * i + 1);
-    t->bloom_level = plan.bloom_level;
-    if (plan.bloom_level > 0) {
-        t->filter_ms = ev_ms(c, E_BF0, E_BF1); t->filter_survivors = c->h_sc->bloom_survivors;
-    }
+    plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL) { *lds_full = true; return 0; }
     *out_count = c->h_sc->total;
-    c->pend.valid = false;
     if (materialize) {
-        c->pend.valid = true; c->pend.path = 0; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count;
+        c->pend.valid = true; c->pend.kind = Pending::LDS; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count;
         c->pend.has_dups = (c->h_sc->err & FJ_STAT_DUPS) != 0 || c->pend.dups_main;
     }
     return 0;
@@ -504,14 +487,8 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
     if (c->h_sc->err & FJ_ERR_LDS_FULL)
         return set_err("many-to-many join: a final partition holds more than 4096 build rows (a build key with thousands of duplicates?); not supported");
     *out_count = c->h_sc->total;
-    t->path = 0; t->passes = plan.npass; t->radix_bits = plan.bits; t->partitions = ja.nparts;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = ev_ms(c, E_BUILD, E_JOIN);
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
-    for (int i = 0; i < evc && i < 4; ++i) t->probe_part_kernel_ms[i] = ev_ms(c, E_PK0 + 2 * i, E_PK0 + 2 * i + 1);
-    c->pend.valid = false;
-    if (materialize) { c->pend.valid = true; c->pend.path = 2; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count; c->pend.has_dups = false; }
+    plan_timings(c, plan, ja.nparts, evc, t);
+    if (materialize) { c->pend.valid = true; c->pend.kind = Pending::MANY; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count; }
     return 0;
 }
 
@@ -525,20 +502,18 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                    const uint64_t* d_bk, const uint64_t* d_bv, size_t nb, const uint64_t* d_pk, size_t np,
                    void* stream, int hash_top_bits, uint64_t* out_count,
                    uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, fj_timings* timings) {
-    if (!c) return set_err("fj_join_device: null context");
     const bool many = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     if (algo < 0 || algo > 2) return set_err("fj_join_device: unknown algo %d", algo);
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_join_device: hash_top_bits must be 64 or 48");
-    if (c->st.active) return set_err("fj_join_device: a stream join is open on this context (fj_stream_finish it first)");
     if ((nb && (!d_bk || !d_bv)) || (np && !d_pk)) return set_err("fj_join_device: null input pointer");
     if (((uintptr_t)d_bk | (uintptr_t)d_bv | (uintptr_t)d_pk) & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
     FJ_ENTER(c);
+    if (begin_step(c, "fj_join_device")) return 1;
     hipStream_t s = (hipStream_t)stream;
     fj_timings t; memset(&t, 0, sizeof t);
     t.sampled_hit_bp = -1;
     u64 count = 0;
-    c->pend.valid = false;
     const Options& opt = options();
     bool use_radix = algo == FJ_ALGO_RADIX || (algo == FJ_ALGO_ADAPTIVE && nb >= opt.radix_threshold) ||
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
@@ -573,8 +548,6 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
 }
 
 int fj_emit_pairs(fj_ctx* c, uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, void* stream, fj_timings* timings) {
-    if (!c) return set_err("fj_emit_pairs: null context");
-    if (c->bc.mat_ready) return fj_bcast_emit(c, d_out_keys, d_out_vals, out_capacity, stream);      // a materialising build-broadcast step (csrc/fj_bcast.hip)
     FJ_ENTER(c);
     fj_timings t = last_timings();
     if (emit_pending(c, d_out_keys, d_out_vals, out_capacity, (hipStream_t)stream, &t)) return 1;
@@ -585,7 +558,6 @@ int fj_emit_pairs(fj_ctx* c, uint64_t* d_out_keys, uint64_t* d_out_vals, size_t 
 
 int fj_owner_split(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, size_t n, int nranks,
                    uint64_t* d_out_keys, uint64_t* d_out_vals, uint64_t* h_counts, void* stream) {
-    if (!c) return set_err("fj_owner_split: null context");
     if (nranks < 1 || nranks > 64) return set_err("fj_owner_split: nranks must be 1..64");
     FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
@@ -606,7 +578,6 @@ int fj_owner_split(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, si
 // open: plan + first-pass pools of both sides; append_*: one first-pass launch per piece (launches accumulate
 // into the same chunk pool); advance_probe: the probe side's remaining passes (so that they can overlap an
 int fj_owner_hist(fj_ctx* c, const uint64_t* d_keys, size_t n, int nranks, uint64_t* h_counts, void* stream) {
-    if (!c) return set_err("fj_owner_hist: null context");
     if (nranks < 1 || nranks > 64) return set_err("fj_owner_hist: nranks must be 1..64");
     FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
@@ -622,7 +593,6 @@ int fj_owner_hist(fj_ctx* c, const uint64_t* d_keys, size_t n, int nranks, uint6
 
 int fj_owner_scatter(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, size_t n, int nranks, const uint64_t* h_counts,
                      uint64_t* d_out_keys, uint64_t* d_out_vals, void* stream) {
-    if (!c) return set_err("fj_owner_scatter: null context");
     if (nranks < 1 || nranks > 64) return set_err("fj_owner_scatter: nranks must be 1..64");
     FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
@@ -645,13 +615,11 @@ int fj_owner_scatter(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, 
 size_t fj_bloom_filter_words(void) { return ((size_t)1 << FJ_PREFILTER_BITS) * FJ_BLOOM_WORDS + 4; }   // + header (variant)
 
 int fj_bloom_export(fj_ctx* c, const uint64_t* d_build_keys, size_t nb, int hash_top_bits, uint32_t* d_filters, void* stream) {
-    if (!c) return set_err("fj_bloom_export: null context");
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_bloom_export: hash_top_bits must be 64 or 48");
-    if (c->st.active) return set_err("fj_bloom_export: a stream join is open on this context (fj_stream_finish it first)");
     if (!d_filters || (nb && !d_build_keys) || ((uintptr_t)d_build_keys & 15) || ((uintptr_t)d_filters & 15)) return set_err("fj_bloom_export: null or misaligned pointer");
     FJ_ENTER(c);
+    if (begin_step(c, "fj_bloom_export")) return 1;
     hipStream_t s = (hipStream_t)stream;
-    c->pend.valid = false;                                 // the passes below reuse the chunk pools a pending emit would read
     const u32 nbuckets = 1u << FJ_PREFILTER_BITS;
     if (nb == 0) {                                          // empty filters reject everything
         HIPCHK(hipMemsetAsync(d_filters, 0, fj_bloom_filter_words() * 4, s));
@@ -674,17 +642,15 @@ int fj_bloom_export(fj_ctx* c, const uint64_t* d_build_keys, size_t nb, int hash
 
 int fj_bloom_prefilter(fj_ctx* c, const uint64_t* d_probe_keys, size_t n, int hash_top_bits, const uint32_t* d_filters,
                        uint64_t* d_out_keys, size_t out_capacity, uint64_t* out_n, void* stream) {
-    if (!c) return set_err("fj_bloom_prefilter: null context");
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_bloom_prefilter: hash_top_bits must be 64 or 48");
-    if (c->st.active) return set_err("fj_bloom_prefilter: a stream join is open on this context (fj_stream_finish it first)");
     if (!d_filters || !out_n || (n && (!d_probe_keys || !d_out_keys)) || ((uintptr_t)d_probe_keys & 15) || ((uintptr_t)d_filters & 15) || ((uintptr_t)d_out_keys & 7))
         return set_err("fj_bloom_prefilter: null or misaligned pointer");
     if (out_capacity < n) return set_err("fj_bloom_prefilter: output capacity %zu < %zu input rows", out_capacity, n);
+    FJ_ENTER(c);
+    if (begin_step(c, "fj_bloom_prefilter")) return 1;
     *out_n = 0;
     if (n == 0) return 0;
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
-    c->pend.valid = false;                                 // the passes below reuse the chunk pools a pending emit would read
     Plan plan; plan.bits = FJ_PREFILTER_BITS; plan_passes(plan, true);
     plan.bloom_level = 1;
     begin_plan(c);

@@ -357,6 +357,18 @@ void begin_plan(fj_ctx* c) {
 }
 void end_plan(fj_ctx* c) { c->plan_in_flight = false; }
 
+void drop_pending(fj_ctx* c) { c->pend = Pending(); }
+
+// Entry of a C-ABI call that starts new work on the context's pools (behind FJ_ENTER): refused while a stream join is open (who: the
+// entry's name; null: not refused - the entries that open a stream join replace it, and the partition diagnostic), and a result that
+// was counted but not emitted is dropped: what it points at is about to be overwritten.  (Not part of begin_plan: emit_pending runs
+// passes under its result.)
+int begin_step(fj_ctx* c, const char* who) {
+    if (who && c->st.active) return set_err("%s: a stream join is open on this context (fj_stream_finish it first)", who);
+    drop_pending(c);
+    return 0;
+}
+
 int read_scalars(fj_ctx* c, hipStream_t s) {
     HIPCHK(hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(Scalars), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -364,6 +376,19 @@ int read_scalars(fj_ctx* c, hipStream_t s) {
 }
 
 float ev_ms(fj_ctx* c, int a, int b) { float ms = 0.f; (void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]); return ms; }
+
+// the timings of a partitioned plan whose join has been read back.  build_phase_ms = the build relation's passes, probe_phase_ms =
+// first probe-side pass .. end of the join (disjoint intervals of one stream; streamed joins overwrite both in fj_stream_finish)
+void plan_timings(fj_ctx* c, const Plan& plan, u64 partitions, int evc, fj_timings* t) {
+    t->path = 0; t->passes = plan.npass; t->radix_bits = plan.bits; t->partitions = partitions;
+    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
+    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
+    t->probe_phase_ms = ev_ms(c, E_BUILD, E_JOIN);
+    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    for (int i = 0; i < evc && i < 4; ++i) t->probe_part_kernel_ms[i] = ev_ms(c, E_PK0 + 2 * i, E_PK0 + 2 * i + 1);
+    t->bloom_level = plan.bloom_level;
+    if (plan.bloom_level > 0) { t->filter_ms = ev_ms(c, E_BF0, E_BF1); t->filter_survivors = c->h_sc->bloom_survivors; }
+}
 
 // diagnostic: per-item phase stamps (s_memrealtime, 100 MHz) written by thread 0 of the first 4096 workgroups of a join kernel
 int stamps_begin(unsigned long long** dbg, hipStream_t s) {
@@ -498,16 +523,14 @@ void fj_ctx_reserve_cus(fj_ctx* c, unsigned n) { if (c) c->reserve_cus = n; }
 int fj_ctx_trim(fj_ctx* c) {
     if (!c) c = host_ctx();                       // NULL: the context behind fj_join_host (nothing to do before its first call)
     if (!c) return 0;
-    if (c->st.active) return set_err("fj_ctx_trim: a stream join is open on this context (fj_stream_finish it first)");
     FJ_ENTER(c);
+    if (begin_step(c, "fj_ctx_trim")) return 1;
     HIPCHK(hipDeviceSynchronize());               // kernels of earlier joins may still read the buffers
-    c->pend.valid = false;
     for (auto& b : c->bufs) if (b.p) { HIPCHK(hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
     c->ws_bytes = 0;
     return 0;
 }
 int fj_generate_build(fj_ctx* c, uint64_t* d_keys, uint64_t* d_vals, uint64_t first, size_t n, void* stream) {
-    if (!c) return set_err("fj_generate_build: null context");
     FJ_ENTER(c);
     HIPCHK(fj_launch_gen_build(d_keys, d_vals, first, n, (hipStream_t)stream));
     return 0;
@@ -515,7 +538,6 @@ int fj_generate_build(fj_ctx* c, uint64_t* d_keys, uint64_t* d_vals, uint64_t fi
 
 int fj_generate_probe(fj_ctx* c, uint64_t* d_keys, uint64_t first, size_t n, uint64_t build_total, uint64_t seed,
                       uint32_t hit_bp, uint64_t* h_expected_hits, void* stream) {
-    if (!c) return set_err("fj_generate_probe: null context");
     if (build_total == 0) return set_err("fj_generate_probe: build_total must be > 0");
     FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
@@ -533,9 +555,9 @@ int fj_generate_probe(fj_ctx* c, uint64_t* d_keys, uint64_t first, size_t n, uin
 int fj_debug_partition(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, size_t n, int total_bits,
                        int hash_top_bits, void* stream, uint64_t* h_out_keys, uint64_t* h_out_vals,
                        uint32_t* h_bucket_of, uint64_t* h_nvalid) {
-    if (!c) return set_err("fj_debug_partition: null context");
     if (total_bits < 2 || total_bits > 24) return set_err("fj_debug_partition: total_bits must be 2..24");
     FJ_ENTER(c);
+    if (begin_step(c, nullptr)) return 1;
     hipStream_t s = (hipStream_t)stream;
     Plan plan; plan.bits = total_bits;
     plan_passes(plan, true);

@@ -78,9 +78,9 @@ int stream_flush_build(fj_ctx* c, StreamState& st, hipStream_t s) {
 
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,
                 size_t probe_piece_rows) {
+    if (begin_step(c, nullptr)) return 1;         // (an open stream join is replaced)
     StreamState& st = c->st;
     st = StreamState();
-    c->pend.valid = false;
     st.plan = make_plan(nb_bound, top_bits);
     st.top_bits = top_bits; st.np_bound = np_bound; st.nb_bound = nb_bound;
     st.p_appends_left = (u32)probe_appends; st.b_appends_left = (u32)build_appends;
@@ -114,11 +114,19 @@ int stream_append_build(fj_ctx* c, const u64* d_bk, size_t n, hipStream_t s) {
     return 0;
 }
 
+// Drop an open stream join without a result (an error on the caller's side between two appends): the context is free for
+// other joins again; the buffers the abandoned passes left half-filled are re-zeroed by the next plan (plan_in_flight).
+int stream_abort(fj_ctx* c) {
+    if (!c->st.active) return 0;
+    HIPCHK(hipDeviceSynchronize());               // launched passes still read the caller's pieces
+    c->st.active = false;
+    return 0;
+}
+
 }  // namespace fjh
 extern "C" {
 
 int fj_stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, void* stream, int hash_top_bits) {
-    if (!c) return set_err("fj_stream_open: null context");
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_stream_open: hash_top_bits must be 64 or 48");
     if (build_appends < 1 || build_appends > 64 || probe_appends < 1 || probe_appends > 64)
         return set_err("fj_stream_open: build_appends and probe_appends must be 1..64");
@@ -127,14 +135,13 @@ int fj_stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_boun
 }
 
 int fj_stream_append_build(fj_ctx* c, const uint64_t* d_bk, size_t n, void* stream) {
-    if (!c || !c->st.active) return set_err("fj_stream_append_build: no stream join is open on this context");
     FJ_ENTER(c);
+    if (!c->st.active) return set_err("fj_stream_append_build: no stream join is open on this context");
     return stream_append_build(c, (const u64*)d_bk, n, (hipStream_t)stream);
 }
 
 int fj_stream_begin(fj_ctx* c, const uint64_t* d_bk, const uint64_t* d_bv, size_t nb, size_t np_bound, int max_appends,
                     void* stream, int hash_top_bits) {
-    if (!c) return set_err("fj_stream_begin: null context");
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_stream_begin: hash_top_bits must be 64 or 48");
     if (max_appends < 1 || max_appends > 64) return set_err("fj_stream_begin: max_appends must be 1..64");
     if (nb && (!d_bk || !d_bv)) return set_err("fj_stream_begin: null input pointer");
@@ -147,14 +154,14 @@ int fj_stream_begin(fj_ctx* c, const uint64_t* d_bk, const uint64_t* d_bv, size_
 }
 
 int fj_stream_append_probe(fj_ctx* c, const uint64_t* d_pk, size_t n, void* stream) {
-    if (!c || !c->st.active) return set_err("fj_stream_append_probe: no stream join is open on this context");
+    FJ_ENTER(c);
     StreamState& st = c->st;
+    if (!st.active) return set_err("fj_stream_append_probe: no stream join is open on this context");
     if (n == 0) return 0;
     if (st.probe_done) return set_err("fj_stream_append_probe: the probe side is already closed");
     if (!d_pk || ((uintptr_t)d_pk & 15)) return set_err("fj_stream_append_probe: probe piece must be a 16-byte aligned device pointer");
     if (st.p_appends_left == 0) return set_err("fj_stream_append_probe: more pieces than probe_appends");
     if (st.np_seen + n > st.np_bound) return set_err("fj_stream_append_probe: more probe rows than np_bound");
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
     --st.p_appends_left; st.np_seen += n;
     st.ppieces.emplace_back((const u64*)d_pk, n);
@@ -166,10 +173,10 @@ int fj_stream_append_probe(fj_ctx* c, const uint64_t* d_pk, size_t n, void* stre
 }
 
 int fj_stream_advance_probe(fj_ctx* c, void* stream) {
-    if (!c || !c->st.active) return set_err("fj_stream_advance_probe: no stream join is open on this context");
-    StreamState& st = c->st;
-    if (st.probe_done) return 0;
     FJ_ENTER(c);
+    StreamState& st = c->st;
+    if (!st.active) return set_err("fj_stream_advance_probe: no stream join is open on this context");
+    if (st.probe_done) return 0;
     hipStream_t s = (hipStream_t)stream;
     st.probe_done = true;
     if (st.plan.npass > 0 && st.np_seen > 0) {
@@ -179,22 +186,16 @@ int fj_stream_advance_probe(fj_ctx* c, void* stream) {
     return 0;
 }
 
-// Drop an open stream join without a result (an error on the caller's side between two appends): the context is free for
-// other joins again; the buffers the abandoned passes left half-filled are re-zeroed by the next plan (plan_in_flight).
 int fj_stream_abort(fj_ctx* c) {
-    if (!c) return set_err("fj_stream_abort: null context");
     FJ_ENTER(c);
-    if (!c->st.active) return 0;
-    HIPCHK(hipDeviceSynchronize());               // launched passes still read the caller's pieces
-    c->st.active = false;
-    return 0;
+    return stream_abort(c);
 }
 
 int fj_stream_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* timings) {
-    if (!c || !c->st.active) return set_err("fj_stream_finish: no stream join is open on this context");
-    StreamState& st = c->st;
-    st.active = false;
     FJ_ENTER(c);
+    StreamState& st = c->st;
+    if (!st.active) return set_err("fj_stream_finish: no stream join is open on this context");
+    st.active = false;
     hipStream_t s = (hipStream_t)stream;
     fj_timings t; memset(&t, 0, sizeof t);
     u64 count = 0;
@@ -213,7 +214,7 @@ int fj_stream_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* t
         if (mat && c->pend.valid && (c->pend.has_dups || c->pend.has_second)) {
             // first-occurrence semantics for duplicate build keys (and the re-partitioning of an oversized partition) need the
             // caller's flat build arrays, which a shuffled stream never sees: the caller takes the owner-scatter form instead
-            c->pend.valid = false;
+            drop_pending(c);
             return set_err("shuffled materialising join: duplicate build keys or an oversized partition (use the owner-scatter form)");
         }
         if (lds_full && st.shuffled)
@@ -246,7 +247,7 @@ int fj_stream_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* t
         t.path = 0; t.passes = 0; t.partitions = 1;
         t.total_ms = ev_ms(c, E_START, E_JOIN);
         // a materialising shuffled join with an empty side has counted zero pairs: the fj_emit_pairs that follows finds that
-        if (st.shuffled && st.with_vals) { c->pend = Pending(); c->pend.valid = true; c->pend.count = 0; }
+        if (st.shuffled && st.with_vals) { drop_pending(c); c->pend.valid = true; }
     }
     if (!t.fell_back) {
         t.build_phase_ms = ev_ms(c, E_SB0, E_SB1);              // the two sides may have run in either order
@@ -326,7 +327,6 @@ int pack_plan_tail(fj_ctx* c, const u64* filters, hipStream_t s) {
 }  // namespace
 
 int fj_shuffle_pack_begin(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_vals, size_t n, size_t nb_total, int nranks, int defer_plan, void* stream) {
-    if (!c) return set_err("fj_shuffle_pack_begin: null context");
     if (n && !d_keys) return set_err("fj_shuffle_pack_begin: null pointer");
     if (((uintptr_t)d_keys | (uintptr_t)d_vals) & 15) return set_err("fj_shuffle_pack_begin: pointers must be 16-byte aligned");
     if (defer_plan && d_vals) return set_err("fj_shuffle_pack_begin: the precheck is for probe pieces (keys only)");
@@ -363,10 +363,9 @@ int fj_shuffle_pack_begin(fj_ctx* c, const uint64_t* d_keys, const uint64_t* d_v
 }
 
 int fj_shuffle_pack_filter(fj_ctx* c, const void* d_part_filters, void* stream) {
-    if (!c) return set_err("fj_shuffle_pack_filter: null context");
-    if (!c->pk.deferred) return set_err("fj_shuffle_pack_filter: no fj_shuffle_pack_begin(defer_plan = 1) is pending on this context");
     if ((uintptr_t)d_part_filters & 7) return set_err("fj_shuffle_pack_filter: misaligned filters");
     FJ_ENTER(c);
+    if (!c->pk.deferred) return set_err("fj_shuffle_pack_filter: no fj_shuffle_pack_begin(defer_plan = 1) is pending on this context");
     return pack_plan_tail(c, (const u64*)d_part_filters, (hipStream_t)stream);
 }
 
@@ -438,16 +437,15 @@ extern "C" {
 
 int fj_stream_open_shuffled(fj_ctx* c, size_t nb_total, int nranks, int rank, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends,
                             int with_vals, void* stream) {
-    if (!c) return set_err("fj_stream_open_shuffled: null context");
     if (rank < 0 || rank >= nranks) return set_err("fj_stream_open_shuffled: rank %d of %d", rank, nranks);
     if (build_appends < 1 || build_appends > 64 || probe_appends < 1 || probe_appends > 64) return set_err("fj_stream_open_shuffled: build_appends and probe_appends must be 1..64");
     Plan plan;
     if (shuffle_plan(nb_total, nranks, &plan)) return 1;
     FJ_ENTER(c);
+    if (begin_step(c, nullptr)) return 1;         // (an open stream join is replaced)
     hipStream_t s = (hipStream_t)stream;
     StreamState& st = c->st;
     st = StreamState();
-    c->pend.valid = false;
     st.plan = plan; st.top_bits = 64; st.shuffled = true; st.with_vals = with_vals != 0;
     const u32 F0 = 1u << plan.fan_log[0];
     st.b_lo = (u32)(((u64)rank * F0 + nranks - 1) / nranks);                     // first bucket b with (b * nranks) >> log2(F0) == rank
@@ -495,13 +493,13 @@ int stream_append_chunks(fj_ctx* c, int side, const void* d_chunks, const u64* d
 }  // namespace
 
 int fj_stream_append_build_chunks(fj_ctx* c, const void* d_chunks, const uint64_t* d_vals, uint32_t* d_dir, size_t nchunks, void* stream) {
-    if (!c || !c->st.active || !c->st.shuffled) return set_err("fj_stream_append_build_chunks: no shuffled stream join is open on this context");
+    FJ_ENTER(c);
     StreamState& st = c->st;
+    if (!st.active || !st.shuffled) return set_err("fj_stream_append_build_chunks: no shuffled stream join is open on this context");
     if (st.build_done) return set_err("fj_stream_append_build_chunks: the build side is already closed");
     if (st.b_appends_left == 0) return set_err("fj_stream_append_build_chunks: more pieces than build_appends");
     if (nchunks && (!d_chunks || !d_dir || ((uintptr_t)d_chunks & 15) || ((uintptr_t)d_vals & 15))) return set_err("fj_stream_append_build_chunks: null or misaligned piece");
     if (nchunks && st.with_vals != (d_vals != nullptr)) return set_err("fj_stream_append_build_chunks: the stream was opened %s values", st.with_vals ? "with" : "without");
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
     --st.b_appends_left;
     if (nchunks) { st.nb_seen += nchunks * FJ_CHUNK; if (stream_append_chunks(c, 0, d_chunks, (const u64*)d_vals, d_dir, nchunks, s)) return 1; }
@@ -510,11 +508,11 @@ int fj_stream_append_build_chunks(fj_ctx* c, const void* d_chunks, const uint64_
 }
 
 int fj_stream_export_part_filters(fj_ctx* c, void* d_out, void* stream) {
-    if (!c || !c->st.active || !c->st.shuffled) return set_err("fj_stream_export_part_filters: no shuffled stream join is open on this context");
+    FJ_ENTER(c);
     StreamState& st = c->st;
+    if (!st.active || !st.shuffled) return set_err("fj_stream_export_part_filters: no shuffled stream join is open on this context");
     if (!st.build_done) return set_err("fj_stream_export_part_filters: the build side is not complete yet");
     if (!d_out || ((uintptr_t)d_out & 7)) return set_err("fj_stream_export_part_filters: null or misaligned output");
-    FJ_ENTER(c);
     hipStream_t s = (hipStream_t)stream;
     const u64 rest = 1ull << (st.plan.bits - st.plan.fan_log[0]);
     const u64 nparts = (u64)st.nbk * rest;                                     // (the padding buckets of the owner's range have no partitions to speak for)
@@ -526,12 +524,12 @@ int fj_stream_export_part_filters(fj_ctx* c, void* d_out, void* stream) {
 }
 
 int fj_stream_append_probe_chunks(fj_ctx* c, const void* d_chunks, uint32_t* d_dir, size_t nchunks, void* stream) {
-    if (!c || !c->st.active || !c->st.shuffled) return set_err("fj_stream_append_probe_chunks: no shuffled stream join is open on this context");
+    FJ_ENTER(c);
     StreamState& st = c->st;
+    if (!st.active || !st.shuffled) return set_err("fj_stream_append_probe_chunks: no shuffled stream join is open on this context");
     if (st.probe_done) return set_err("fj_stream_append_probe_chunks: the probe side is already closed");
     if (st.p_appends_left == 0) return set_err("fj_stream_append_probe_chunks: more pieces than probe_appends");
     if (nchunks && (!d_chunks || !d_dir || ((uintptr_t)d_chunks & 15))) return set_err("fj_stream_append_probe_chunks: null or misaligned piece");
-    FJ_ENTER(c);
     --st.p_appends_left;
     if (nchunks == 0) return 0;
     if (!st.probe_prepared) {

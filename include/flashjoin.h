@@ -155,7 +155,9 @@ int fj_last_timings(fj_timings* out);
  * stream is a hipStream_t (NULL = default stream).  hash_top_bits is 64 for a single-GPU join and
  * 48 after fj_owner_split (the top 16 hash bits chose the owner GPU).
  * Materialising joins: with d_out_keys == NULL the call counts only and keeps its partitions
- * resident; fj_emit_pairs() then writes exactly *out_count pairs into caller-allocated buffers.
+ * resident; fj_emit_pairs() then writes exactly *out_count pairs into caller-allocated buffers.  A context holds ONE such
+ * pending result (of this call, a materialising stream join or build-broadcast step): the next call that starts new work on the
+ * context drops it; an fj_emit_pairs that is refused (capacity below the count, misaligned buffers) leaves it pending.
  * With d_out_keys != NULL and out_capacity >= count both steps happen in this call.  With out_capacity >= np - room for
  * ANY result, what the reference allocates too (hash_join.cpp:330-334) - a partitioned join with unique build keys runs in
  * ONE pass over the probe side (no counting pass; option "mat_single_pass", default 1): the first *out_count rows of the
@@ -201,7 +203,8 @@ int fj_bcast_plan(size_t nb_total, int* bits, uint32_t* nparts, int* mid_bytes);
  * copy into the 7-byte wire format (a rank's own share straight into its receive buffer), the exchange, the owner's second
  * pass - on three streams, the host blocking once per piece; a failure on any rank is reported by every rank.
  *   fj_dist_unique_id           - rank 0: 128 bytes for the other ranks (any out-of-band channel), as ncclGetUniqueId
- *   fj_dist_comm_create         - every rank, after selecting its device and creating its fj_ctx: ncclCommInitRank inside.
+ *   fj_dist_comm_create         - every rank, after selecting its device and creating its fj_ctx (which outlives the
+ *                                 communicator: fj_dist_comm_destroy drops a result the context holds in its buffers): ncclCommInitRank inside.
  *                                 RCCL is bound at run time (dlopen of librccl.so.1): a host that never calls this needs neither
  *                                 the library nor its headers.  Payload: grouped ncclSend / ncclRecv on an exchange stream;
  *                                 control collectives on a second communicator (ncclCommSplit) so that they do not queue behind

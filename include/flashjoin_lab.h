@@ -104,7 +104,7 @@ int fj_part_filter_sample(fj_ctx* ctx, const uint64_t* d_raw_keys, size_t n, siz
  * writes the build values as a fourth part of the region (u64[n]: 14 bytes per build row; fj_bcast_region_bytes / _piece_span with
  * with_vals = 1 / part 3); fj_bcast_join counts with the counting step's kernel (a probe row counts once however many copies of its
  * key the build side holds; partitions of more than ~6000 keys are refused: they must fit the pair writer's table); fj_bcast_finish
- * leaves the regions and the probe partitions in place and fj_emit_pairs (fj_bcast_emit) writes this rank's pairs - (probe key, value
+ * leaves the regions and the probe partitions in place and fj_emit_pairs writes this rank's pairs - (probe key, value
  * of one copy of the build key) of its OWN probe rows: in this form the pairs stay with the probe rows.
  */
 size_t fj_bcast_region_bytes(size_t nb_total, size_t nkeys, int with_vals);
@@ -115,7 +115,6 @@ int fj_bcast_probe(fj_ctx* ctx, const uint64_t* d_probe_keys, size_t np, size_t 
 int fj_bcast_join(fj_ctx* ctx, const void* d_base, int nsrc, const uint64_t* region_off, const uint64_t* nkeys, uint32_t part_lo, uint32_t part_hi, void* stream);
 int fj_bcast_finish(fj_ctx* ctx, void* stream, uint64_t* out_count, fj_timings* timings);
 void fj_bcast_abort(fj_ctx* ctx);
-int fj_bcast_emit(fj_ctx* ctx, uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, void* stream);
 
 /*
  * Sender-side bloom precheck of the owner shuffle (no reference counterpart).  fj_bloom_export: an owner partitions the

@@ -1410,6 +1410,73 @@ def test_build_broadcast_form_materialising_matches_the_oracle(fj, oracle, world
         fj.set_option("plan_target_keys", 4096)
 
 
+def _bcast_mat_step(eng, rng, nb, np_):
+    """One materialising build-broadcast step of a one-rank world, counted and NOT emitted: (count, what must stay alive, the
+    oracle's pairs)."""
+    import torch
+    bk = np.unique(rng.integers(0, 2**64, size=nb, dtype=np.uint64))
+    bv = bk * np.uint64(0x9E3779B97F4A7C15) + np.uint64(3)
+    pk = np.concatenate([rng.choice(bk, np_ // 2), rng.integers(0, 2**64, size=np_ - np_ // 2, dtype=np.uint64)])
+    bk_t, bv_t, pk_t = (torch.from_numpy(x.view(np.int64).copy()).cuda() for x in (bk, bv, pk))
+    nbt = int(bk.size)
+    nparts = eng.bcast_plan(nbt)[1]
+    base = torch.empty(eng.bcast_region_bytes(nbt, nbt, True), dtype=torch.uint8, device="cuda:0")
+    eng.bcast_pack(bk_t, nbt, base, 1, vals=bv_t)
+    assert eng.bcast_pack_bounds(1)[-1] == nbt
+    eng.bcast_probe(pk_t, nbt)
+    eng.bcast_join(base, [0], [nbt], 0, nparts)
+    n = eng.bcast_finish()
+    assert n > 0
+    return n, (bk_t, bv_t, pk_t, base), (bk, bv, pk)
+
+
+def test_stale_build_broadcast_result_is_not_emitted(fj, oracle):
+    """A materialising build-broadcast step whose pairs are never fetched (distributed_join(materialize=True) without return_arrays)
+    must not stand in for the next two-phase materialising join on the same context: the one-shot join (count, then fj_emit_pairs)
+    returns its OWN pairs.  The one-shot join is no bigger than the step on either side."""
+    import torch
+    from flash_hash_join_amd.lab import LabEngine
+    eng = LabEngine("cuda:0")
+    rng = np.random.default_rng(4242)
+    _, keep, _ = _bcast_mat_step(eng, rng, 70_000, 300_000)
+    bk = np.unique(rng.integers(0, 2**64, size=50_000, dtype=np.uint64))
+    bv = rng.integers(0, 2**64, size=bk.size, dtype=np.uint64)
+    pk = np.concatenate([rng.choice(bk, 100_000), rng.integers(0, 2**64, size=100_000, dtype=np.uint64)])
+    exp, ek, ev = oracle.np_join(bk, bv, pk, return_arrays=True)
+    fj.set_option("mat_single_pass", 0)
+    try:
+        n, _, k, v = fj.hash_join_radix(*(torch.from_numpy(x.view(np.int64).copy()).cuda() for x in (bk, bv, pk)), return_arrays=True)
+    finally:
+        fj.set_option("mat_single_pass", 1)
+    assert n == exp
+    assert _digest(oracle, k.cpu().numpy().view(np.uint64), v.cpu().numpy().view(np.uint64)) == _digest(oracle, ek, ev)
+    del keep
+
+
+def test_refused_build_broadcast_emit_leaves_the_result_pending(fj, oracle):
+    """fj_emit_pairs of a materialising build-broadcast step: a call that is refused (output capacity below the count, a misaligned
+    output buffer) writes nothing and leaves the result pending; the next correct call writes the oracle's pairs, and a further
+    one finds nothing pending (as test_c_abi_rejects_bad_arguments asserts for a one-shot join)."""
+    import ctypes
+    import torch
+    from flash_hash_join_amd import _lib
+    from flash_hash_join_amd.lab import LabEngine
+    eng = LabEngine("cuda:0")
+    L = _lib.load()
+    n, keep, (bk, bv, pk) = _bcast_mat_step(eng, np.random.default_rng(77), 40_000, 90_000)
+    exp, ek, ev = oracle.np_join(bk, bv, pk, return_arrays=True)
+    assert n == exp
+    st = torch.cuda.current_stream(0).cuda_stream
+    t = _lib.FjTimings()
+    ok = torch.empty(n + 1, dtype=torch.int64, device="cuda:0"); ov = torch.empty_like(ok)
+    assert L.fj_emit_pairs(eng.ctx, ok.data_ptr(), ov.data_ptr(), n - 1, st, ctypes.byref(t)) == 1 and "capacity" in _lib.last_error()
+    assert L.fj_emit_pairs(eng.ctx, ok.data_ptr() + 4, ov.data_ptr(), n, st, ctypes.byref(t)) == 1 and "aligned" in _lib.last_error()
+    assert L.fj_emit_pairs(eng.ctx, ok.data_ptr(), ov.data_ptr(), n, st, ctypes.byref(t)) == 0
+    assert _digest(oracle, ok[:n].cpu().numpy().view(np.uint64), ov[:n].cpu().numpy().view(np.uint64)) == _digest(oracle, ek, ev)
+    assert L.fj_emit_pairs(eng.ctx, ok.data_ptr(), ov.data_ptr(), n, st, ctypes.byref(t)) == 1 and "no counted" in _lib.last_error()
+    del keep
+
+
 @pytest.mark.parametrize("np_rank", [200_000, 4_000_000])
 def test_build_broadcast_refuses_a_partition_that_cannot_fit_the_table(fj, np_rank):
     """One final partition of the global plan holds 20000 distinct build keys (built by inverting the key mixer: their mixed keys share
