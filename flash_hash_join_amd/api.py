@@ -33,6 +33,9 @@ from ._lib import FjTimings, check
 
 ALGO_ADAPTIVE, ALGO_SCALAR, ALGO_RADIX = 0, 1, 2
 ALGO_MANY_TO_MANY = 0x10          # FJ_ALGO_MANY_TO_MANY: OR'ed into algo (extension, include/flashjoin.h)
+ALGO_LEFT_OUTER = 0x20            # FJ_ALGO_LEFT_OUTER: left outer join, np rows (extension)
+ALGO_ANTI = 0x40                  # FJ_ALGO_ANTI: the probe rows without a partner (extension)
+_OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
 _ctx_locks: Dict[int, Any] = {}
@@ -106,14 +109,15 @@ def last_timings() -> Optional[dict]:
 def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arrays: bool):
     global _last
     L = _lib.load()
-    bk, bv, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(bv, "build_values"), _as_u64_host(pk, "probe_keys")
-    if bv.size < bk.size:
+    bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
+    bv = _as_u64_host(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
+    if bv is not None and bv.size < bk.size:
         raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
     cnt = ctypes.c_uint64(0)
     sec = ctypes.c_double(0.0)
     ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
     want = bool(materialize and return_arrays)
-    check(L.fj_join_host(algo, bloom, materialize, bk.ctypes.data, bv.ctypes.data, bk.size, pk.ctypes.data, pk.size,
+    check(L.fj_join_host(algo, bloom, materialize, bk.ctypes.data, bv.ctypes.data if bv is not None else None, bk.size, pk.ctypes.data, pk.size,
                          ctypes.byref(cnt), ctypes.byref(sec),
                          ctypes.byref(ok) if want else None, ctypes.byref(ov) if want else None))
     t = FjTimings()
@@ -122,6 +126,19 @@ def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_array
     n = int(cnt.value)
     if not want:
         return n, float(sec.value)
+    if algo & _OUTER:                   # left outer: np rows; anti: n keys and no values
+        rows = pk.size if algo & ALGO_LEFT_OUTER else n
+        try:
+            keys = (np.ctypeslib.as_array(ctypes.cast(ok, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
+                    else np.empty(0, np.uint64))
+            vals = None
+            if algo & ALGO_LEFT_OUTER:
+                vals = (np.ctypeslib.as_array(ctypes.cast(ov, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
+                        else np.empty(0, np.uint64))
+        finally:
+            L.fj_free_host(ok)
+            L.fj_free_host(ov)
+        return n, float(sec.value), keys, vals
     try:
         if n:
             keys = np.ctypeslib.as_array(ctypes.cast(ok, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy()
@@ -163,23 +180,43 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     global _last
     import torch
     L = _lib.load()
-    bk, bv, pk = _dev_tensor(bk, "build_keys"), _dev_tensor(bv, "build_values"), _dev_tensor(pk, "probe_keys")
-    if bv.numel() < bk.numel():
+    bk, pk = _dev_tensor(bk, "build_keys"), _dev_tensor(pk, "probe_keys")
+    bv = _dev_tensor(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
+    if bv is not None and bv.numel() < bk.numel():
         raise ValueError(f"build_values has {bv.numel()} elements, build_keys has {bk.numel()}")
     dev = bk.device.index if bk.device.index is not None else torch.cuda.current_device()
     ctx = context(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     cnt = ctypes.c_uint64(0)
     t = FjTimings()
+    bv_ptr = bv.data_ptr() if bv is not None else None
+    if (algo & _OUTER) and materialize:
+        # left outer / anti join: np-row buffers always (a left join HAS np rows), one call, never a pending result to emit
+        left = bool(algo & ALGO_LEFT_OUTER)
+        n_p = pk.numel()
+        ok = torch.empty(n_p, dtype=torch.int64, device=bk.device)
+        ov = torch.empty(n_p, dtype=torch.int64, device=bk.device) if left else None
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(), n_p, stream,
+                                   hash_top_bits, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr() if left else None, n_p, ctypes.byref(t)))
+        n = int(cnt.value)
+        _last = t
+        if not return_arrays:
+            return n, t.total_ms * 1e-3
+        if left:
+            return n, t.total_ms * 1e-3, ok, ov
+        # anti: the first n rows; exact-size copy unless they fill most of the buffer (the rule of the inner join above)
+        ok = ok[:n].clone() if n * 4 < n_p * 3 else ok[:n]
+        return n, t.total_ms * 1e-3, ok, None
     with _ctx_locks.setdefault(dev, threading.RLock()):      # count + emit are two calls on one context: keep other threads out
         out = None
-        if (materialize and not (algo & ALGO_MANY_TO_MANY) and pk.numel() > 0 and bk.numel() > 0 and get_option("mat_single_pass")
+        if (materialize and not (algo & (ALGO_MANY_TO_MANY | _OUTER)) and pk.numel() > 0 and bk.numel() > 0 and get_option("mat_single_pass")
                 and _room_for(pk.numel(), dev)):      # (a many-to-many join can return more pairs than probe rows)
             # room for ANY result (the reference allocates the same, hash_join.cpp:330-334): the join may run in one pass over
             # the probe side; the pairs are the first n rows
             ok = torch.empty(pk.numel(), dtype=torch.int64, device=bk.device)
             ov = torch.empty(pk.numel(), dtype=torch.int64, device=bk.device)
-            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv.data_ptr(), bk.numel(), pk.data_ptr(),
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(),
                                    pk.numel(), stream, hash_top_bits, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(), pk.numel(), ctypes.byref(t)))
             n = int(cnt.value)
             _last = t
@@ -193,7 +230,7 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
                     ok, ov = ok[:n], ov[:n]
                 return n, t.total_ms * 1e-3, ok, ov
             return n, t.total_ms * 1e-3
-        check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv.data_ptr(), bk.numel(), pk.data_ptr(),
+        check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(),
                                pk.numel(), stream, hash_top_bits, ctypes.byref(cnt), None, None, 0, ctypes.byref(t)))
         n = int(cnt.value)
         if materialize and n > 0:
@@ -227,11 +264,11 @@ def _from_dlpack_if_device(x: Any):
 
 
 def _join(algo: int, bloom: int, materialize: int, build_keys, build_values, probe_keys, return_arrays: bool):
-    build_keys, build_values, probe_keys = (_from_dlpack_if_device(x) for x in (build_keys, build_values, probe_keys))
+    build_keys, build_values, probe_keys = (_from_dlpack_if_device(x) if x is not None else None for x in (build_keys, build_values, probe_keys))
     if _is_torch_tensor(build_keys) and build_keys.is_cuda:
         return join_device(algo, bloom, materialize, build_keys, build_values, probe_keys, return_arrays)
     if _is_torch_tensor(build_keys):
-        build_keys, build_values, probe_keys = (x.numpy() for x in (build_keys, build_values, probe_keys))
+        build_keys, build_values, probe_keys = (x.numpy() if x is not None else None for x in (build_keys, build_values, probe_keys))
     return _join_host(algo, bloom, materialize, build_keys, build_values, probe_keys, return_arrays)
 
 
@@ -308,6 +345,40 @@ def inner_join(build_keys, build_values, probe_keys, return_arrays: bool = False
     return _join(ALGO_RADIX | ALGO_MANY_TO_MANY, 0, 1, build_keys, build_values, probe_keys, return_arrays)
 
 
+# ---- extension: left outer and anti joins (N:1 semantics: a duplicated build key matches with its FIRST occurrence's value) ---------
+def _fill(vals, m: int, fill_value):
+    if fill_value == 0 or vals.shape[0] == m:
+        return vals
+    if _is_torch_tensor(vals):
+        vals[m:] = int(np.array(fill_value, dtype=np.uint64).view(np.int64))     # int64 storage of the uint64 word
+    else:
+        vals[m:] = np.uint64(fill_value)
+    return vals
+
+
+def left_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0):
+    """Left outer join: every probe row once.  Returns (m, seconds) or (m, seconds, keys, values), m = matched probe rows (what
+    the counting joins return).  keys / values hold len(probe_keys) rows: rows [0, m) the matched (probe_key, build_value) pairs,
+    rows [m, n) the unmatched probe keys with value `fill_value`; order within either range unspecified."""
+    r = _join(ALGO_ADAPTIVE | ALGO_LEFT_OUTER, 0, 1, build_keys, build_values, probe_keys, return_arrays)
+    if not return_arrays:
+        return r
+    m, sec, keys, vals = r
+    return m, sec, keys, _fill(vals, m, fill_value)
+
+
+def anti_join(build_keys, probe_keys, return_arrays: bool = False):
+    """Anti join (NOT EXISTS / NOT IN): the probe rows whose key is not among the build keys.  Returns (u, seconds) or
+    (u, seconds, keys) with the u unmatched probe keys, in unspecified order."""
+    r = _join(ALGO_ADAPTIVE | ALGO_ANTI, 0, 1, build_keys, None, probe_keys, return_arrays)
+    return r if not return_arrays else r[:3]
+
+
+def anti_join_count(build_keys, probe_keys):
+    """Number of probe rows whose key is not among the build keys: (u, seconds)."""
+    return _join(ALGO_ADAPTIVE | ALGO_ANTI, 0, 0, build_keys, None, probe_keys, False)
+
+
 def sort_pairs(keys, values):
     """The pairs a `return_arrays=True` join handed back, in (key, value) order as unsigned 64-bit integers - the join's own
     output order is unspecified, so comparisons go through this.  NumPy arrays or device tensors."""
@@ -349,5 +420,5 @@ REFERENCE_EXPORTS = [
     "initialize",
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
-EXTENSIONS = ["inner_join", "inner_join_count"]
+EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

@@ -276,6 +276,10 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
 int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& plan, size_t np, const PassIter& pit, hipStream_t s,
                     fj_timings* t, int evc, u64* out_count, bool* lds_full, int top_bits, SingleOut* so = nullptr);
 
+// ---- left outer / anti joins (fj_outer.hip): mode FJ_OJ_LEFT or FJ_OJ_ANTI, materialising; outputs hold >= np rows ----
+int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov);
+
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,
                 size_t probe_piece_rows = 0);

@@ -175,7 +175,12 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (out_keys) *out_keys = nullptr;
     if (out_vals) *out_vals = nullptr;
     const bool many_host = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
-    if (algo < 0 || (algo & ~FJ_ALGO_MANY_TO_MANY) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
+    if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
+    if (left && !materialize) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER needs materialize = 1 (its match count is the counting join's)");
+    const bool outer_mat = (left || anti) && materialize;      // left outer / anti join writing rows: np-row device buffers, no emit step
     {
         static std::mutex create_mu;
         std::lock_guard<std::mutex> lk(create_mu);
@@ -209,7 +214,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // A counting join of the partitioned plan starts on the first piece: the build side is copied and partitioned, then every
     // probe piece gets its first partition pass while the next one crosses PCIe (the join hides under the copy; the bloom
     // precheck is skipped here - it saves device time the copy does not leave on the critical path).
-    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host;
+    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti;
     hipStream_t js = nullptr;
     auto t0 = std::chrono::steady_clock::now();
     unsigned cursor = 0;
@@ -218,7 +223,8 @@ int fj_join_host(int algo, int bloom, int materialize,
     bool joined = false;
     if (h2d_pipelined(c, dbk, bk, nb * 8, piece, &cursor, nullptr)) return 1;
     if (!streamed) {
-        if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
+        if (anti && !bv) dbv = dbk;                                             // (an anti join reads no value)
+        else if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
         if (h2d_pipelined(c, dpk, pk, np * 8, piece, &cursor, nullptr)) return 1;
         HIPCHK(hipStreamSynchronize(c->side));
     } else {
@@ -237,11 +243,29 @@ int fj_join_host(int algo, int bloom, int materialize,
         count = cnt; joined = true;
     }
     const double h2d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    double d2h = 0;
+    if (outer_mat) {
+        void *dok, *dov = nullptr;
+        if (get_buf(c, W_H_OK, std::max<size_t>(np, 1) * 8, &dok) || (left && get_buf(c, W_H_OV, std::max<size_t>(np, 1) * 8, &dov))) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
+                           &count, (u64*)dok, (u64*)dov, np, &t)) return 1;
+        const size_t rows = left ? np : count;                                 // LEFT: every probe row; ANTI: the unmatched keys
+        if (out_keys && (out_vals || !left)) {
+            u64* hk = (u64*)malloc(std::max<size_t>(rows, 1) * 8);
+            u64* hv = left ? (u64*)malloc(std::max<size_t>(rows, 1) * 8) : nullptr;
+            if (!hk || (left && !hv)) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", rows); }
+            auto t1 = std::chrono::steady_clock::now();
+            if (rows) { HIPCHK(hipMemcpy(hk, dok, rows * 8, hipMemcpyDeviceToHost)); if (left) HIPCHK(hipMemcpy(hv, dov, rows * 8, hipMemcpyDeviceToHost)); }
+            d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+            *out_keys = hk;
+            if (out_vals) *out_vals = hv;
+        }
+        joined = true;
+    }
     if (!joined) {
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
                            &count, nullptr, nullptr, 0, &t)) return 1;
     }
-    double d2h = 0;
     if (materialize && c->pend.valid) {
         void *dok, *dov;
         if (get_buf(c, W_H_OK, count * 8, &dok) || get_buf(c, W_H_OV, count * 8, &dov)) return 1;
@@ -259,7 +283,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined ? 1 : 0;
+    t.host_streamed = joined && !outer_mat ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
     if (out_seconds) *out_seconds = t.total_ms * 1e-3;

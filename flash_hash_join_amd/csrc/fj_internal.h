@@ -240,3 +240,34 @@ hipError_t fj_launch_gen_probe(u64* keys, u64 first, u64 n, u64 build_total, u64
 
 // owner GPU of a key: range reduction of the top 16 bits of hash word 1
 __host__ __device__ inline u32 fj_owner_of_w1(u32 w1, u32 nranks) { return ((w1 >> 16) * nranks) >> 16; }
+
+// ---- left outer / anti joins (csrc/fj_outer.hip; FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI of include/flashjoin.h) ----------------------
+// Output rows: hits (probe key, build value) from a front cursor counting up from 0, misses (probe key[, 0]) from a back cursor
+// counting down from np.  One LDS cursor pair per workgroup collects a round's reservations wave by wave (ballot + popcount); thread 0
+// turns the round's totals into global ranges with ONE atomic per cursor, behind a barrier.
+#define FJ_OJ_LEFT 0          // left outer join, unique build keys (duplicates: FJ_STAT_DUPS)
+#define FJ_OJ_ANTI 1          // anti join: misses only, keys only
+#define FJ_OJ_LEFT_FIRST 2    // left outer join whose build 'values' are row indices: the smallest wins, then orig_vals[idx]
+struct FjOjCursor { u32 hit, miss; u64 hit_base, miss_base; };
+// called by every thread of the workgroup with its wave's totals nh / nm (wave-uniform): returns the first hit row and the first
+// miss rank (counted from the back) of the calling wave in this round
+__device__ __forceinline__ void fj_oj_reserve(FjOjCursor* cur, u32 nh, u32 nm, u32 lane, u32 tid, unsigned long long* ghit,
+                                              unsigned long long* gmiss, u64& hpos, u64& mpos) {
+    u32 wh = 0, wm = 0;
+    if (lane == 0) { if (nh) wh = atomicAdd(&cur->hit, nh); if (nm) wm = atomicAdd(&cur->miss, nm); }
+    wh = __shfl(wh, 0, 64); wm = __shfl(wm, 0, 64);
+    __syncthreads();
+    if (tid == 0) {
+        const u32 H = cur->hit, M = cur->miss;
+        cur->hit_base = H ? (u64)atomicAdd(ghit, (unsigned long long)H) : 0ull;
+        cur->miss_base = M ? (u64)atomicAdd(gmiss, (unsigned long long)M) : 0ull;
+        cur->hit = 0; cur->miss = 0;
+    }
+    __syncthreads();
+    hpos = cur->hit_base + wh; mpos = cur->miss_base + wm;
+}
+// a.out_cursor counts the hits, miss_cursor the misses; a.out_capacity >= np (rows beyond it are never written: FJ_ERR_OUTCAP)
+hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsigned long long* miss_cursor, hipStream_t s);
+// global table: build with row indices (first occurrence; vals = false: keys only), then the outer probe (a.total = hit cursor)
+hipError_t fj_launch_gt_build_first(const FjGtArgs& a, bool vals, hipStream_t s);
+hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long long* miss_cursor, u64 out_capacity, hipStream_t s);

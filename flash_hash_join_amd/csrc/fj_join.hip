@@ -1518,6 +1518,87 @@ __global__ __launch_bounds__(256) void fj_gt_probe_kernel(FjGtArgs a) {
     }
 }
 
+// ---- left outer / anti joins on the global table (FJ_OJ_*, csrc/fj_outer.hip) ----
+// build: every copy of a key lowers its slot's value to its ROW INDEX (tvals and *empty_val pre-set to all ones): the first
+// occurrence wins deterministically, whichever copy wins the slot's CAS.  VALS = false (anti join): keys only.
+template <bool VALS>
+__global__ __launch_bounds__(256) void fj_gt_build_first_kernel(FjGtArgs a) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < a.nb; i += stride) {
+        const u64 key = a.bk[i];
+        if (key == FJ_EMPTY_KEY) { a.flags[0] = 1; if (VALS) atomicMin((unsigned long long*)a.empty_val, (unsigned long long)i); continue; }
+        const u64 h = fj_hash64(key);
+        u64 pos = (h & a.cap_mask) & ~(u64)(FJ_GT_GROUP - 1);
+        for (u64 step = 0; step <= a.cap_mask; ++step) {
+            const u64 old = atomicCAS((unsigned long long*)&a.tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+            if (old == FJ_EMPTY_KEY || old == key) {
+                if (VALS) atomicMin((unsigned long long*)&a.tvals[pos], (unsigned long long)i);
+                break;
+            }
+            pos = (pos + 1) & a.cap_mask;
+        }
+    }
+}
+
+// probe: rounds of 4096 rows per workgroup (4 per thread), hits from the front (a.total), misses from the back (miss_cursor);
+// LEFT: the value is gathered from the caller's build_values by the slot's row index
+template <int MODE>
+__global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, unsigned long long* miss_cursor, u64 out_capacity) {
+    constexpr bool VALS = MODE != FJ_OJ_ANTI;
+    constexpr u32 NT = 1024, KPT = 4;
+    __shared__ FjOjCursor cur;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) { cur.hit = 0; cur.miss = 0; }
+    __syncthreads();
+    const bool has_empty = a.flags[0] != 0;
+    const u64 np = a.np;
+    for (u64 base = (u64)blockIdx.x * NT * KPT; base < np; base += (u64)gridDim.x * NT * KPT) {     // (uniform per workgroup)
+        u64 k[KPT];
+        u32 hit = 0, miss = 0, okm = 0;
+#pragma unroll
+        for (u32 u = 0; u < KPT; ++u) {
+            const u64 i = base + u * NT + tid;
+            k[u] = 0;
+            if (i < np) { k[u] = a.pk[i]; okm |= 1u << u; }
+        }
+        u64 where[KPT];
+#pragma unroll
+        for (u32 u = 0; u < KPT; ++u) {
+            where[u] = 0;
+            if (!((okm >> u) & 1u)) continue;
+            bool h;
+            if (k[u] == FJ_EMPTY_KEY) h = has_empty;
+            else h = gt_lookup(a.tkeys, a.cap_mask, k[u], fj_hash64(k[u]), where[u]);
+            if (h && VALS) hit |= 1u << u;
+            if (!h) miss |= 1u << u;
+        }
+        u64 hb[KPT], mb[KPT];
+        u32 nh = 0, nm = 0;
+#pragma unroll
+        for (u32 u = 0; u < KPT; ++u) {
+            hb[u] = __ballot((hit >> u) & 1u); mb[u] = __ballot((miss >> u) & 1u);
+            nh += (u32)__popcll(hb[u]); nm += (u32)__popcll(mb[u]);
+        }
+        u64 hpos, mpos;
+        fj_oj_reserve(&cur, nh, nm, lane, tid, a.total, miss_cursor, hpos, mpos);
+        const u64 below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (u32 u = 0; u < KPT; ++u) {
+            if ((hit >> u) & 1u) {
+                const u64 o = hpos + (u32)__popcll(hb[u] & below);
+                const u64 row = k[u] == FJ_EMPTY_KEY ? *a.empty_val : a.tvals[where[u]];
+                if (o < out_capacity) { a.out_keys[o] = k[u]; a.out_vals[o] = a.bv[row]; }
+            }
+            if ((miss >> u) & 1u) {
+                const u64 m = mpos + (u32)__popcll(mb[u] & below);
+                const u64 o = VALS ? np - 1 - m : m;                      // LEFT: from the back; ANTI: rows [0, u)
+                if (m < np && o < out_capacity) { a.out_keys[o] = k[u]; if (VALS) a.out_vals[o] = 0; }
+            }
+            hpos += (u32)__popcll(hb[u]); mpos += (u32)__popcll(mb[u]);
+        }
+    }
+}
+
 // =============================== multi-GPU owner split ========================================
 // lanes of this wave whose value d (< 2^(nbits-1), or exactly 2^(nbits-1) for "no key") equals mine: nbits ballots
 __device__ __forceinline__ u64 fj_match_any(u32 d, u32 nbits) {
@@ -1766,6 +1847,26 @@ hipError_t fj_launch_gt_probe(const FjGtArgs& a, bool materialize, u32 grid, hip
         if (bloom) hipLaunchKernelGGL((fj_gt_probe_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((fj_gt_probe_kernel<false, false>), dim3(grid), dim3(256), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_build_first(const FjGtArgs& a, bool vals, hipStream_t s) {
+    if (a.nb == 0) return hipSuccess;
+    if (vals && !a.tvals) return hipErrorInvalidValue;
+    u64 blocks = (a.nb + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (vals) hipLaunchKernelGGL(fj_gt_build_first_kernel<true>, dim3((u32)blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(fj_gt_build_first_kernel<false>, dim3((u32)blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long long* miss_cursor, u64 out_capacity, hipStream_t s) {
+    if (a.np == 0) return hipSuccess;
+    if (!a.out_keys || !miss_cursor || (mode != FJ_OJ_ANTI && (!a.out_vals || !a.tvals || !a.bv))) return hipErrorInvalidValue;
+    const u64 rounds = (a.np + 4095) / 4096;
+    const u32 grid = (u32)(rounds < 2048 ? rounds : 2048);
+    if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_ANTI>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+    else hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_LEFT>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
     return hipGetLastError();
 }
 

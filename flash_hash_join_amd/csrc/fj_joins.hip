@@ -503,7 +503,21 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                    void* stream, int hash_top_bits, uint64_t* out_count,
                    uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, fj_timings* timings) {
     const bool many = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
+    const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
+    if (left || anti) {
+        // left outer / anti join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
+        algo &= ~(FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI);
+        if (left && anti) return set_err("fj_join_device: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
+        if (many) return set_err("fj_join_device: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
+        if (left && !materialize) return set_err("fj_join_device: FJ_ALGO_LEFT_OUTER needs materialize = 1 (its match count is the counting join's)");
+        if (materialize) {
+            if (np && (!d_out_keys || (left && !d_out_vals))) return set_err("fj_join_device: FJ_ALGO_%s needs output buffers (d_out_keys%s)", left ? "LEFT_OUTER" : "ANTI", left ? " and d_out_vals" : "");
+            if (out_capacity < np) return set_err("fj_join_device: output capacity %zu < %zu probe rows (FJ_ALGO_%s writes every probe row)", out_capacity, np, left ? "LEFT_OUTER" : "ANTI");
+            if (((uintptr_t)d_out_keys | (uintptr_t)(left ? d_out_vals : nullptr)) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
+        }
+        if (!left && !d_bv) d_bv = d_bk;                    // an anti join reads no value (the counting paths below want a pointer)
+    }
     if (algo < 0 || algo > 2) return set_err("fj_join_device: unknown algo %d", algo);
     if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_join_device: hash_top_bits must be 64 or 48");
     if ((nb && (!d_bk || !d_bv)) || (np && !d_pk)) return set_err("fj_join_device: null input pointer");
@@ -517,6 +531,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const Options& opt = options();
     bool use_radix = algo == FJ_ALGO_RADIX || (algo == FJ_ALGO_ADAPTIVE && nb >= opt.radix_threshold) ||
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
+    if ((left || anti) && materialize) {                    // one pass over the probe side, never a pending result
+        if (join_outer(c, left ? FJ_OJ_LEFT : FJ_OJ_ANTI, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count,
+                       (u64*)d_out_keys, (u64*)d_out_vals)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
     if (nb == 0 || np == 0) {                   // empty side: (0, t), hash_join.cpp behaviour for empty inputs
         count = 0;
     } else if (many) {
@@ -538,6 +560,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     } else {
         if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t, &count)) return 1;
     }
+    if (anti) count = np - count;                           // counting anti join: the probe rows the N:1 count leaves out
     if (out_count) *out_count = count;
     if (materialize && d_out_keys && d_out_vals && c->pend.valid) {
         if (emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;

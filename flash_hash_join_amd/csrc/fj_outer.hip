@@ -1,0 +1,325 @@
+// fj_outer.hip -- left outer and anti joins on the partitioned plan (an EXTENSION: FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI,
+// include/flashjoin.h).
+//
+// The N:1 join of the reference (first occurrence of a duplicate build key wins, hash_join.cpp:125) answers "which probe rows have
+// a partner, and with which value".  A left outer join also returns the rows WITHOUT one, an anti join only those.  With N:1
+// semantics a left join has exactly np output rows, so it runs in ONE pass over the probe side: no counting pass, no scan.
+//
+// Same partitioning and work items as the other joins (zero-pass plans: flat arrays, items are nsplit slices; one or more passes:
+// chunk lists, items are the probe side's final tiles); one 1024-thread workgroup per item keeps in LDS
+//   LEFT  8192 key slots + 8192 values (128 KiB),     ANTI  16384 key slots (128 KiB),
+// linear probing from the low hash word, a slot claimed by a 64-bit compare-and-swap, duplicate keys merged at insert.  Then the
+// item's probe rows stream through in rounds of 8192 (8 per thread; the next round's loads in flight during this one's reservation): hits are written from a FRONT cursor counting up from 0,
+// misses from a BACK cursor counting down from np (ANTI: misses only, from row 0 up).  Positions are reserved wave-wide (ballot + popcount into
+// an LDS cursor per workgroup), and thread 0 turns the round's totals into global ranges with one atomic per cursor and round
+// (fj_oj_reserve; the scheme of the single-pass emit kernel, csrc/fj_join.hip): ~125K atomics per cursor at 1B probe rows.
+//
+// Fallbacks, both decided by the host from the device error word:
+//   FJ_STAT_DUPS (LEFT)    a build key occurs more than once: the output is rewritten by a second launch whose build side carries
+//                          row indices (fj_iota_kernel); every copy lowers its slot's index with an LDS atomic minimum and the
+//                          winners are turned into values with one gather from the caller's build_values (the first-occurrence rule
+//                          of the radix path and of the NumPy reference in the tests);
+//   FJ_ERR_LDS_FULL        a partition holds more distinct keys than the table takes (15/16 of its slots): the whole join runs
+//                          again on the global HBM table (fj_gt_outer_probe_kernel, csrc/fj_join.hip), timings.fell_back = 1.
+#include "fj_host.h"
+
+namespace {
+
+constexpr u32 OJ_NT = 1024, OJ_KPT = 8, OJ_ROUND_CHUNKS = OJ_NT * OJ_KPT / FJ_CHUNK;
+struct OjHdr { u32 full, dups, empty_cnt, nkeys; FjOjCursor cur; u64 empty_val; };
+
+__device__ __forceinline__ u32 oj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
+    if (cs.list) return cs.list[idx];
+    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
+    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
+    return ((cnt - 1u) << 24) | idx;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a, u64 np, unsigned long long* miss_cursor) {
+    constexpr bool VALS = MODE != FJ_OJ_ANTI, FIRST = MODE == FJ_OJ_LEFT_FIRST;
+    constexpr u32 TS = VALS ? 8192u : 16384u, LIMIT = TS - TS / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    OjHdr* hdr = reinterpret_cast<OjHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(OjHdr));
+    u64* tvals = tkeys + TS;                                  // (VALS only)
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 item = blockIdx.x;
+    u32 p, b0 = 0, nbc, s_lo, s_hi;
+    if (a.items) {
+        if (item >= *a.nitems_dev) return;
+        const uint4 it = a.items[item];
+        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
+    } else {
+        const u32 slice = item % a.nsplit;
+        p = item / a.nsplit;
+        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
+    }
+    if (s_lo >= s_hi) return;
+    if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
+    else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+
+    for (u32 i = tid; i < TS; i += OJ_NT) { tkeys[i] = FJ_EMPTY_KEY; if (FIRST) tvals[i] = ~0ull; }
+    if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->cur.hit = 0; hdr->cur.miss = 0; hdr->empty_val = FIRST ? ~0ull : 0ull; }
+    __syncthreads();
+
+    // ---- build: distinct keys (and the value of one copy; FIRST: the smallest row index) ----
+    for (u32 c0 = 0; c0 < nbc; c0 += OJ_NT / FJ_CHUNK) {
+        const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        if (c >= nbc) continue;
+        const u32 e = oj_entry(a.build, b0 + c);
+        if (off >= FJ_LIST_CNT(e)) continue;
+        const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+        const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
+        const u64 val = VALS ? a.build.vals[src] : 0;
+        if (key == FJ_EMPTY_KEY) {                           // the empty marker is never stored in the table
+            const u32 before = atomicAdd(&hdr->empty_cnt, 1u);
+            if (FIRST) atomicMin((unsigned long long*)&hdr->empty_val, (unsigned long long)val);
+            else if (VALS) { if (before == 0) hdr->empty_val = val; else hdr->dups = 1; }
+            continue;
+        }
+        u32 pos = FJ_HW2(key) & (TS - 1);
+        bool placed = false;
+        for (u32 step = 0; step < TS; ++step) {
+            const u64 old = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+            if (old == FJ_EMPTY_KEY) {
+                if (atomicAdd(&hdr->nkeys, 1u) >= LIMIT) hdr->full = 1;
+                if (FIRST) atomicMin((unsigned long long*)&tvals[pos], (unsigned long long)val);
+                else if (VALS) tvals[pos] = val;
+                placed = true;
+                break;
+            }
+            if (old == key) {
+                if (FIRST) atomicMin((unsigned long long*)&tvals[pos], (unsigned long long)val);
+                else if (VALS) hdr->dups = 1;
+                placed = true;
+                break;
+            }
+            pos = (pos + 1) & (TS - 1);
+        }
+        if (!placed) hdr->full = 1;
+    }
+    __syncthreads();
+    if (hdr->full) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }     // the host re-runs the join on the HBM table
+    if (VALS && !FIRST && hdr->dups) { if (tid == 0) atomicOr(a.err, FJ_STAT_DUPS); return; }   // ... or this one with row indices
+    const bool has_empty = hdr->empty_cnt != 0;
+    if (FIRST) {                                             // winning row indices -> the caller's values
+        for (u32 i = tid; i < TS; i += OJ_NT) if (tkeys[i] != FJ_EMPTY_KEY) tvals[i] = a.orig_vals[tvals[i]];
+        if (tid == 0 && has_empty) hdr->empty_val = a.orig_vals[hdr->empty_val];
+        __syncthreads();
+    }
+    const u64 empty_val = hdr->empty_val;
+
+    // ---- probe: rounds of OJ_NT * OJ_KPT rows, hits to the front, misses to the back; the next round's keys are requested
+    // before this round's reservation (its barriers and the global atomic's round trip hide the loads' latency) ----
+    u64 k[OJ_KPT];
+    u32 okm = 0;
+    auto load_round = [&](u32 pc, u64 (&kk)[OJ_KPT], u32& ok) {
+        ok = 0;
+#pragma unroll
+        for (u32 u = 0; u < OJ_KPT; ++u) {
+            const u32 c = pc + u * (OJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            kk[u] = 0;
+            if (c >= s_hi) continue;
+            const u32 e = oj_entry(a.probe, c);
+            if (off >= FJ_LIST_CNT(e)) continue;
+            kk[u] = a.probe.keys[(u64)FJ_LIST_ID(e) * FJ_CHUNK + off];
+            ok |= 1u << u;
+        }
+    };
+    load_round(s_lo, k, okm);
+    for (u32 pc = s_lo; pc < s_hi; pc += OJ_ROUND_CHUNKS) {
+        u64 v[OJ_KPT];
+        u32 hit = 0, miss = 0;
+#pragma unroll
+        for (u32 u = 0; u < OJ_KPT; ++u) {
+            v[u] = 0;
+            if (!((okm >> u) & 1u)) continue;
+            if (!a.probe.list) k[u] = fj_key_mix(k[u]);
+            bool h = false;
+            if (k[u] == FJ_EMPTY_KEY) { h = has_empty; v[u] = empty_val; }
+            else {
+                u32 pos = FJ_HW2(k[u]) & (TS - 1);
+                for (;;) {                                   // the build left >= 1/16 of the slots empty: always terminates
+                    const u64 t = tkeys[pos];
+                    if (t == k[u]) { h = true; if (VALS) v[u] = tvals[pos]; break; }
+                    if (t == FJ_EMPTY_KEY) break;
+                    pos = (pos + 1) & (TS - 1);
+                }
+            }
+            if (h) hit |= 1u << u; else miss |= 1u << u;
+        }
+        if (!VALS) hit = 0;                                  // ANTI writes misses only
+        u64 hb[OJ_KPT], mb[OJ_KPT];
+        u32 nh = 0, nm = 0;
+#pragma unroll
+        for (u32 u = 0; u < OJ_KPT; ++u) {
+            hb[u] = __ballot((hit >> u) & 1u); mb[u] = __ballot((miss >> u) & 1u);
+            nh += (u32)__popcll(hb[u]); nm += (u32)__popcll(mb[u]);
+        }
+        u64 kn[OJ_KPT];
+        u32 okn = 0;
+        if (pc + OJ_ROUND_CHUNKS < s_hi) load_round(pc + OJ_ROUND_CHUNKS, kn, okn);
+        u64 hpos, mpos;
+        fj_oj_reserve(&hdr->cur, nh, nm, lane, tid, a.out_cursor, miss_cursor, hpos, mpos);
+        const u64 below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (u32 u = 0; u < OJ_KPT; ++u) {
+            if ((hit >> u) & 1u) {
+                const u64 o = hpos + (u32)__popcll(hb[u] & below);
+                if (o < a.out_capacity) { a.out_keys[o] = fj_key_unmix(k[u]); a.out_vals[o] = v[u]; }
+                else atomicOr(a.err, FJ_ERR_OUTCAP);
+            }
+            if ((miss >> u) & 1u) {
+                const u64 m = mpos + (u32)__popcll(mb[u] & below);
+                const u64 o = VALS ? np - 1 - m : m;          // LEFT: from the back; ANTI: the misses are the whole output
+                if (m < np && o < a.out_capacity) {
+                    a.out_keys[o] = fj_key_unmix(k[u]);
+                    if (VALS) a.out_vals[o] = 0;
+                } else atomicOr(a.err, FJ_ERR_OUTCAP);
+            }
+            hpos += (u32)__popcll(hb[u]); mpos += (u32)__popcll(mb[u]);
+        }
+#pragma unroll
+        for (u32 u = 0; u < OJ_KPT; ++u) k[u] = kn[u];
+        okm = okn;
+    }
+}
+
+}  // namespace
+
+hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsigned long long* miss_cursor, hipStream_t s) {
+    const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;
+    if (!a.out_cursor || !miss_cursor || !a.out_keys || (mode != FJ_OJ_ANTI && !a.out_vals) || (mode == FJ_OJ_LEFT_FIRST && !a.orig_vals))
+        return hipErrorInvalidValue;
+    const u32 lds = (u32)sizeof(OjHdr) + (mode == FJ_OJ_ANTI ? 16384u * 8 : 8192u * 16);
+    auto kern = mode == FJ_OJ_ANTI ? fj_outer_join_kernel<FJ_OJ_ANTI>
+              : mode == FJ_OJ_LEFT_FIRST ? fj_outer_join_kernel<FJ_OJ_LEFT_FIRST> : fj_outer_join_kernel<FJ_OJ_LEFT>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    if (nb) hipLaunchKernelGGL(kern, dim3(nb), dim3(OJ_NT), lds, s, a, np, miss_cursor);
+    return hipGetLastError();
+}
+
+namespace fjh {
+
+// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
+// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  LEFT builds with row indices (the smallest wins, first occurrence)
+static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, hipStream_t s,
+                             fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov) {
+    const bool left = mode != FJ_OJ_ANTI;
+    u64 cap = 64;
+    while (cap < 2 * (u64)nb) cap <<= 1;
+    FjGtArgs a{};
+    void* p;
+    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
+    if (left) { if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1; a.tvals = (u64*)p; }
+    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
+    a.bk = bk; a.bv = left ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr;
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));           // (row index minimum)
+    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    if (left) HIPCHK(hipMemsetAsync(a.tvals, 0xFF, cap * 8, s));
+    HIPCHK(fj_launch_gt_build_first(a, left, s));
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    HIPCHK(fj_launch_gt_outer_probe(a, mode, &c->d_sc->expected, np, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join's global-table probe wrote out of its rows");
+    const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
+    if (left ? hits + misses != np : misses > np) return set_err("internal error: outer join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
+    *out_count = left ? hits : misses;
+    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
+    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
+    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
+    t->probe_phase_ms = t->join_ms;
+    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    return 0;
+}
+
+// FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI with materialize = 1 (fj_join_device has checked the arguments): *out_count = matched probe
+// rows (LEFT) or unmatched ones (ANTI).  use_radix: the partitioned plan, else the global table.
+int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov) {
+    const bool left = mode != FJ_OJ_ANTI;
+    *out_count = 0;
+    if (np == 0) return 0;
+    if (nb == 0) {                                           // every probe row is unmatched
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        HIPCHK(hipMemcpyAsync(d_ok, pk, np * 8, hipMemcpyDeviceToDevice, s));
+        if (left) HIPCHK(hipMemsetAsync(d_ov, 0, np * 8, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        HIPCHK(hipStreamSynchronize(s));
+        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        *out_count = left ? 0 : np;
+        return 0;
+    }
+    if (!use_radix) return join_outer_global(c, mode, bk, bv, nb, pk, np, s, t, out_count, d_ok, d_ov);
+
+    const Plan plan = make_plan(nb, top_bits, false);
+    begin_plan(c);
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (clear_plan_scalars(c, s)) return 1;                  // (total = the hit cursor, expected = the miss cursor)
+    FjLdsJoinArgs ja{};
+    PassIter bit, pit;
+    pass_init(bit, 0, left, nb, plan, top_bits);
+    int evc = 0;
+    if (run_passes(c, bit, bk, left ? bv : nullptr, s, &ja.build, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    pass_init(pit, 1, false, np, plan, top_bits);
+    pit.want_items = true;
+    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
+    void* p;
+    if (ja.probe.list) {
+        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
+    } else {                                                 // zero-pass plan: slices of the flat probe side
+        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
+        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
+    }
+    ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
+    ja.out_cursor = &c->d_sc->total; ja.out_capacity = np; ja.out_keys = d_ok; ja.out_vals = left ? d_ov : nullptr;
+    HIPCHK(fj_launch_outer_join(ja, mode, np, &c->d_sc->expected, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    end_plan(c);
+    if (left && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
+        // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
+        if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
+        u64* rowidx = (u64*)p;
+        HIPCHK(fj_launch_iota(rowidx, nb, s));
+        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both cursors
+        HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
+        HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
+        PassIter bit2;
+        pass_init(bit2, 0, true, nb, plan, top_bits);
+        begin_plan(c);
+        if (run_passes(c, bit2, bk, rowidx, s, &ja.build, nullptr)) return 1;
+        end_plan(c);
+        ja.orig_vals = bv;
+        HIPCHK(fj_launch_outer_join(ja, FJ_OJ_LEFT_FIRST, np, &c->d_sc->expected, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        if (read_scalars(c, s)) return 1;
+        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    }
+    plan_timings(c, plan, ja.nparts, evc, t);
+    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
+        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
+        if (join_outer_global(c, mode, bk, bv, nb, pk, np, s, &t2, out_count, d_ok, d_ov)) return 1;
+        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
+        return 0;
+    }
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join kernel wrote out of its rows");
+    const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
+    if (left ? hits + misses != np : misses > np) return set_err("internal error: outer join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
+    *out_count = left ? hits : misses;
+    return 0;
+}
+
+}  // namespace fjh

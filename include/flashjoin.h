@@ -37,6 +37,21 @@ extern "C" {
  * number of pairs.  Partitioned plan only; fails when a final partition would hold more than 4096 build rows (a key with
  * thousands of duplicates).  `bloom` is ignored. */
 #define FJ_ALGO_MANY_TO_MANY 0x10
+/* EXTENSIONS (no reference counterpart; csrc/fj_outer.hip): OR one of these into `algo` together with a base value (ADAPTIVE, SCALAR
+ * or RADIX: it picks the partitioned plan or the global HBM table exactly as for the inner join).  N:1 semantics as everywhere: a
+ * duplicated build key matches with the value of its FIRST occurrence in build order, on both paths.
+ *   FJ_ALGO_LEFT_OUTER - left outer join; materialize = 1 only.  d_out_keys and d_out_vals (8-byte aligned) hold >= np rows.
+ *                        *out_count = m, the matched probe rows (what the counting join returns); rows [0, m) are the matched
+ *                        (probe_key, build_value) pairs, rows [m, np) the unmatched probe keys with value 0: every probe row once,
+ *                        order within either range unspecified.
+ *   FJ_ALGO_ANTI       - the probe rows without a partner.  materialize = 0: *out_count = np - the N:1 count of the same algo and
+ *                        bloom.  materialize = 1: d_out_keys (8-byte aligned, >= np rows) receives the u = *out_count unmatched probe
+ *                        keys in rows [0, u); d_out_vals may be NULL and is never written.  d_build_vals may be NULL.
+ * Both: bloom is ignored when materialising; never a pending result for fj_emit_pairs (a result that was pending is dropped);
+ * fj_join_host returns np rows (LEFT) or u keys and *out_vals = NULL (ANTI).  Refused up front, before any device work: both flags,
+ * either with FJ_ALGO_MANY_TO_MANY, LEFT with materialize = 0, an output capacity below np, NULL or misaligned output buffers. */
+#define FJ_ALGO_LEFT_OUTER 0x20
+#define FJ_ALGO_ANTI 0x40
 
 typedef struct fj_ctx fj_ctx;
 
@@ -76,7 +91,7 @@ const char* fj_version(void);
  * binding checks it once after loading the library (flash_hash_join_amd/_lib.py does).  Structs the library fills or reads on a
  * caller's behalf (fj_dist_timings, fj_dist_engine_ops) start with a struct_size word the caller sets to sizeof(its struct): the
  * library touches no byte beyond it. */
-#define FJ_ABI_VERSION 6
+#define FJ_ABI_VERSION 7
 int fj_abi_version(void);
 
 /* Process-wide dispatch options (no reference counterpart; the reference hard-codes 1'000'000 at hash_join.cpp:576).  Initial values:
