@@ -23,7 +23,7 @@ LIB_PATH = (os.path.join(_PKG, "lib", "libflashjoin_hip.so") if not VARIANT
             else os.path.join(_PKG, "lib", "ab", VARIANT + ".so"))
 PRODUCT_LIB_PATH = os.path.join(_PKG, "lib", "libflashjoin_hip.so")
 LAB_LIB_PATH = os.path.join(_PKG, "lib", "libflashjoin_hip_lab.so")
-ABI_VERSION = 7                     # include/flashjoin.h: FJ_ABI_VERSION
+ABI_VERSION = 8                     # include/flashjoin.h: FJ_ABI_VERSION
 CSRC = os.path.join(_PKG, "csrc")
 
 # every symbol include/flashjoin.h declares (what libflashjoin_hip.so exports: csrc/exports.map)

@@ -35,6 +35,7 @@ ALGO_ADAPTIVE, ALGO_SCALAR, ALGO_RADIX = 0, 1, 2
 ALGO_MANY_TO_MANY = 0x10          # FJ_ALGO_MANY_TO_MANY: OR'ed into algo (extension, include/flashjoin.h)
 ALGO_LEFT_OUTER = 0x20            # FJ_ALGO_LEFT_OUTER: left outer join, np rows (extension)
 ALGO_ANTI = 0x40                  # FJ_ALGO_ANTI: the probe rows without a partner (extension)
+ALGO_ROW_IDS = 0x80               # FJ_ALGO_ROW_IDS: output rows hold row positions (gather maps) instead of keys and values (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -379,6 +380,30 @@ def anti_join_count(build_keys, probe_keys):
     return _join(ALGO_ADAPTIVE | ALGO_ANTI, 0, 0, build_keys, None, probe_keys, False)
 
 
+# ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
+_HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI}
+
+
+def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool = False):
+    """Row-index gather maps of a join: which probe row matched which build row, so that the caller can gather the other
+    columns of both tables.  Positions are 0-based row numbers of the flattened inputs; order within each range unspecified.
+
+    how="inner"  (n, seconds, probe_idx, build_idx): one row per matched probe row, build_idx the key's FIRST occurrence
+                 (smallest build row); many_to_many=True: one row per (probe row, build row) pair with equal keys.
+    how="left"   (m, seconds, probe_idx, build_idx): every probe row once, rows [0, m) matched, rows [m, len(probe_keys))
+                 unmatched with build_idx == -1; m = matched rows, as left_join returns.
+    how="anti"   (u, seconds, probe_idx, None): the u probe rows whose key is not among the build keys.
+    The index arrays are int64: NumPy for host inputs, torch.int64 on the inputs' device for device tensors / DLPack."""
+    if how not in _HOW:
+        raise ValueError(f"join_indices: how must be one of {sorted(_HOW)}, got {how!r}")
+    if many_to_many and how != "inner":
+        raise ValueError(f"join_indices: many_to_many=True needs how='inner' (got how={how!r})")
+    algo = (ALGO_RADIX | ALGO_MANY_TO_MANY if many_to_many else ALGO_ADAPTIVE | _HOW[how]) | ALGO_ROW_IDS
+    n, sec, pi, bi = _join(algo, 0, 1, build_keys, None, probe_keys, True)
+    as_i64 = lambda a: a if a is None or _is_torch_tensor(a) else np.asarray(a).view(np.int64)
+    return n, sec, as_i64(pi), as_i64(bi)
+
+
 def sort_pairs(keys, values):
     """The pairs a `return_arrays=True` join handed back, in (key, value) order as unsigned 64-bit integers - the join's own
     output order is unspecified, so comparisons go through this.  NumPy arrays or device tensors."""
@@ -420,5 +445,5 @@ REFERENCE_EXPORTS = [
     "initialize",
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
-EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count"]
+EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

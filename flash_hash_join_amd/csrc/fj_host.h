@@ -145,6 +145,8 @@ struct PassIter {
     u32* alloc_word = nullptr; u32* seg_word = nullptr; u32* err_word = nullptr;
     // the previous level arrived from other GPUs in the 7-byte wire format (FjPartArgs::in_pk7)
     bool in_pk7 = false; u32 in_b0 = 0, in_top_shift = 0;
+    // has_vals with a flat first input and no value array: the first pass makes the rows' positions (FjPartArgs::vals_pos)
+    bool vals_pos = false;
 };
 
 }  // namespace fjh
@@ -277,8 +279,9 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
                     fj_timings* t, int evc, u64* out_count, bool* lds_full, int top_bits, SingleOut* so = nullptr);
 
 // ---- left outer / anti joins (fj_outer.hip): mode FJ_OJ_LEFT or FJ_OJ_ANTI, materialising; outputs hold >= np rows ----
+// rid: the row-id form (FJ_ALGO_ROW_IDS): probe positions in d_ok, first-occurrence build positions (~0: none) in d_ov
 int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
-               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov);
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid = false);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

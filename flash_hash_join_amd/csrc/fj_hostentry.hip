@@ -176,7 +176,9 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (out_vals) *out_vals = nullptr;
     const bool many_host = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
     if (left && !materialize) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER needs materialize = 1 (its match count is the counting join's)");
@@ -223,7 +225,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     bool joined = false;
     if (h2d_pipelined(c, dbk, bk, nb * 8, piece, &cursor, nullptr)) return 1;
     if (!streamed) {
-        if (anti && !bv) dbv = dbk;                                             // (an anti join reads no value)
+        if ((anti && !bv) || rid) dbv = dbk;                                    // (an anti join reads no value, a row-id join none either)
         else if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
         if (h2d_pipelined(c, dpk, pk, np * 8, piece, &cursor, nullptr)) return 1;
         HIPCHK(hipStreamSynchronize(c->side));

@@ -47,6 +47,8 @@ struct FjPartArgs {
     // chunk-list input in the owner shuffle's 7-byte wire format (chunks received from other GPUs, csrc/fj_pack.hip): chunk id i
     // lives at byte i * FJ_WIRE7_BYTES of in_keys; bits 56..63 of its keys = (in_b0 + the tile's parent bucket) >> in_top_shift
     u32 in_pk7, in_b0, in_top_shift;
+    // flat input with values: 1 = the values are the rows' 0-based positions, made by the pass (in_vals is not read; row-id joins)
+    u32 vals_pos;
 };
 
 // a chunk pool plus its per-bucket chunk lists (output of one pass, input of the next)
@@ -173,6 +175,9 @@ struct FjLdsJoinArgs {
     u32 avg_build_keys;          // build rows per final partition on average (host hint: selects the 16384-slot counting kernel, fj_join_wide.hip)
     unsigned long long* dbg;     // diagnostic: per-item phase stamps (s_memrealtime), nullptr in production
     u32 dbg_flags;               // diagnostic ablations: 1 = skip lookups, 2 = skip inserts, 4 = no output stores (results wrong on purpose); 8 = test hook: the cuckoo emit kernel sends every 7th item down its retry path (results exact)
+    // row-id join (FJ_ALGO_ROW_IDS): both sides' values are row positions (chunk pools: the vals plane; flat arrays: the index
+    // itself, vals == nullptr); the writers put the probe row's position in out_keys and the build row's in out_vals
+    u32 row_ids;
 };
 // next_item: device word for the persistent counting kernel's work counter (nullptr: one workgroup per item)
 hipError_t fj_launch_lds_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, u32* next_item = nullptr,
@@ -222,6 +227,8 @@ struct FjGtArgs {                // global (non-partitioned) table
     unsigned long long* total;
     const u64* out_off;                     // [grid+1]
     u64* out_keys; u64* out_vals;
+    u32 row_ids;                            // row-id join: tvals hold first-occurrence row indices (fj_gt_build_first_kernel); the writer
+                                            // puts the probe row's index in out_keys and the table's in out_vals
 };
 hipError_t fj_launch_gt_build(const FjGtArgs& a, hipStream_t s);
 hipError_t fj_launch_gt_probe(const FjGtArgs& a, bool materialize, u32 grid, hipStream_t s);

@@ -218,8 +218,11 @@ constexpr u32 JP_META = 512;    // probe-side chunk-list entries staged in LDS p
 // sides are fetched together, all build keys of the partition are requested in one shot (not chunk
 // by chunk), and probe keys are prefetched two rounds (2 x 8 keys per lane) ahead; the first two
 // rounds are requested before the table is even initialised.
-template <bool MAT, int NT, bool LIST>
+// RID (MAT only): the row-id form (FjLdsJoinArgs::row_ids) - the build values are row positions, the smallest wins (a.dedup) and
+// is written as it is; the probe row's position comes from the probe side's vals plane at the key's own slot (flat arrays: its index)
+template <bool MAT, int NT, bool LIST, bool RID = false>
 __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
+    static_assert(!RID || MAT, "row ids are written by the emitting pass");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     JoinHdr* hdr = reinterpret_cast<JoinHdr*>(smem);
     u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(JoinHdr));
@@ -305,7 +308,7 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
                 if (off < FJ_LIST_CNT(e)) {
                     const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
                     bk[j] = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);
-                    if (MAT) bv[j] = a.build.vals[src];
+                    if (MAT) bv[j] = (RID && !a.build.vals) ? src : a.build.vals[src];
                     bok |= 1u << j;
                 }
             }
@@ -397,10 +400,12 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
             atomicMin((unsigned long long*)&tvals[sl], (unsigned long long)best);
         }
         __syncthreads();
-        for (u32 sl = tid; sl < S; sl += NT)
-            if (reinterpret_cast<const unsigned char*>(ttags)[sl] != 0) tvals[sl] = a.orig_vals[tvals[sl]];
-        if (tid == 0 && hdr->has_empty) hdr->empty_val = a.orig_vals[hdr->empty_val];
-        __syncthreads();
+        if (!RID) {                                         // (row ids: the winning index is the output)
+            for (u32 sl = tid; sl < S; sl += NT)
+                if (reinterpret_cast<const unsigned char*>(ttags)[sl] != 0) tvals[sl] = a.orig_vals[tvals[sl]];
+            if (tid == 0 && hdr->has_empty) hdr->empty_val = a.orig_vals[hdr->empty_val];
+            __syncthreads();
+        }
     }
     const bool has_empty = hdr->has_empty != 0;
     const u64 obase = MAT ? a.out_off[item] : 0;
@@ -448,7 +453,15 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
                             if ((m >> lane) & 1ull) {
                                 const u64 o = obase + wb + off[i] + (u32)__popcll(m & ((1ull << lane) - 1ull));
                                 if (a.dbg_flags & 4u) continue;             // (ablation: no output stores)
-                                a.out_keys[o] = fj_key_unmix(k2[i]);          // (tables and chunk pools hold mixed keys)
+                                if (RID) {
+                                    // the key's slot in the probe round (load_round's layout): a hit is a valid key, c < nbatch
+                                    const u32 ks = 4u * (u32)hgrp + (u32)i;
+                                    const u32 c = r * CPR + (ks >> 1) * CPL + tid / (FJ_CHUNK / 2), off = (tid % (FJ_CHUNK / 2)) * 2 + (ks & 1u);
+                                    const u64 src = (u64)FJ_LIST_ID(pm[c]) * FJ_CHUNK + off;
+                                    a.out_keys[o] = a.probe.vals ? a.probe.vals[src] : src;
+                                } else {
+                                    a.out_keys[o] = fj_key_unmix(k2[i]);          // (tables and chunk pools hold mixed keys)
+                                }
                                 a.out_vals[o] = k2[i] == FJ_EMPTY_KEY ? hdr->empty_val : tvals[where[i]];
                             }
                         }
@@ -969,7 +982,11 @@ struct EkHdr { u32 has_empty, nstash, full, dups, cursor, novf, cur2[2]; u64 emp
 // hides under a whole round of LDS lookups.  Pair order is unspecified (as everywhere); the cursor ends as the match count.
 // Duplicate build keys are reported exactly (FJ_STAT_DUPS, the sweep of the counting kernels) and the host then discards the
 // output and runs the two-pass first-occurrence path.
-template <int NT, bool DEDUP, bool SINGLE = false>
+// RID: the row-id form (FjLdsJoinArgs::row_ids).  The build values are row positions (DEDUP: the smallest wins and is written as it
+// is, no gather); the probe row's position is read from the probe pool's values plane at the key's slot.  SINGLE: once a round is
+// probed its keys are not needed any more - the pending round's kp[8] holds the hits' positions instead (loaded when the round
+// becomes pending, while its list entries are still staged; the loads complete under the next round).
+template <int NT, bool DEDUP, bool SINGLE = false, bool RID = false>
 __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a, u32* __restrict__ next_item) {
     static_assert(!(SINGLE && DEDUP), "the single-pass form serves unique build keys");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1089,7 +1106,7 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
         u32 nrounds = (nbatch + CPR - 1) / CPR;
         if (lv) {
             load_round(pm, 0, nbatch, ka, oka);
-            if (!SINGLE && nrounds > 1) load_round(pm, 1, nbatch, kb, okb);
+            if (!SINGLE && !RID && nrounds > 1) load_round(pm, 1, nbatch, kb, okb);      // (RID: one round ahead, as SINGLE: registers)
             // ---- build, step 1: keys ----
             u32 nbb = d.nbc < JB_META ? d.nbc : JB_META;
             for (u32 bb = 0; bb < d.nbc; bb += JB_META) {
@@ -1156,7 +1173,7 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
                     else if (code == 0xFFFFu) val = hdr->empty_val;
                     else val = hdr->stash_val[code - S];
                     const u64 o = gb + wbp + pre + (u32)__popcll(m & ((1ull << lane) - 1ull));
-                    a.out_keys[o] = fj_key_unmix(kp[i]);
+                    a.out_keys[o] = RID ? kp[i] : fj_key_unmix(kp[i]);
                     a.out_vals[o] = val;
                 }
                 pre += (u32)__popcll(m);
@@ -1190,7 +1207,7 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
             }
         }
         __syncthreads();                                     // values are in place
-        if (DEDUP && lv && !full) {                          // winning row indices -> values (one gather from the caller's array)
+        if (DEDUP && !RID && lv && !full) {                  // winning row indices -> values (one gather from the caller's array)
             {   // all gathers of a thread in flight together (unconditional loads: row 0 stands in where there is nothing to fetch)
                 u64 v[S / NT]; u32 okm = 0;
 #pragma unroll
@@ -1288,8 +1305,20 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
                             gbv = totp ? atomicAdd(a.out_cursor, (unsigned long long)totp) : 0ull;   // not waited for here
                         }
                         if (pend) flush();
+                        if constexpr (RID) {
+                            // the hits' probe positions, from the slots load_round read their keys from (pm holds this batch)
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) kp[i] = k[i];
+                            for (int i = 0; i < 8; ++i) {
+                                kp[i] = 0;
+                                if ((hb >> i) & 1u) {
+                                    const u32 c = r * CPR + (u32)(i >> 1) * CPL + tid / (FJ_CHUNK / 2), off = (tid % (FJ_CHUNK / 2)) * 2 + (u32)(i & 1);
+                                    kp[i] = a.probe.vals[(u64)FJ_LIST_ID(pm[c]) * FJ_CHUNK + off];
+                                }
+                            }
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) kp[i] = k[i];
+                        }
 #pragma unroll
                         for (int i = 0; i < 4; ++i) scp[i] = sc[i];
                         hbp = hb; wbp = wb; pend = true; par ^= 1u;
@@ -1306,15 +1335,23 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
                         __syncthreads();
                         nrounds = (nbatch + CPR - 1) / CPR;
                         load_round(pm, 0, nbatch, ka, oka);
-                        if (nrounds > 1) load_round(pm, 1, nbatch, kb, okb);
+                        if (!RID && nrounds > 1) load_round(pm, 1, nbatch, kb, okb);
                     }
                     for (u32 r = 0; r < nrounds; ++r) {
                         u64 k[8];
+                        u32 okm;
+                        if constexpr (RID) {                      // one round ahead: the position loads of the writes need the registers
     #pragma unroll
-                        for (int i = 0; i < 8; ++i) { k[i] = ka[i]; ka[i] = kb[i]; }
-                        const u32 okm = oka;
-                        oka = okb;
-                        if (r + 2 < nrounds) load_round(pm, r + 2, nbatch, kb, okb);
+                            for (int i = 0; i < 8; ++i) k[i] = ka[i];
+                            okm = oka;
+                            if (r + 1 < nrounds) load_round(pm, r + 1, nbatch, ka, oka);
+                        } else {
+    #pragma unroll
+                            for (int i = 0; i < 8; ++i) { k[i] = ka[i]; ka[i] = kb[i]; }
+                            okm = oka;
+                            oka = okb;
+                            if (r + 2 < nrounds) load_round(pm, r + 2, nbatch, kb, okb);
+                        }
     #pragma unroll
                         for (int h = 0; h < 8; h += 4) {              // two halves of 4 keys: 8 LDS reads in flight per lane
                             u64 c1[4], c2[4];
@@ -1354,7 +1391,13 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
                                     const u64 m = hitm[i];
                                     if ((m >> lane) & 1ull) {
                                         const u64 o = obase + wb + off[i] + (u32)__popcll(m & ((1ull << lane) - 1ull));
-                                        a.out_keys[o] = fj_key_unmix(k[h + i]);
+                                        if constexpr (RID) {              // the probe row's position, from the key's own slot (a hit: c < nbatch)
+                                            const u32 ks = (u32)(h + i);
+                                            const u32 c = r * CPR + (ks >> 1) * CPL + tid / (FJ_CHUNK / 2), po = (tid % (FJ_CHUNK / 2)) * 2 + (ks & 1u);
+                                            a.out_keys[o] = a.probe.vals[(u64)FJ_LIST_ID(pm[c]) * FJ_CHUNK + po];
+                                        } else {
+                                            a.out_keys[o] = fj_key_unmix(k[h + i]);
+                                        }
                                         a.out_vals[o] = val[i];
                                     }
                                 }
@@ -1446,7 +1489,8 @@ __device__ __forceinline__ bool gt_lookup(const u64* __restrict__ tkeys, u64 cap
     return false;
 }
 
-template <bool MAT, bool BLOOM>
+// RID: the row-id form (FjGtArgs::row_ids): the probe row's index in out_keys, the table's first-occurrence row index in out_vals
+template <bool MAT, bool BLOOM, bool RID = false>
 __global__ __launch_bounds__(256) void fj_gt_probe_kernel(FjGtArgs a) {
     __shared__ u32 s_cnt, s_cursor;
     const u32 tid = threadIdx.x, lane = tid & 63, g = blockIdx.x, G = gridDim.x;
@@ -1498,7 +1542,7 @@ __global__ __launch_bounds__(256) void fj_gt_probe_kernel(FjGtArgs a) {
                     wb = __shfl(wb, 0, 64);
                     if (hit) {
                         const u64 o = obase + wb + (u32)__popcll(m & ((1ull << lane) - 1ull));
-                        a.out_keys[o] = k[i];
+                        a.out_keys[o] = RID ? 2 * pi + (u64)i : k[i];
                         a.out_vals[o] = val;
                     }
                 }
@@ -1542,7 +1586,8 @@ __global__ __launch_bounds__(256) void fj_gt_build_first_kernel(FjGtArgs a) {
 
 // probe: rounds of 4096 rows per workgroup (4 per thread), hits from the front (a.total), misses from the back (miss_cursor);
 // LEFT: the value is gathered from the caller's build_values by the slot's row index
-template <int MODE>
+// RID: the row-id form - probe row indices in out_keys, the winning build row index (LEFT; all ones for a miss) in out_vals
+template <int MODE, bool RID = false>
 __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, unsigned long long* miss_cursor, u64 out_capacity) {
     constexpr bool VALS = MODE != FJ_OJ_ANTI;
     constexpr u32 NT = 1024, KPT = 4;
@@ -1587,12 +1632,12 @@ __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, uns
             if ((hit >> u) & 1u) {
                 const u64 o = hpos + (u32)__popcll(hb[u] & below);
                 const u64 row = k[u] == FJ_EMPTY_KEY ? *a.empty_val : a.tvals[where[u]];
-                if (o < out_capacity) { a.out_keys[o] = k[u]; a.out_vals[o] = a.bv[row]; }
+                if (o < out_capacity) { a.out_keys[o] = RID ? base + u * NT + tid : k[u]; a.out_vals[o] = RID ? row : a.bv[row]; }
             }
             if ((miss >> u) & 1u) {
                 const u64 m = mpos + (u32)__popcll(mb[u] & below);
                 const u64 o = VALS ? np - 1 - m : m;                      // LEFT: from the back; ANTI: rows [0, u)
-                if (m < np && o < out_capacity) { a.out_keys[o] = k[u]; if (VALS) a.out_vals[o] = 0; }
+                if (m < np && o < out_capacity) { a.out_keys[o] = RID ? base + u * NT + tid : k[u]; if (VALS) a.out_vals[o] = RID ? ~0ull : 0ull; }
             }
             hpos += (u32)__popcll(hb[u]); mpos += (u32)__popcll(mb[u]);
         }
@@ -1750,15 +1795,18 @@ hipError_t fj_launch_lds_join(const FjLdsJoinArgs& a, bool materialize, hipStrea
     const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;       // grid of the one-workgroup-per-item kernels
     if (materialize) {
         // chunk lists on both sides, unique build keys: the cuckoo form (resident workgroups, one per CU, next item prefetched)
+        if (a.row_ids && (!a.dedup || a.orig_vals)) return hipErrorInvalidValue;     // row ids: the smallest build row wins, no gather
         if (a.build.list && a.probe.list && a.items && next_item && nb >= persistent_min_items && !a.dbg && !(a.dbg_flags & ~8u)) {
             const u32 ldsp = sizeof(EkHdr) + 2 * S * 8 + 2 * (JP_META + JB_META) * 4 + 16 + S / 8 + CK_OVF * 8;
-            auto pk = a.dedup ? fj_emit_join_persistent<1024, true> : fj_emit_join_persistent<1024, false>;
+            auto pk = a.row_ids ? fj_emit_join_persistent<1024, true, false, true>
+                                : a.dedup ? fj_emit_join_persistent<1024, true> : fj_emit_join_persistent<1024, false>;
             hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(pk), ldsp);
             if (e != hipSuccess) return e;
             const u32 grid = nb < 256 ? nb : 256;            // (*next_item is zero: the emitting pass has its own counter word)
             hipLaunchKernelGGL(pk, dim3(grid), dim3(1024), ldsp, s, a, next_item);
             return hipGetLastError();
         }
+        if (a.row_ids) return fj_launch_lds_emit_retry(a, s, false);      // few items: the tagged kernel's row-id form, one workgroup per item
         const u32 lds = sizeof(JoinHdr) + 2 * S * 8 + S + S / 2 + (JP_META + JB_META) * 4;
         auto kern = (a.build.list && a.probe.list) ? fj_lds_join_kernel<true, 1024, true> : fj_lds_join_kernel<true, 1024, false>;
         hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
@@ -1788,10 +1836,11 @@ hipError_t fj_launch_lds_join(const FjLdsJoinArgs& a, bool materialize, hipStrea
 }
 
 hipError_t fj_launch_emit_single(const FjLdsJoinArgs& a, hipStream_t s, u32* next_item) {
-    if (!a.build.list || !a.probe.list || !a.items || !next_item || !a.out_cursor || a.dedup || !a.build.vals) return hipErrorInvalidValue;
+    if (!a.build.list || !a.probe.list || !a.items || !next_item || !a.out_cursor || a.dedup || !a.build.vals || (a.row_ids && !a.probe.vals))
+        return hipErrorInvalidValue;
     const u32 nb = a.items_cap;
     const u32 ldsp = sizeof(EkHdr) + 2 * S * 8 + 2 * (JP_META + JB_META) * 4 + 16 + S / 8 + CK_OVF * 8;
-    auto pk = fj_emit_join_persistent<1024, false, true>;
+    auto pk = a.row_ids ? fj_emit_join_persistent<1024, false, true, true> : fj_emit_join_persistent<1024, false, true>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(pk), ldsp);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pk, dim3(nb < 256 ? nb : 256), dim3(1024), ldsp, s, a, next_item);
@@ -1804,7 +1853,10 @@ hipError_t fj_launch_lds_emit_retry(const FjLdsJoinArgs& a0, hipStream_t s, bool
     a.retry_only = only_marked ? 1u : 0u;
     const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;
     const u32 lds = sizeof(JoinHdr) + 2 * S * 8 + S + S / 2 + (JP_META + JB_META) * 4;
-    auto kern = (a.build.list && a.probe.list) ? fj_lds_join_kernel<true, 1024, true> : fj_lds_join_kernel<true, 1024, false>;
+    if (a.row_ids && (!a.dedup || a.orig_vals)) return hipErrorInvalidValue;     // row ids: the smallest build row wins, no gather
+    const bool lists = a.build.list && a.probe.list;
+    auto kern = a.row_ids ? (lists ? fj_lds_join_kernel<true, 1024, true, true> : fj_lds_join_kernel<true, 1024, false, true>)
+                          : (lists ? fj_lds_join_kernel<true, 1024, true> : fj_lds_join_kernel<true, 1024, false>);
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(1024), lds, s, a);
@@ -1840,7 +1892,10 @@ hipError_t fj_launch_gt_build(const FjGtArgs& a, hipStream_t s) {
 
 hipError_t fj_launch_gt_probe(const FjGtArgs& a, bool materialize, u32 grid, hipStream_t s) {
     const bool bloom = a.bloom != nullptr;
-    if (materialize) {
+    if (materialize && a.row_ids) {
+        if (bloom) return hipErrorInvalidValue;          // (a row-id table is built by fj_gt_build_first_kernel, which sets no filter bits)
+        hipLaunchKernelGGL((fj_gt_probe_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, a);
+    } else if (materialize) {
         if (bloom) hipLaunchKernelGGL((fj_gt_probe_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((fj_gt_probe_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
     } else {
@@ -1862,9 +1917,14 @@ hipError_t fj_launch_gt_build_first(const FjGtArgs& a, bool vals, hipStream_t s)
 
 hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long long* miss_cursor, u64 out_capacity, hipStream_t s) {
     if (a.np == 0) return hipSuccess;
-    if (!a.out_keys || !miss_cursor || (mode != FJ_OJ_ANTI && (!a.out_vals || !a.tvals || !a.bv))) return hipErrorInvalidValue;
+    if (!a.out_keys || !miss_cursor || (mode != FJ_OJ_ANTI && (!a.out_vals || !a.tvals || (!a.bv && !a.row_ids)))) return hipErrorInvalidValue;
     const u64 rounds = (a.np + 4095) / 4096;
     const u32 grid = (u32)(rounds < 2048 ? rounds : 2048);
+    if (a.row_ids) {
+        if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_ANTI, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+        else hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_LEFT, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+        return hipGetLastError();
+    }
     if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_ANTI>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
     else hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_LEFT>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
     return hipGetLastError();

@@ -19,7 +19,11 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
     if (pd.count > 0) {
         void* p;
         if (pd.kind == Pending::LDS) {
-            if (pd.has_dups) {
+            if (pd.lds.row_ids) {
+                // row ids: the build pool's values are row positions already - the smallest per key is the first occurrence, and it
+                // is the output as it stands (no second build-side partition, no gather)
+                pd.lds.dedup = 1; pd.lds.orig_vals = nullptr;
+            } else if (pd.has_dups) {
                 // duplicate build keys: the reference's radix path keeps the FIRST occurrence (stable partition +
                 // insert_local, hash_join.cpp:125).  Re-partition the build side with row indices as payload; the
                 // join kernel keeps the smallest index per key and fetches its value from the caller's array.
@@ -66,7 +70,8 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
                 if (get_buf(c, W_OUT_OFF2, ((size_t)pd.nitems2 + 1) * 8, &p)) return 1;
                 HIPCHK(fj_launch_scan_u32_to_u64(pd.lds2.part_count, (u64*)p, pd.nitems2, s));
                 pd.lds2.out_off = (const u64*)p; pd.lds2.out_keys = d_ok + pd.count_main; pd.lds2.out_vals = d_ov + pd.count_main;
-                pd.lds2.dedup = pd.has_dups ? 1u : 0u; pd.lds2.orig_vals = pd.has_dups ? pd.bv : nullptr; pd.lds2.dbg = nullptr;
+                const bool rid = pd.lds2.row_ids != 0;
+                pd.lds2.dedup = (pd.has_dups || rid) ? 1u : 0u; pd.lds2.orig_vals = (pd.has_dups && !rid) ? pd.bv : nullptr; pd.lds2.dbg = nullptr;
                 HIPCHK(fj_launch_lds_emit_retry(pd.lds2, s, false));  // (the tagged emit kernel over every item of the set: a few hundred items)
             }
         } else if (pd.kind == Pending::MANY) {      // many-to-many: count per item -> scan -> emit
@@ -106,8 +111,10 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
 }
 
 // non-partitioned path: one table in HBM (Infinity-Cache / L2 resident when small)
+// rid (row-id join): the table keeps every key's FIRST row index (fj_gt_build_first_kernel), no filter
 int join_global(fj_ctx* c, int bloom, int materialize, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np,
-                hipStream_t s, fj_timings* t, u64* out_count) {
+                hipStream_t s, fj_timings* t, u64* out_count, bool rid = false) {
+    if (rid) bloom = 0;
     u64 cap = 64;
     while (cap < 2 * (u64)nb) cap <<= 1;
     FjGtArgs a{};
@@ -120,12 +127,18 @@ int join_global(fj_ctx* c, int bloom, int materialize, const u64* bk, const u64*
     const u32 grid = (u32)std::min<u64>(2048, std::max<u64>(1, npairs / 256));
     if (get_buf(c, W_WG_COUNT, (size_t)grid * 4, &p)) return 1; a.wg_count = (u32*)p;
     a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.bv = bv; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    a.bk = bk; a.bv = rid ? nullptr : bv; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    a.row_ids = rid ? 1u : 0u;
 
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
     HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
     if (a.bloom) HIPCHK(hipMemsetAsync(a.bloom, 0, cap / 8 * 4, s));
+    if (rid) {                                       // (row index minimum: all ones at rest)
+        HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));
+        HIPCHK(hipMemsetAsync(a.tvals, 0xFF, cap * 8, s));
+        HIPCHK(fj_launch_gt_build_first(a, true, s));
+    } else
     HIPCHK(fj_launch_gt_build(a, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
@@ -237,7 +250,7 @@ int skew_join(fj_ctx* c, const FjLdsJoinArgs& ja, const Plan& plan, int top_bits
     const bool had_dups = (c->h_sc->err & FJ_STAT_DUPS) != 0;
     HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, 4, s));                              // the main join's status bits have been acted on
     if (skew_side(c, bit2, 0, materialize != 0, ja.build, bo, bchunks, S, top_bits - plan.bits, plan.npass, W_SK_TILES_B, d_nt, s)) return 1;
-    if (skew_side(c, pit2, 1, false, ja.probe, po, pchunks, S, top_bits - plan.bits, probe_slot, W_SK_TILES_P, d_nt + 1, s)) return 1;
+    if (skew_side(c, pit2, 1, ja.row_ids != 0, ja.probe, po, pchunks, S, top_bits - plan.bits, probe_slot, W_SK_TILES_P, d_nt + 1, s)) return 1;   // (row ids: the probe positions travel)
     FjLdsJoinArgs j2 = ja;
     j2.build = bit2.prev; j2.probe = pit2.prev; j2.nparts = j2.probe.nb; j2.nsplit = 1;
     j2.items = pit2.tiles; j2.nitems_dev = pit2.ntiles; j2.items_cap = pit2.items_cap; j2.part_count = pit2.part_count;
@@ -392,8 +405,9 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
 // radix path: partition both relations, then one LDS-table join per final partition
 // bloom: 0 = no precheck, 1 = precheck whenever the plan allows one (the *_bloom functions), 2 = decide from a sample
 // of the probe side (the adaptive_* functions): SURVEY 8(f) "bloom auto-enable by sampled hit rate"
+// rid: row-id join (materialising, no precheck): both sides' first passes make the rows' positions as values
 int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
-               hipStream_t s, fj_timings* t, u64* out_count, bool* lds_full, SingleOut* so = nullptr) {
+               hipStream_t s, fj_timings* t, u64* out_count, bool* lds_full, SingleOut* so = nullptr, bool rid = false) {
     Plan plan = make_plan(nb, top_bits, bloom != 0);
     *lds_full = false;
     t->sampled_hit_bp = -1;
@@ -408,11 +422,12 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
     PassIter bit, pit;
     // a counting join never looks at a value: its build side moves keys only (half the build-phase bytes)
     pass_init(bit, 0, materialize != 0, nb, plan, top_bits);
+    bit.vals_pos = rid;
     int evc = 0;
     if (plan.bloom_level > 0) bit.save_level = plan.bloom_level;
     // build relation first, then the probe relation, on the caller's stream (the build-side filter of a bloom plan needs
     // the whole build side anyway)
-    if (run_passes(c, bit, bk, materialize ? bv : nullptr, s, &ja.build, nullptr)) return 1;
+    if (run_passes(c, bit, bk, (materialize && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     Plan pplan = plan;
     if (bloom == 2) {
@@ -428,7 +443,8 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
         t->sampled_hit_bp = (int)hit_bp;
         if (hit_bp > (u32)options().bloom_auto_max_hit_bp) { pplan = make_plan(nb, top_bits, false); plan.bloom_level = 0; plan.npass = pplan.npass; }
     }
-    pass_init(pit, 1, false, np, pplan, top_bits);
+    pass_init(pit, 1, rid, np, pplan, top_bits);
+    pit.vals_pos = rid;
     pit.want_items = true;
     {
         // probe rows that will reach the join: behind the filter the sampled hit rate + what the filter lets through (~10 % of the misses);
@@ -442,6 +458,7 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
     if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     ja.avg_build_keys = (u32)std::min<u64>(0xFFFFFFFFu, (u64)nb >> plan.bits);
+    ja.row_ids = rid ? 1u : 0u;
     if (radix_join_tail(c, materialize, ja, plan, np, pit, s, t, evc, out_count, lds_full, top_bits, so)) return 1;
     if (c->pend.valid) { c->pend.bk = bk; c->pend.bv = bv; c->pend.nb = nb; c->pend.top_bits = top_bits; }
     return 0;
@@ -451,7 +468,7 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
 // materialising), then the probe relation, then one workgroup per work item; no bloom stage, no fallback: a partition of
 // more than 4096 build rows is an error.
 int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
-              hipStream_t s, fj_timings* t, u64* out_count) {
+              hipStream_t s, fj_timings* t, u64* out_count, bool rid = false) {
     const Plan plan = make_plan(nb, top_bits, false, 2048);          // aim at half of the kernel's 4096 rows per partition
     begin_plan(c);
     HIPCHK(hipEventRecord(c->ev[E_START], s));
@@ -459,10 +476,12 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
     FjLdsJoinArgs ja{};
     PassIter bit, pit;
     pass_init(bit, 0, materialize != 0, nb, plan, top_bits);
-    pass_init(pit, 1, false, np, plan, top_bits);
+    pass_init(pit, 1, rid, np, plan, top_bits);
+    bit.vals_pos = pit.vals_pos = rid;                               // (row ids: both sides' first passes make the positions)
     pit.want_items = true;
     int evc = 0;
-    if (run_passes(c, bit, bk, materialize ? bv : nullptr, s, &ja.build, nullptr)) return 1;
+    ja.row_ids = rid ? 1u : 0u;
+    if (run_passes(c, bit, bk, (materialize && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
@@ -504,7 +523,15 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                    uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, fj_timings* timings) {
     const bool many = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
+    const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
+    if (rid) {
+        // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
+        algo &= ~FJ_ALGO_ROW_IDS;
+        if (!materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
+        if (!d_bv) d_bv = d_bk;                             // never read: the build rows' positions are made on the device
+        bloom = 0;                                          // (the filter kernel moves no payload)
+    }
     if (left || anti) {
         // left outer / anti join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
         algo &= ~(FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI);
@@ -533,7 +560,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
     if ((left || anti) && materialize) {                    // one pass over the probe side, never a pending result
         if (join_outer(c, left ? FJ_OJ_LEFT : FJ_OJ_ANTI, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count,
-                       (u64*)d_out_keys, (u64*)d_out_vals)) return 1;
+                       (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;
@@ -542,23 +569,23 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     if (nb == 0 || np == 0) {                   // empty side: (0, t), hash_join.cpp behaviour for empty inputs
         count = 0;
     } else if (many) {
-        if (join_many(c, materialize, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count)) return 1;
+        if (join_many(c, materialize, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, rid)) return 1;
     } else if (use_radix) {
         bool lds_full = false;
         // adaptive_*: the precheck is decided from a sample of the probe side; *_bloom by name: always on; otherwise off
-        const int bloom_mode = algo == FJ_ALGO_ADAPTIVE ? (options().bloom_auto ? 2 : (bloom ? 1 : 0)) : (bloom ? 1 : 0);
+        const int bloom_mode = rid ? 0 : algo == FJ_ALGO_ADAPTIVE ? (options().bloom_auto ? 2 : (bloom ? 1 : 0)) : (bloom ? 1 : 0);
         SingleOut so;
         so.keys = (u64*)d_out_keys; so.vals = (u64*)d_out_vals; so.cap = out_capacity;
         const bool try_single = materialize && d_out_keys && d_out_vals && out_capacity >= np && options().mat_single_pass &&
                                 !(((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7);
-        if (join_radix(c, materialize, bloom_mode, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, &lds_full, try_single ? &so : nullptr)) return 1;
+        if (join_radix(c, materialize, bloom_mode, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, &lds_full, try_single ? &so : nullptr, rid)) return 1;
         if (lds_full) {
             fj_timings t2; memset(&t2, 0, sizeof t2);
-            if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t2, &count)) return 1;
+            if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t2, &count, rid)) return 1;
             t2.total_ms += t.total_ms; t2.fell_back = 1; t2.sampled_hit_bp = t.sampled_hit_bp; t = t2;
         }
     } else {
-        if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t, &count)) return 1;
+        if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t, &count, rid)) return 1;
     }
     if (anti) count = np - count;                           // counting anti join: the probe rows the N:1 count leaves out
     if (out_count) *out_count = count;

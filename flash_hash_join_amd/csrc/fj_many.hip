@@ -27,7 +27,9 @@ __device__ __forceinline__ u32 mm_entry(const FjChunkSet& cs, u32 idx) {       /
     return ((cnt - 1u) << 24) | idx;
 }
 
-template <bool MAT>
+// RID (MAT only): the row-id form (FjLdsJoinArgs::row_ids) - build values are row positions, and the probe row's position
+// (its vals plane; flat arrays: the index) takes the key's place
+template <bool MAT, bool RID = false>
 __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MmHdr* hdr = reinterpret_cast<MmHdr*>(smem);
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a) {
                 const u32 r = atomicAdd(&hdr->nrows, 1u);
                 if (r >= MM_ROWS) hdr->full = 1;
                 else {
-                    if (MAT) rvals[r] = a.build.vals[src];
+                    if (MAT) rvals[r] = (RID && !a.build.vals) ? src : a.build.vals[src];
                     u32* h;
                     if (key == FJ_EMPTY_KEY) h = &hdr->empty_head;        // the empty marker is never stored in the table
                     else {
@@ -96,10 +98,11 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a) {
     unsigned long long local = 0;
     for (u32 pc = s_lo; pc < s_hi; pc += MM_NT / FJ_CHUNK) {
         const u32 c = pc + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
-        u64 key = 0; bool ok = false;
+        u64 key = 0, psrc = 0; bool ok = false;
         if (c < s_hi) {
             const u32 e = mm_entry(a.probe, c);
-            if (off < FJ_LIST_CNT(e)) { key = a.probe.keys[(u64)FJ_LIST_ID(e) * FJ_CHUNK + off]; if (!a.probe.list) key = fj_key_mix(key); ok = true; }
+            psrc = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            if (off < FJ_LIST_CNT(e)) { key = a.probe.keys[psrc]; if (!a.probe.list) key = fj_key_mix(key); ok = true; }
         }
         u32 h = MM_NONE;
         if (ok) {
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a) {
             if (lane == 63) wb = atomicAdd(&hdr->cursor, wave_total);
             wb = __shfl(wb, 63, 64);
             u64 o = obase + wb + (inc - cnt);
-            const u64 raw = fj_key_unmix(key);
+            const u64 raw = RID ? ((h != MM_NONE && a.probe.vals) ? a.probe.vals[psrc] : psrc) : fj_key_unmix(key);     // (read by the lanes that write)
             for (u32 r = h; r != MM_NONE; r = rnext[r]) { a.out_keys[o] = raw; a.out_vals[o] = rvals[r]; ++o; }
         }
     }
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a) {
 hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s) {
     const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;
     const u32 lds = sizeof(MmHdr) + MM_S * 8 + MM_ROWS * 8 + MM_S * 4 + MM_ROWS * 4;
-    auto kern = materialize ? fj_mm_join_kernel<true> : fj_mm_join_kernel<false>;
+    auto kern = materialize ? (a.row_ids ? fj_mm_join_kernel<true, true> : fj_mm_join_kernel<true>) : fj_mm_join_kernel<false>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(MM_NT), lds, s, a);

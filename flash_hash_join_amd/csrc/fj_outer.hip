@@ -35,9 +35,12 @@ __device__ __forceinline__ u32 oj_entry(const FjChunkSet& cs, u32 idx) {       /
     return ((cnt - 1u) << 24) | idx;
 }
 
-template <int MODE>
+// RID: the row-id form (FjLdsJoinArgs::row_ids; MODE LEFT_FIRST or ANTI) - build values are row positions and the smallest is
+// written as it is; every output row gets the probe row's position (its vals plane; flat arrays: the index), a miss the value ~0
+template <int MODE, bool RID = false>
 __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a, u64 np, unsigned long long* miss_cursor) {
     constexpr bool VALS = MODE != FJ_OJ_ANTI, FIRST = MODE == FJ_OJ_LEFT_FIRST;
+    static_assert(!RID || MODE != FJ_OJ_LEFT, "row ids: the first occurrence wins");
     constexpr u32 TS = VALS ? 8192u : 16384u, LIMIT = TS - TS / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     OjHdr* hdr = reinterpret_cast<OjHdr*>(smem);
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
         if (off >= FJ_LIST_CNT(e)) continue;
         const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
         const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
-        const u64 val = VALS ? a.build.vals[src] : 0;
+        const u64 val = VALS ? ((RID && !a.build.vals) ? src : a.build.vals[src]) : 0;
         if (key == FJ_EMPTY_KEY) {                           // the empty marker is never stored in the table
             const u32 before = atomicAdd(&hdr->empty_cnt, 1u);
             if (FIRST) atomicMin((unsigned long long*)&hdr->empty_val, (unsigned long long)val);
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
     if (hdr->full) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }     // the host re-runs the join on the HBM table
     if (VALS && !FIRST && hdr->dups) { if (tid == 0) atomicOr(a.err, FJ_STAT_DUPS); return; }   // ... or this one with row indices
     const bool has_empty = hdr->empty_cnt != 0;
-    if (FIRST) {                                             // winning row indices -> the caller's values
+    if (FIRST && !RID) {                                     // winning row indices -> the caller's values
         for (u32 i = tid; i < TS; i += OJ_NT) if (tkeys[i] != FJ_EMPTY_KEY) tvals[i] = a.orig_vals[tvals[i]];
         if (tid == 0 && has_empty) hdr->empty_val = a.orig_vals[hdr->empty_val];
         __syncthreads();
@@ -113,22 +116,25 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
 
     // ---- probe: rounds of OJ_NT * OJ_KPT rows, hits to the front, misses to the back; the next round's keys are requested
     // before this round's reservation (its barriers and the global atomic's round trip hide the loads' latency) ----
-    u64 k[OJ_KPT];
+    u64 k[OJ_KPT], rp[RID ? OJ_KPT : 1];                      // rp: the probe rows' positions (RID)
     u32 okm = 0;
-    auto load_round = [&](u32 pc, u64 (&kk)[OJ_KPT], u32& ok) {
+    auto load_round = [&](u32 pc, u64 (&kk)[OJ_KPT], u64 (&pp)[RID ? OJ_KPT : 1], u32& ok) {
         ok = 0;
 #pragma unroll
         for (u32 u = 0; u < OJ_KPT; ++u) {
             const u32 c = pc + u * (OJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0;
+            if (RID) pp[RID ? u : 0] = 0;
             if (c >= s_hi) continue;
             const u32 e = oj_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
-            kk[u] = a.probe.keys[(u64)FJ_LIST_ID(e) * FJ_CHUNK + off];
+            const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            kk[u] = a.probe.keys[src];
+            if (RID) pp[RID ? u : 0] = a.probe.vals ? a.probe.vals[src] : src;
             ok |= 1u << u;
         }
     };
-    load_round(s_lo, k, okm);
+    load_round(s_lo, k, rp, okm);
     for (u32 pc = s_lo; pc < s_hi; pc += OJ_ROUND_CHUNKS) {
         u64 v[OJ_KPT];
         u32 hit = 0, miss = 0;
@@ -158,9 +164,9 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
             hb[u] = __ballot((hit >> u) & 1u); mb[u] = __ballot((miss >> u) & 1u);
             nh += (u32)__popcll(hb[u]); nm += (u32)__popcll(mb[u]);
         }
-        u64 kn[OJ_KPT];
+        u64 kn[OJ_KPT], rpn[RID ? OJ_KPT : 1];
         u32 okn = 0;
-        if (pc + OJ_ROUND_CHUNKS < s_hi) load_round(pc + OJ_ROUND_CHUNKS, kn, okn);
+        if (pc + OJ_ROUND_CHUNKS < s_hi) load_round(pc + OJ_ROUND_CHUNKS, kn, rpn, okn);
         u64 hpos, mpos;
         fj_oj_reserve(&hdr->cur, nh, nm, lane, tid, a.out_cursor, miss_cursor, hpos, mpos);
         const u64 below = (1ull << lane) - 1ull;
@@ -168,21 +174,21 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
         for (u32 u = 0; u < OJ_KPT; ++u) {
             if ((hit >> u) & 1u) {
                 const u64 o = hpos + (u32)__popcll(hb[u] & below);
-                if (o < a.out_capacity) { a.out_keys[o] = fj_key_unmix(k[u]); a.out_vals[o] = v[u]; }
+                if (o < a.out_capacity) { a.out_keys[o] = RID ? rp[RID ? u : 0] : fj_key_unmix(k[u]); a.out_vals[o] = v[u]; }
                 else atomicOr(a.err, FJ_ERR_OUTCAP);
             }
             if ((miss >> u) & 1u) {
                 const u64 m = mpos + (u32)__popcll(mb[u] & below);
                 const u64 o = VALS ? np - 1 - m : m;          // LEFT: from the back; ANTI: the misses are the whole output
                 if (m < np && o < a.out_capacity) {
-                    a.out_keys[o] = fj_key_unmix(k[u]);
-                    if (VALS) a.out_vals[o] = 0;
+                    a.out_keys[o] = RID ? rp[RID ? u : 0] : fj_key_unmix(k[u]);
+                    if (VALS) a.out_vals[o] = RID ? ~0ull : 0ull;
                 } else atomicOr(a.err, FJ_ERR_OUTCAP);
             }
             hpos += (u32)__popcll(hb[u]); mpos += (u32)__popcll(mb[u]);
         }
 #pragma unroll
-        for (u32 u = 0; u < OJ_KPT; ++u) k[u] = kn[u];
+        for (u32 u = 0; u < OJ_KPT; ++u) { k[u] = kn[u]; if (RID) rp[RID ? u : 0] = rpn[RID ? u : 0]; }
         okm = okn;
     }
 }
@@ -191,10 +197,12 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
 
 hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsigned long long* miss_cursor, hipStream_t s) {
     const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;
-    if (!a.out_cursor || !miss_cursor || !a.out_keys || (mode != FJ_OJ_ANTI && !a.out_vals) || (mode == FJ_OJ_LEFT_FIRST && !a.orig_vals))
+    if (!a.out_cursor || !miss_cursor || !a.out_keys || (mode != FJ_OJ_ANTI && !a.out_vals) || (mode == FJ_OJ_LEFT_FIRST && !a.orig_vals && !a.row_ids))
         return hipErrorInvalidValue;
+    if (a.row_ids && mode == FJ_OJ_LEFT) return hipErrorInvalidValue;            // row ids: LEFT_FIRST (first occurrence) or ANTI
     const u32 lds = (u32)sizeof(OjHdr) + (mode == FJ_OJ_ANTI ? 16384u * 8 : 8192u * 16);
-    auto kern = mode == FJ_OJ_ANTI ? fj_outer_join_kernel<FJ_OJ_ANTI>
+    auto kern = a.row_ids ? (mode == FJ_OJ_ANTI ? fj_outer_join_kernel<FJ_OJ_ANTI, true> : fj_outer_join_kernel<FJ_OJ_LEFT_FIRST, true>)
+              : mode == FJ_OJ_ANTI ? fj_outer_join_kernel<FJ_OJ_ANTI>
               : mode == FJ_OJ_LEFT_FIRST ? fj_outer_join_kernel<FJ_OJ_LEFT_FIRST> : fj_outer_join_kernel<FJ_OJ_LEFT>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -207,7 +215,7 @@ namespace fjh {
 // the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
 // "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  LEFT builds with row indices (the smallest wins, first occurrence)
 static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, hipStream_t s,
-                             fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov) {
+                             fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid) {
     const bool left = mode != FJ_OJ_ANTI;
     u64 cap = 64;
     while (cap < 2 * (u64)nb) cap <<= 1;
@@ -216,8 +224,8 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
     if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
     if (left) { if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1; a.tvals = (u64*)p; }
     a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.bv = left ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
-    a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr;
+    a.bk = bk; a.bv = (left && !rid) ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr; a.row_ids = rid ? 1u : 0u;
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
     HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));           // (row index minimum)
@@ -243,22 +251,25 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
 
 // FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI with materialize = 1 (fj_join_device has checked the arguments): *out_count = matched probe
 // rows (LEFT) or unmatched ones (ANTI).  use_radix: the partitioned plan, else the global table.
+// rid (row-id join): positions instead of keys and values; LEFT keeps the first occurrence from the start (its build side carries
+// the positions its first pass makes), a miss gets the value ~0
 int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
-               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov) {
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid) {
     const bool left = mode != FJ_OJ_ANTI;
     *out_count = 0;
     if (np == 0) return 0;
     if (nb == 0) {                                           // every probe row is unmatched
         HIPCHK(hipEventRecord(c->ev[E_START], s));
-        HIPCHK(hipMemcpyAsync(d_ok, pk, np * 8, hipMemcpyDeviceToDevice, s));
-        if (left) HIPCHK(hipMemsetAsync(d_ov, 0, np * 8, s));
+        if (rid) HIPCHK(fj_launch_iota(d_ok, np, s));
+        else HIPCHK(hipMemcpyAsync(d_ok, pk, np * 8, hipMemcpyDeviceToDevice, s));
+        if (left) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         HIPCHK(hipStreamSynchronize(s));
         t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
         *out_count = left ? 0 : np;
         return 0;
     }
-    if (!use_radix) return join_outer_global(c, mode, bk, bv, nb, pk, np, s, t, out_count, d_ok, d_ov);
+    if (!use_radix) return join_outer_global(c, mode, bk, bv, nb, pk, np, s, t, out_count, d_ok, d_ov, rid);
 
     const Plan plan = make_plan(nb, top_bits, false);
     begin_plan(c);
@@ -267,10 +278,12 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     FjLdsJoinArgs ja{};
     PassIter bit, pit;
     pass_init(bit, 0, left, nb, plan, top_bits);
+    bit.vals_pos = rid;
     int evc = 0;
-    if (run_passes(c, bit, bk, left ? bv : nullptr, s, &ja.build, nullptr)) return 1;
+    if (run_passes(c, bit, bk, (left && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    pass_init(pit, 1, false, np, plan, top_bits);
+    pass_init(pit, 1, rid, np, plan, top_bits);
+    pit.vals_pos = rid;
     pit.want_items = true;
     if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
@@ -284,12 +297,13 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     }
     ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
     ja.out_cursor = &c->d_sc->total; ja.out_capacity = np; ja.out_keys = d_ok; ja.out_vals = left ? d_ov : nullptr;
-    HIPCHK(fj_launch_outer_join(ja, mode, np, &c->d_sc->expected, s));
+    ja.row_ids = rid ? 1u : 0u;
+    HIPCHK(fj_launch_outer_join(ja, (rid && left) ? FJ_OJ_LEFT_FIRST : mode, np, &c->d_sc->expected, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
     end_plan(c);
-    if (left && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
+    if (left && !rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
         if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
         u64* rowidx = (u64*)p;
@@ -311,7 +325,7 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
         fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_outer_global(c, mode, bk, bv, nb, pk, np, s, &t2, out_count, d_ok, d_ov)) return 1;
+        if (join_outer_global(c, mode, bk, bv, nb, pk, np, s, &t2, out_count, d_ok, d_ov, rid)) return 1;
         t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
         return 0;
     }

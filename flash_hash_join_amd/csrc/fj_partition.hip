@@ -66,11 +66,14 @@ enum { M_SLAB_CUR = 0, M_SLAB_REM, M_NEW_BASE, M_NEED, M_NLINES, M_FLUSH, M_SEG,
 // PK7: the input chunks are in the owner shuffle's 7-byte wire format (FJ_WIRE7_BYTES per chunk: the low words, the middle 16
 // bits and bits 48..55 of the mixed keys as three planes; bits 56..63 are the top bits of the chunk's first-pass bucket) - the
 // pass that reads what other GPUs sent unpacks it in registers (csrc/fj_pack.hip writes the format).
-template <int NT, int KPT, int LINE_LOG, bool HAS_VALS, bool FLAT, bool PROBE_SIDE, int RLOG = FJ_RUN_LOG, bool PK7 = false>
+// POS (flat inputs with values only): the values are the rows' 0-based positions, made here instead of read (row-id joins:
+// no position array exists in HBM).
+template <int NT, int KPT, int LINE_LOG, bool HAS_VALS, bool FLAT, bool PROBE_SIDE, int RLOG = FJ_RUN_LOG, bool PK7 = false, bool POS = false>
 __global__ __launch_bounds__(NT, 4) void fj_partition_kernel(FjPartArgs a) {
     constexpr u32 T = NT * KPT, LINE = 1u << LINE_LOG, TC = T / FJ_CHUNK, NW = NT / 64, LOS = LINE + FJ_LO_PAD;     // LOS: stride of a carry row
     static_assert(T % FJ_CHUNK == 0 && TC <= NT && LINE >= 4 && T + 64 < (1u << 17), "tile geometry");
     static_assert(!PK7 || (!FLAT && KPT % 4 == 0), "wire-format chunks come through chunk lists, four keys per load group");
+    static_assert(!POS || (FLAT && HAS_VALS), "positions are made by the first pass over a flat input");
     // RUNS (RLOG > 0): a bucket takes its chunk ids in aligned runs of RU = 2^RLOG ids (used in a rotated order; what a segment
     // leaves unused of its last run is marked FJ_DIR_INVALID), so that fj_level_lists places RU list entries per step
     // (FjChunkSet::run_log).  The allocator then counts in units of one run.  RLOG == 0: ids one by one in the order the tiles
@@ -152,6 +155,7 @@ __global__ __launch_bounds__(NT, 4) void fj_partition_kernel(FjPartArgs a) {
             if (FLAT) {
                 base = (u64)(t0 + tt) * T + ((u32)i * NT + tid) * 2;
                 nv = base + 1 < a.n_flat ? 2u : (base < a.n_flat ? 1u : 0u);
+                if (POS) { vv[2 * i] = base; vv[2 * i + 1] = base + 1; }
                 if (base > last_pair) base = last_pair;     // stay inside the array (tail tile only)
             } else {
                 const u32 kidx = ((u32)i * NT + tid) * 2;
@@ -162,11 +166,11 @@ __global__ __launch_bounds__(NT, 4) void fj_partition_kernel(FjPartArgs a) {
             }
             if (tiny) {                                      // a 1-key relation: no 16-B load possible
                 kk[2 * i] = nv ? a.in_keys[0] : 0; kk[2 * i + 1] = 0;
-                if (HAS_VALS) { vv[2 * i] = nv ? a.in_vals[0] : 0; vv[2 * i + 1] = 0; }
+                if (HAS_VALS) { vv[2 * i] = (nv && !POS) ? a.in_vals[0] : 0; vv[2 * i + 1] = 0; }
             } else {
                 const u64x2 q = *reinterpret_cast<const u64x2*>(a.in_keys + base);
                 kk[2 * i] = q.x; kk[2 * i + 1] = q.y;
-                if (HAS_VALS) {
+                if (HAS_VALS && !POS) {
                     const u64x2 w = *reinterpret_cast<const u64x2*>(a.in_vals + base);
                     vv[2 * i] = w.x; vv[2 * i + 1] = w.y;
                 }
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(NT, 4) void fj_partition_kernel(FjPartArgs a) {
 #pragma unroll
             for (int i = 0; i < KPT / 2; ++i) {
                 const u64 base = (u64)(t0 + tt) * T + ((u32)i * NT + tid) * 2;
-                if (base + 1 == a.n_flat) { kk[2 * i] = a.in_keys[base]; if (HAS_VALS) vv[2 * i] = a.in_vals[base]; }
+                if (base + 1 == a.n_flat) { kk[2 * i] = a.in_keys[base]; if (HAS_VALS) vv[2 * i] = POS ? base : a.in_vals[base]; }
             }
         }
     };
@@ -961,11 +965,11 @@ __global__ __launch_bounds__(1024) void fj_dir_rank_kernel(u32* __restrict__ dir
     if (blockIdx.x == 0 && tid == 0) *nalloc = n;
 }
 
-template <int NT, int KPT, int LINE_LOG, bool HAS_VALS, bool FLAT, bool PROBE_SIDE, int RLOG = FJ_RUN_LOG, bool PK7 = false>
+template <int NT, int KPT, int LINE_LOG, bool HAS_VALS, bool FLAT, bool PROBE_SIDE, int RLOG = FJ_RUN_LOG, bool PK7 = false, bool POS = false>
 hipError_t launch_part0(const FjPartArgs& a, u32 grid, hipStream_t s) {
     const u32 F = 1u << a.fan_log;
     const PartLds L = part_lds_layout(NT * KPT, F, 1u << LINE_LOG, HAS_VALS, NT / 64);
-    auto kern = fj_partition_kernel<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, RLOG, PK7>;
+    auto kern = fj_partition_kernel<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, RLOG, PK7, POS>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), L.total);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), L.total, s, a);
@@ -975,6 +979,13 @@ hipError_t launch_part0(const FjPartArgs& a, u32 grid, hipStream_t s) {
 // run length of the output's chunk ids (a.run_log): single ids exist for flat inputs only
 template <int NT, int KPT, int LINE_LOG, bool HAS_VALS, bool FLAT, bool PROBE_SIDE>
 hipError_t launch_part1(const FjPartArgs& a, u32 grid, hipStream_t s) {
+    if constexpr (FLAT && HAS_VALS) {
+        if (a.vals_pos) {                                     // row-id joins: the values are the rows' positions
+            if (a.run_log == 0) return launch_part0<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, 0, false, true>(a, grid, s);
+            if (a.run_log != FJ_RUN_LOG) return hipErrorInvalidValue;
+            return launch_part0<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, FJ_RUN_LOG, false, true>(a, grid, s);
+        }
+    }
     if constexpr (FLAT) { if (a.run_log == 0) return launch_part0<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, 0>(a, grid, s); }
     if (a.run_log != FJ_RUN_LOG) return hipErrorInvalidValue;
     return launch_part0<NT, KPT, LINE_LOG, HAS_VALS, FLAT, PROBE_SIDE, FJ_RUN_LOG>(a, grid, s);

@@ -196,6 +196,7 @@ int pass_launch(fj_ctx* c, PassIter& it, const u64* keys, const u64* vals, size_
         a.in_tiles = it.tiles; a.in_ntiles = it.ntiles; a.n_flat = 0;
     } else {
         a.in_keys = keys; a.in_vals = vals; a.in_list = nullptr; a.in_dir = nullptr; a.in_tiles = nullptr; a.in_ntiles = nullptr; a.n_flat = n;
+        a.vals_pos = it.has_vals && it.vals_pos ? 1u : 0u;
         G = std::min(G, pass_groups((n + FJ_CHUNK - 1) / FJ_CHUNK, n, it.tile_chunks, it.F));
     }
     a.parent0 = 0;

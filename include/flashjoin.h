@@ -52,6 +52,21 @@ extern "C" {
  * either with FJ_ALGO_MANY_TO_MANY, LEFT with materialize = 0, an output capacity below np, NULL or misaligned output buffers. */
 #define FJ_ALGO_LEFT_OUTER 0x20
 #define FJ_ALGO_ANTI 0x40
+/* EXTENSION (no reference counterpart; the reference returns (probe_key, build_value) pairs, hash_join.cpp:365-380): OR this into
+ * `algo` (also together with one of the flags above) and the output rows hold ROW POSITIONS - gather maps - instead of keys and
+ * values: d_out_keys[i] = 0-based position of the probe row in d_probe_keys, d_out_vals[i] = 0-based position of the build row in
+ * d_build_keys.  Order within each range unspecified, as everywhere.
+ *   base (ADAPTIVE / SCALAR / RADIX) - one row per matched probe row; the build position is the key's FIRST occurrence (smallest
+ *                                      index) on every path (partitioned plan, skew re-partition, HBM-table fallback, scalar_hbm_table)
+ *   | FJ_ALGO_MANY_TO_MANY           - one row per (probe row, build row) with equal keys; the same 4096-rows limit
+ *   | FJ_ALGO_LEFT_OUTER             - np rows: [0, m) matched, [m, np) unmatched with build position UINT64_MAX; *out_count = m
+ *   | FJ_ALGO_ANTI                   - the u = *out_count unmatched probe positions; d_out_vals may be NULL and is never written
+ * materialize = 1 only; d_build_vals may be NULL and is never read; bloom is ignored.  The two-phase form (count with d_out_keys ==
+ * NULL, then fj_emit_pairs) works for the base and many-to-many forms: the pending result remembers that it holds row ids.
+ * fj_join_host: *out_keys / *out_vals are the position arrays (*out_vals = NULL with ANTI).  Refused up front, before any device
+ * work: materialize = 0, and with LEFT_OUTER or ANTI everything those flags refuse (FJ_ALGO_MANY_TO_MANY among it).  The multi-GPU
+ * and stream joins take no algo word: they have no row-id form. */
+#define FJ_ALGO_ROW_IDS 0x80
 
 typedef struct fj_ctx fj_ctx;
 
@@ -91,7 +106,7 @@ const char* fj_version(void);
  * binding checks it once after loading the library (flash_hash_join_amd/_lib.py does).  Structs the library fills or reads on a
  * caller's behalf (fj_dist_timings, fj_dist_engine_ops) start with a struct_size word the caller sets to sizeof(its struct): the
  * library touches no byte beyond it. */
-#define FJ_ABI_VERSION 7
+#define FJ_ABI_VERSION 8
 int fj_abi_version(void);
 
 /* Process-wide dispatch options (no reference counterpart; the reference hard-codes 1'000'000 at hash_join.cpp:576).  Initial values:
