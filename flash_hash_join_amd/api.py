@@ -36,6 +36,7 @@ ALGO_MANY_TO_MANY = 0x10          # FJ_ALGO_MANY_TO_MANY: OR'ed into algo (exten
 ALGO_LEFT_OUTER = 0x20            # FJ_ALGO_LEFT_OUTER: left outer join, np rows (extension)
 ALGO_ANTI = 0x40                  # FJ_ALGO_ANTI: the probe rows without a partner (extension)
 ALGO_ROW_IDS = 0x80               # FJ_ALGO_ROW_IDS: output rows hold row positions (gather maps) instead of keys and values (extension)
+ALGO_FULL_OUTER = 0x100           # FJ_ALGO_FULL_OUTER: full outer join, np + r rows; the count is the pair (m, r) (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -114,17 +115,30 @@ def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_array
     bv = _as_u64_host(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
     if bv is not None and bv.size < bk.size:
         raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
-    cnt = ctypes.c_uint64(0)
+    cnt = (ctypes.c_uint64 * 2)(0, 0)                   # (a full outer join fills both words: matched probe rows, unmatched build rows)
     sec = ctypes.c_double(0.0)
     ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
     want = bool(materialize and return_arrays)
     check(L.fj_join_host(algo, bloom, materialize, bk.ctypes.data, bv.ctypes.data if bv is not None else None, bk.size, pk.ctypes.data, pk.size,
-                         ctypes.byref(cnt), ctypes.byref(sec),
+                         cnt, ctypes.byref(sec),
                          ctypes.byref(ok) if want else None, ctypes.byref(ov) if want else None))
     t = FjTimings()
     L.fj_last_timings(ctypes.byref(t))
     _last = t
-    n = int(cnt.value)
+    n = int(cnt[0])
+    if algo & ALGO_FULL_OUTER:          # np + r rows; the count is the pair (m, r)
+        r = int(cnt[1])
+        if not want:
+            return (n, r), float(sec.value)
+        rows = pk.size + r
+        try:
+            arr = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
+                             else np.empty(0, np.uint64))
+            keys, vals = arr(ok), arr(ov)
+        finally:
+            L.fj_free_host(ok)
+            L.fj_free_host(ov)
+        return (n, r), float(sec.value), keys, vals
     if not want:
         return n, float(sec.value)
     if algo & _OUTER:                   # left outer: np rows; anti: n keys and no values
@@ -191,6 +205,25 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     cnt = ctypes.c_uint64(0)
     t = FjTimings()
     bv_ptr = bv.data_ptr() if bv is not None else None
+    if algo & ALGO_FULL_OUTER:
+        # full outer join: room for every row of both sides, one call, never a pending result; the count is the pair (m, r)
+        n_p, n_b = pk.numel(), bk.numel()
+        ok = torch.empty(n_p + n_b, dtype=torch.int64, device=bk.device)
+        ov = torch.empty(n_p + n_b, dtype=torch.int64, device=bk.device)
+        cnt2 = (ctypes.c_uint64 * 2)(0, 0)
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, n_b, pk.data_ptr(), n_p, stream,
+                                   hash_top_bits, cnt2, ok.data_ptr(), ov.data_ptr(), n_p + n_b, ctypes.byref(t)))
+        m, r = int(cnt2[0]), int(cnt2[1])
+        _last = t
+        if not return_arrays:
+            return (m, r), t.total_ms * 1e-3
+        rows = n_p + r                      # exact size: copies unless the rows fill most of the buffers (the rule of the inner join below)
+        if rows * 4 < (n_p + n_b) * 3:
+            ok, ov = ok[:rows].clone(), ov[:rows].clone()
+        else:
+            ok, ov = ok[:rows], ov[:rows]
+        return (m, r), t.total_ms * 1e-3, ok, ov
     if (algo & _OUTER) and materialize:
         # left outer / anti join: np-row buffers always (a left join HAS np rows), one call, never a pending result to emit
         left = bool(algo & ALGO_LEFT_OUTER)
@@ -380,8 +413,41 @@ def anti_join_count(build_keys, probe_keys):
     return _join(ALGO_ADAPTIVE | ALGO_ANTI, 0, 0, build_keys, None, probe_keys, False)
 
 
+# ---- extension: full outer join, fused into one call and one set of partition passes (csrc/fj_outer.hip) ---------------------------
+def full_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0):
+    """Full outer join (N:1).  Returns (m, r, seconds) or (m, r, seconds, keys, values) with len(probe_keys) + r rows:
+    rows [0, m) the matched (probe_key, build_value) pairs (a duplicated build key: its FIRST occurrence's value), rows
+    [m, len(probe_keys)) the unmatched probe keys with value `fill_value` - together what left_join returns - and behind them the r
+    build rows (build_key, build_value) whose key is not among the probe keys, every copy of a duplicated key included.  Order
+    within each range unspecified."""
+    res = _join(ALGO_ADAPTIVE | ALGO_FULL_OUTER, 0, 1, build_keys, build_values, probe_keys, return_arrays)
+    (m, r), sec = res[0], res[1]
+    if not return_arrays:
+        return m, r, sec
+    keys, vals = res[2], res[3]
+    n_p = keys.shape[0] - r
+    if fill_value != 0 and n_p > m:
+        vals[m:n_p] = (int(np.array(fill_value, dtype=np.uint64).view(np.int64)) if _is_torch_tensor(vals) else np.uint64(fill_value))
+    return m, r, sec, keys, vals
+
+
+# ---- extension: semi join (the N:1 inner join minus its value column; no new kernel) -------------------------------------------------
+def semi_join(build_keys, probe_keys, return_arrays: bool = False):
+    """Semi join (EXISTS / IN): the probe rows whose key is among the build keys, each once.  Returns (s, seconds) or
+    (s, seconds, keys) with the s matched probe keys, in unspecified order.  No value column is asked of the caller: the build
+    keys stand in for it and the join's value output is dropped."""
+    if not return_arrays:
+        return semi_join_count(build_keys, probe_keys)
+    return _join(ALGO_ADAPTIVE, 0, 1, build_keys, build_keys, probe_keys, True)[:3]
+
+
+def semi_join_count(build_keys, probe_keys):
+    """Number of probe rows whose key is among the build keys: (s, seconds) - the N:1 count (a counting join reads no value)."""
+    return _join(ALGO_ADAPTIVE, 0, 0, build_keys, build_keys, probe_keys, False)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
-_HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI}
+_HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
 
 def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool = False):
@@ -393,6 +459,9 @@ def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool 
     how="left"   (m, seconds, probe_idx, build_idx): every probe row once, rows [0, m) matched, rows [m, len(probe_keys))
                  unmatched with build_idx == -1; m = matched rows, as left_join returns.
     how="anti"   (u, seconds, probe_idx, None): the u probe rows whose key is not among the build keys.
+    how="semi"   (s, seconds, probe_idx, None): the s probe rows whose key IS among the build keys, each once.
+    how="full"   (m, r, seconds, probe_idx, build_idx): len(probe_keys) + r rows - the rows of how="left", then the r build rows
+                 whose key is not among the probe keys with probe_idx == -1 (every copy of a duplicated key).
     The index arrays are int64: NumPy for host inputs, torch.int64 on the inputs' device for device tensors / DLPack."""
     if how not in _HOW:
         raise ValueError(f"join_indices: how must be one of {sorted(_HOW)}, got {how!r}")
@@ -401,6 +470,10 @@ def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool 
     algo = (ALGO_RADIX | ALGO_MANY_TO_MANY if many_to_many else ALGO_ADAPTIVE | _HOW[how]) | ALGO_ROW_IDS
     n, sec, pi, bi = _join(algo, 0, 1, build_keys, None, probe_keys, True)
     as_i64 = lambda a: a if a is None or _is_torch_tensor(a) else np.asarray(a).view(np.int64)
+    if how == "full":
+        return n[0], n[1], sec, as_i64(pi), as_i64(bi)
+    if how == "semi":
+        return n, sec, as_i64(pi), None
     return n, sec, as_i64(pi), as_i64(bi)
 
 
@@ -445,5 +518,6 @@ REFERENCE_EXPORTS = [
     "initialize",
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
-EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices"]
+EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
+              "full_join", "semi_join", "semi_join_count"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

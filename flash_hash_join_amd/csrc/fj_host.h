@@ -86,6 +86,7 @@ enum Slot {
     W_PK_FI, W_PK_BKEYS, W_PK_OBASE,                                   // fj_shuffle_pack_*: output-chunk index, keys per bucket, output chunks before a bucket
     W_RX_REL, W_RX_LIST, W_RX_SEGOFF, W_RX_BCH, W_RX_BOFF, W_RX_TOFF, W_RX_TILES,   // a received piece as a chunk set
     W_SK_TILES_B, W_SK_TILES_P, W_SK_NT, W_PART_COUNT2, W_OUT_OFF2,                 // re-partitioning of oversized final partitions (skew_join)
+    W_FULL_BITS,                                                                    // full outer join: matched bits of the build rows / of the global table's slots
     W_NSLOTS
 };
 
@@ -282,6 +283,10 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
 // rid: the row-id form (FJ_ALGO_ROW_IDS): probe positions in d_ok, first-occurrence build positions (~0: none) in d_ov
 int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
                hipStream_t s, fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid = false);
+// FJ_ALGO_FULL_OUTER: rows [0, np) as FJ_OJ_LEFT writes them, then the build rows without a probe partner; outputs hold >= np + nb
+// rows; out_counts[0] = matched probe rows, out_counts[1] = unmatched build rows
+int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
+              hipStream_t s, fj_timings* t, u64* out_counts, u64* d_ok, u64* d_ov, bool rid);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

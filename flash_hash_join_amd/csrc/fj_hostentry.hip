@@ -177,11 +177,19 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool many_host = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
     if (left && !materialize) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER needs materialize = 1 (its match count is the counting join's)");
+    if (full) {
+        if (left || anti) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_%s", left ? "LEFT_OUTER" : "ANTI");
+        if (many_host) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_MANY_TO_MANY");
+        if (!materialize) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER needs materialize = 1 (its match count is the counting join's)");
+        if (nb && !bv && !rid) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER needs build values (only FJ_ALGO_ROW_IDS reads none)");
+        if (!out_count) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER needs out_count (two words: matched probe rows, unmatched build rows)");
+    }
     const bool outer_mat = (left || anti) && materialize;      // left outer / anti join writing rows: np-row device buffers, no emit step
     {
         static std::mutex create_mu;
@@ -216,7 +224,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // A counting join of the partitioned plan starts on the first piece: the build side is copied and partitioned, then every
     // probe piece gets its first partition pass while the next one crosses PCIe (the join hides under the copy; the bloom
     // precheck is skipped here - it saves device time the copy does not leave on the critical path).
-    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti;
+    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti && !full;
     hipStream_t js = nullptr;
     auto t0 = std::chrono::steady_clock::now();
     unsigned cursor = 0;
@@ -246,6 +254,27 @@ int fj_join_host(int algo, int bloom, int materialize,
     }
     const double h2d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     double d2h = 0;
+    u64 full_r = 0;
+    if (full) {                                                                // full outer join: (np + nb)-row device buffers, np + r rows back
+        void *dok, *dov;
+        const size_t cap = np + nb;
+        if (get_buf(c, W_H_OK, std::max<size_t>(cap, 1) * 8, &dok) || get_buf(c, W_H_OV, std::max<size_t>(cap, 1) * 8, &dov)) return 1;
+        u64 counts[2] = {0, 0};
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
+                           counts, (u64*)dok, (u64*)dov, cap, &t)) return 1;
+        count = counts[0]; full_r = counts[1];
+        const size_t rows = np + (size_t)full_r;
+        if (out_keys && out_vals) {
+            u64* hk = (u64*)malloc(std::max<size_t>(rows, 1) * 8);
+            u64* hv = (u64*)malloc(std::max<size_t>(rows, 1) * 8);
+            if (!hk || !hv) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", rows); }
+            auto t1 = std::chrono::steady_clock::now();
+            if (rows) { HIPCHK(hipMemcpy(hk, dok, rows * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hv, dov, rows * 8, hipMemcpyDeviceToHost)); }
+            d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+            *out_keys = hk; *out_vals = hv;
+        }
+        joined = true;
+    }
     if (outer_mat) {
         void *dok, *dov = nullptr;
         if (get_buf(c, W_H_OK, std::max<size_t>(np, 1) * 8, &dok) || (left && get_buf(c, W_H_OV, std::max<size_t>(np, 1) * 8, &dov))) return 1;
@@ -285,9 +314,10 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined && !outer_mat ? 1 : 0;
+    t.host_streamed = joined && !outer_mat && !full ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
+    if (full) out_count[1] = full_r;
     if (out_seconds) *out_seconds = t.total_ms * 1e-3;
     return 0;
 }

@@ -229,6 +229,8 @@ struct FjGtArgs {                // global (non-partitioned) table
     u64* out_keys; u64* out_vals;
     u32 row_ids;                            // row-id join: tvals hold first-occurrence row indices (fj_gt_build_first_kernel); the writer
                                             // puts the probe row's index in out_keys and the table's in out_vals
+    u32* matched;                           // full outer join: one bit per table slot, set by the outer probe on a hit (zeroed before it;
+                                            // capacity / 32 words + one more: a probe row hit the empty marker key); nullptr otherwise
 };
 hipError_t fj_launch_gt_build(const FjGtArgs& a, hipStream_t s);
 hipError_t fj_launch_gt_probe(const FjGtArgs& a, bool materialize, u32 grid, hipStream_t s);
@@ -278,3 +280,15 @@ hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsign
 // global table: build with row indices (first occurrence; vals = false: keys only), then the outer probe (a.total = hit cursor)
 hipError_t fj_launch_gt_build_first(const FjGtArgs& a, bool vals, hipStream_t s);
 hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long long* miss_cursor, u64 out_capacity, hipStream_t s);
+
+// ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
+// bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat
+// arrays: the row index), zeroed before the launch.  Every work item ORs in the rows whose key one of its probe rows hit (mode
+// FJ_OJ_LEFT or FJ_OJ_LEFT_FIRST; otherwise fj_launch_outer_join).
+hipError_t fj_launch_outer_join_full(const FjLdsJoinArgs& a, int mode, u64 np, unsigned long long* miss_cursor, u64* bits, hipStream_t s);
+// the rows with a zero bit, compacted into out rows [base, base + *cursor): (key, value), or (~0, build position) in the row-id
+// form; orig_vals != nullptr: the vals plane holds row indices into it.  Rows at or beyond out_capacity are not written (FJ_ERR_OUTCAP).
+hipError_t fj_launch_full_sweep(const FjChunkSet& build, const u64* bits, const u64* orig_vals, u32 row_ids, u64* out_keys, u64* out_vals,
+                                u64 base, u64 out_capacity, unsigned long long* cursor, u32* err, hipStream_t s);
+// global table: the build rows whose slot's bit in a.matched is zero (a.bk / a.bv / a.row_ids as for the probe)
+hipError_t fj_launch_gt_full_sweep(const FjGtArgs& a, u64 base, u64 out_capacity, unsigned long long* cursor, u32* err, hipStream_t s);

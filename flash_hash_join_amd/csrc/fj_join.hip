@@ -1587,9 +1587,11 @@ __global__ __launch_bounds__(256) void fj_gt_build_first_kernel(FjGtArgs a) {
 // probe: rounds of 4096 rows per workgroup (4 per thread), hits from the front (a.total), misses from the back (miss_cursor);
 // LEFT: the value is gathered from the caller's build_values by the slot's row index
 // RID: the row-id form - probe row indices in out_keys, the winning build row index (LEFT; all ones for a miss) in out_vals
-template <int MODE, bool RID = false>
+// FULL: the full outer join (MODE LEFT) - every hit also sets its slot's bit in a.matched (fj_gt_full_sweep_kernel reads them)
+template <int MODE, bool RID = false, bool FULL = false>
 __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, unsigned long long* miss_cursor, u64 out_capacity) {
     constexpr bool VALS = MODE != FJ_OJ_ANTI;
+    static_assert(!FULL || VALS, "full outer join: a left join's table");
     constexpr u32 NT = 1024, KPT = 4;
     __shared__ FjOjCursor cur;
     const u32 tid = threadIdx.x, lane = tid & 63;
@@ -1616,6 +1618,10 @@ __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, uns
             else h = gt_lookup(a.tkeys, a.cap_mask, k[u], fj_hash64(k[u]), where[u]);
             if (h && VALS) hit |= 1u << u;
             if (!h) miss |= 1u << u;
+            if (FULL && h) {
+                if (k[u] == FJ_EMPTY_KEY) a.matched[(a.cap_mask + 1) >> 5] = 1u;
+                else if (!((a.matched[where[u] >> 5] >> (where[u] & 31)) & 1u)) atomicOr(&a.matched[where[u] >> 5], 1u << (where[u] & 31));
+            }
         }
         u64 hb[KPT], mb[KPT];
         u32 nh = 0, nm = 0;
@@ -1640,6 +1646,44 @@ __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, uns
                 if (m < np && o < out_capacity) { a.out_keys[o] = RID ? base + u * NT + tid : k[u]; if (VALS) a.out_vals[o] = RID ? ~0ull : 0ull; }
             }
             hpos += (u32)__popcll(hb[u]); mpos += (u32)__popcll(mb[u]);
+        }
+    }
+}
+
+// full outer join, last step on the global table: every build row looks its key up again; the rows of slots no probe row hit are
+// appended behind row `base` ((key, value), or (~0, row index) in the row-id form).  Reservation as in fj_full_sweep_kernel.
+__global__ __launch_bounds__(1024) void fj_gt_full_sweep_kernel(FjGtArgs a, u64 base, u64 out_capacity, unsigned long long* cursor, u32* err) {
+    __shared__ u32 s_cnt;
+    __shared__ u64 s_base;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    const bool empty_hit = a.matched[(a.cap_mask + 1) >> 5] != 0;
+    for (u64 i0 = (u64)blockIdx.x * 1024; i0 < a.nb; i0 += (u64)gridDim.x * 1024) {     // (uniform per workgroup)
+        const u64 i = i0 + tid;
+        bool un = false;
+        u64 key = 0;
+        if (i < a.nb) {
+            key = a.bk[i];
+            if (key == FJ_EMPTY_KEY) un = !empty_hit;
+            else {
+                u64 where = 0;
+                const bool found = gt_lookup(a.tkeys, a.cap_mask, key, fj_hash64(key), where);
+                un = !found || !((a.matched[where >> 5] >> (where & 31)) & 1u);
+            }
+        }
+        const u64 bal = __ballot(un);
+        const u32 n = (u32)__popcll(bal);
+        u32 w = 0;
+        if (lane == 0 && n) w = atomicAdd(&s_cnt, n);
+        w = __shfl(w, 0, 64);
+        __syncthreads();
+        if (tid == 0) { s_base = s_cnt ? (u64)atomicAdd(cursor, (unsigned long long)s_cnt) : 0ull; s_cnt = 0; }
+        __syncthreads();
+        if (un) {
+            const u64 o = base + s_base + w + (u32)__popcll(bal & ((1ull << lane) - 1ull));
+            if (o < out_capacity) { a.out_keys[o] = a.row_ids ? ~0ull : key; a.out_vals[o] = a.row_ids ? i : a.bv[i]; }
+            else atomicOr(err, FJ_ERR_OUTCAP);
         }
     }
 }
@@ -1920,6 +1964,12 @@ hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long l
     if (!a.out_keys || !miss_cursor || (mode != FJ_OJ_ANTI && (!a.out_vals || !a.tvals || (!a.bv && !a.row_ids)))) return hipErrorInvalidValue;
     const u64 rounds = (a.np + 4095) / 4096;
     const u32 grid = (u32)(rounds < 2048 ? rounds : 2048);
+    if (a.matched) {                                     // full outer join
+        if (mode != FJ_OJ_LEFT) return hipErrorInvalidValue;
+        if (a.row_ids) hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_LEFT, true, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+        else hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_LEFT, false, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+        return hipGetLastError();
+    }
     if (a.row_ids) {
         if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_ANTI, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
         else hipLaunchKernelGGL((fj_gt_outer_probe_kernel<FJ_OJ_LEFT, true>), dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
@@ -1927,6 +1977,15 @@ hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long l
     }
     if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_ANTI>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
     else hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_LEFT>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_full_sweep(const FjGtArgs& a, u64 base, u64 out_capacity, unsigned long long* cursor, u32* err, hipStream_t s) {
+    if (a.nb == 0) return hipSuccess;
+    if (!a.matched || !a.out_keys || !a.out_vals || !cursor || !err || (!a.bv && !a.row_ids)) return hipErrorInvalidValue;
+    const u64 rounds = (a.nb + 1023) / 1024;
+    const u32 grid = (u32)(rounds < 2048 ? rounds : 2048);
+    hipLaunchKernelGGL(fj_gt_full_sweep_kernel, dim3(grid), dim3(1024), 0, s, a, base, out_capacity, cursor, err);
     return hipGetLastError();
 }
 

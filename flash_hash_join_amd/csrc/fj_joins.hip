@@ -524,6 +524,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool many = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
+    const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     if (rid) {
         // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
@@ -531,6 +532,18 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (!materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
         if (!d_bv) d_bv = d_bk;                             // never read: the build rows' positions are made on the device
         bloom = 0;                                          // (the filter kernel moves no payload)
+    }
+    if (full) {
+        // full outer join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
+        algo &= ~FJ_ALGO_FULL_OUTER;
+        if (left || anti) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_%s", left ? "LEFT_OUTER" : "ANTI");
+        if (many) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_MANY_TO_MANY");
+        if (!materialize) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs materialize = 1 (its match count is the counting join's)");
+        if ((np || nb) && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs output buffers (d_out_keys and d_out_vals)");
+        if (out_capacity < np || out_capacity - np < nb) return set_err("fj_join_device: output capacity %zu < %zu probe rows + %zu build rows (FJ_ALGO_FULL_OUTER may write every row of both sides)", out_capacity, np, nb);
+        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
+        if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs d_build_vals (only FJ_ALGO_ROW_IDS reads no build value)");
+        if (!out_count) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs out_count (two words: matched probe rows, unmatched build rows)");
     }
     if (left || anti) {
         // left outer / anti join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
@@ -558,6 +571,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const Options& opt = options();
     bool use_radix = algo == FJ_ALGO_RADIX || (algo == FJ_ALGO_ADAPTIVE && nb >= opt.radix_threshold) ||
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
+    if (full) {                                             // the left join and the unmatched build rows in one plan, never a pending result
+        u64 counts[2] = {0, 0};
+        if (join_full(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, counts, (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
+        out_count[0] = counts[0]; out_count[1] = counts[1];
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
     if ((left || anti) && materialize) {                    // one pass over the probe side, never a pending result
         if (join_outer(c, left ? FJ_OJ_LEFT : FJ_OJ_ANTI, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count,
                        (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;

@@ -1,5 +1,5 @@
-// fj_outer.hip -- left outer and anti joins on the partitioned plan (an EXTENSION: FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI,
-// include/flashjoin.h).
+// fj_outer.hip -- left outer, anti and full outer joins on the partitioned plan (an EXTENSION: FJ_ALGO_LEFT_OUTER / FJ_ALGO_ANTI /
+// FJ_ALGO_FULL_OUTER, include/flashjoin.h).
 //
 // The N:1 join of the reference (first occurrence of a duplicate build key wins, hash_join.cpp:125) answers "which probe rows have
 // a partner, and with which value".  A left outer join also returns the rows WITHOUT one, an anti join only those.  With N:1
@@ -21,11 +21,15 @@
 //                          of the radix path and of the NumPy reference in the tests);
 //   FJ_ERR_LDS_FULL        a partition holds more distinct keys than the table takes (15/16 of its slots): the whole join runs
 //                          again on the global HBM table (fj_gt_outer_probe_kernel, csrc/fj_join.hip), timings.fell_back = 1.
+//
+// Full outer join (FJ_ALGO_FULL_OUTER): the left join's launch in its FULL form also marks, in a bitmap in HBM, the build rows its
+// probe rows matched; fj_full_sweep_kernel then appends the unmarked build rows behind row np (join_full below).
 #include "fj_host.h"
 
 namespace {
 
 constexpr u32 OJ_NT = 1024, OJ_KPT = 8, OJ_ROUND_CHUNKS = OJ_NT * OJ_KPT / FJ_CHUNK;
+constexpr u32 OJ_MBITS_WORDS = 8192 / 32 + 4;                 // full outer join: hit bits of the 8192 slots + the empty marker's word (16-byte multiple)
 struct OjHdr { u32 full, dups, empty_cnt, nkeys; FjOjCursor cur; u64 empty_val; };
 
 __device__ __forceinline__ u32 oj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
@@ -37,15 +41,23 @@ __device__ __forceinline__ u32 oj_entry(const FjChunkSet& cs, u32 idx) {       /
 
 // RID: the row-id form (FjLdsJoinArgs::row_ids; MODE LEFT_FIRST or ANTI) - build values are row positions and the smallest is
 // written as it is; every output row gets the probe row's position (its vals plane; flat arrays: the index), a miss the value ~0
-template <int MODE, bool RID = false>
-__global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a, u64 np, unsigned long long* miss_cursor) {
+// FULL: the full outer join (FJ_ALGO_FULL_OUTER; MODE LEFT or LEFT_FIRST) - rows [0, np) as above, and the item remembers which of its
+// table's slots were hit: one bit per slot in LDS (mbits, behind the values; one more word for the empty marker key), set by the probe
+// rounds.  After its last round the item walks its partition's build chunks once more, looks every row's key up and ORs the rows of hit
+// slots into `bits` (one bit per build row at chunk id * FJ_CHUNK + offset - the same place for every item of the partition, whatever
+// slot the key took in this item's table; a wave covers 64 consecutive rows of one chunk: one 64-bit atomic per non-zero ballot).
+// Marking per ROW is what makes every copy of a matched duplicate key count as matched.  fj_full_sweep_kernel reads the zero bits.
+template <int MODE, bool RID = false, bool FULL = false>
+__global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a, u64 np, unsigned long long* miss_cursor, u64* bits) {
     constexpr bool VALS = MODE != FJ_OJ_ANTI, FIRST = MODE == FJ_OJ_LEFT_FIRST;
     static_assert(!RID || MODE != FJ_OJ_LEFT, "row ids: the first occurrence wins");
+    static_assert(!FULL || VALS, "full outer join: a left join's table");
     constexpr u32 TS = VALS ? 8192u : 16384u, LIMIT = TS - TS / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     OjHdr* hdr = reinterpret_cast<OjHdr*>(smem);
     u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(OjHdr));
     u64* tvals = tkeys + TS;                                  // (VALS only)
+    u32* mbits = reinterpret_cast<u32*>(tvals + TS);          // (FULL only) [TS / 32] hit slots, [TS / 32] != 0: the empty marker key was hit
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
     u32 p, b0 = 0, nbc, s_lo, s_hi;
@@ -64,6 +76,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
     else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
 
     for (u32 i = tid; i < TS; i += OJ_NT) { tkeys[i] = FJ_EMPTY_KEY; if (FIRST) tvals[i] = ~0ull; }
+    if (FULL) for (u32 i = tid; i < OJ_MBITS_WORDS; i += OJ_NT) mbits[i] = 0;
     if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->cur.hit = 0; hdr->cur.miss = 0; hdr->empty_val = FIRST ? ~0ull : 0ull; }
     __syncthreads();
 
@@ -144,12 +157,18 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
             if (!((okm >> u) & 1u)) continue;
             if (!a.probe.list) k[u] = fj_key_mix(k[u]);
             bool h = false;
-            if (k[u] == FJ_EMPTY_KEY) { h = has_empty; v[u] = empty_val; }
+            if (k[u] == FJ_EMPTY_KEY) { h = has_empty; v[u] = empty_val; if (FULL && h) mbits[TS / 32] = 1; }
             else {
                 u32 pos = FJ_HW2(k[u]) & (TS - 1);
                 for (;;) {                                   // the build left >= 1/16 of the slots empty: always terminates
                     const u64 t = tkeys[pos];
-                    if (t == k[u]) { h = true; if (VALS) v[u] = tvals[pos]; break; }
+                    if (t == k[u]) {
+                        h = true;
+                        if (VALS) v[u] = tvals[pos];
+                        // (read first: most hits find their slot's bit set already and skip the LDS atomic)
+                        if (FULL && !((mbits[pos >> 5] >> (pos & 31)) & 1u)) atomicOr(&mbits[pos >> 5], 1u << (pos & 31));
+                        break;
+                    }
                     if (t == FJ_EMPTY_KEY) break;
                     pos = (pos + 1) & (TS - 1);
                 }
@@ -191,6 +210,76 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
         for (u32 u = 0; u < OJ_KPT; ++u) { k[u] = kn[u]; if (RID) rp[RID ? u : 0] = rpn[RID ? u : 0]; }
         okm = okn;
     }
+    if (FULL) {
+        // ---- the build rows this item's probe rows found: uniform control flow up to the ballot (c is wave-uniform) ----
+        static_assert(FJ_CHUNK % 64 == 0, "a wave covers 64 consecutive rows of one chunk");
+        __syncthreads();
+        const bool empty_hit = mbits[TS / 32] != 0;
+        for (u32 c0 = 0; c0 < nbc; c0 += OJ_NT / FJ_CHUNK) {
+            const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            bool mt = false;
+            u64 src = 0;
+            if (c < nbc) {
+                const u32 e = oj_entry(a.build, b0 + c);
+                src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+                if (off < FJ_LIST_CNT(e)) {
+                    const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);
+                    if (key == FJ_EMPTY_KEY) mt = empty_hit;
+                    else {
+                        u32 pos = FJ_HW2(key) & (TS - 1);
+                        for (;;) {                           // (the key is in the table: the build put it there)
+                            const u64 t = tkeys[pos];
+                            if (t == key) { mt = (mbits[pos >> 5] >> (pos & 31)) & 1u; break; }
+                            if (t == FJ_EMPTY_KEY) break;
+                            pos = (pos + 1) & (TS - 1);
+                        }
+                    }
+                }
+            }
+            const u64 bal = __ballot(mt);
+            if (lane == 0 && bal) atomicOr((unsigned long long*)&bits[src >> 6], (unsigned long long)bal);
+        }
+    }
+}
+
+// full outer join, last step: the build rows whose bit is still zero -> out rows [base, base + *cursor).  Rounds of four chunks per
+// workgroup; a round's rows are reserved wave by wave in LDS (ballot + popcount) and with one global atomic per workgroup.
+__global__ __launch_bounds__(OJ_NT) void fj_full_sweep_kernel(FjChunkSet b, const u64* __restrict__ bits, const u64* __restrict__ orig_vals, u32 row_ids,
+                                                              u64* __restrict__ out_keys, u64* __restrict__ out_vals, u64 base, u64 out_capacity,
+                                                              unsigned long long* cursor, u32* err) {
+    __shared__ u32 s_cnt;
+    __shared__ u64 s_base;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 nch = b.list ? b.boff[b.nb] : (u32)((b.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    for (u32 c0 = blockIdx.x * (OJ_NT / FJ_CHUNK); c0 < nch; c0 += gridDim.x * (OJ_NT / FJ_CHUNK)) {     // (uniform per workgroup)
+        const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        bool un = false;
+        u64 src = 0;
+        if (c < nch) {
+            const u32 e = oj_entry(b, c);
+            src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            if (off < FJ_LIST_CNT(e)) un = !((bits[src >> 6] >> (src & 63)) & 1ull);
+        }
+        const u64 bal = __ballot(un);
+        const u32 n = (u32)__popcll(bal);
+        u32 w = 0;
+        if (lane == 0 && n) w = atomicAdd(&s_cnt, n);
+        w = __shfl(w, 0, 64);
+        __syncthreads();
+        if (tid == 0) { s_base = s_cnt ? (u64)atomicAdd(cursor, (unsigned long long)s_cnt) : 0ull; s_cnt = 0; }
+        __syncthreads();
+        if (un) {
+            const u64 o = base + s_base + w + (u32)__popcll(bal & ((1ull << lane) - 1ull));
+            if (o < out_capacity) {
+                u64 v = b.vals ? b.vals[src] : src;              // (no vals plane: flat arrays of a row-id join, the index is the position)
+                if (orig_vals) v = orig_vals[v];
+                out_keys[o] = row_ids ? ~0ull : (b.list ? fj_key_unmix(b.keys[src]) : b.keys[src]);   // chunk pools hold mixed keys
+                out_vals[o] = v;
+            } else atomicOr(err, FJ_ERR_OUTCAP);
+        }
+    }
 }
 
 }  // namespace
@@ -206,7 +295,30 @@ hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsign
               : mode == FJ_OJ_LEFT_FIRST ? fj_outer_join_kernel<FJ_OJ_LEFT_FIRST> : fj_outer_join_kernel<FJ_OJ_LEFT>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
-    if (nb) hipLaunchKernelGGL(kern, dim3(nb), dim3(OJ_NT), lds, s, a, np, miss_cursor);
+    if (nb) hipLaunchKernelGGL(kern, dim3(nb), dim3(OJ_NT), lds, s, a, np, miss_cursor, (u64*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_outer_join_full(const FjLdsJoinArgs& a, int mode, u64 np, unsigned long long* miss_cursor, u64* bits, hipStream_t s) {
+    const u32 nb = a.items ? a.items_cap : a.nparts * a.nsplit;
+    if (!a.out_cursor || !miss_cursor || !a.out_keys || !a.out_vals || !bits || (mode != FJ_OJ_LEFT && mode != FJ_OJ_LEFT_FIRST)) return hipErrorInvalidValue;
+    if (mode == FJ_OJ_LEFT ? a.row_ids != 0 : (!a.orig_vals && !a.row_ids)) return hipErrorInvalidValue;
+    const u32 lds = (u32)sizeof(OjHdr) + 8192u * 16 + OJ_MBITS_WORDS * 4;
+    auto kern = a.row_ids ? fj_outer_join_kernel<FJ_OJ_LEFT_FIRST, true, true>
+              : mode == FJ_OJ_LEFT_FIRST ? fj_outer_join_kernel<FJ_OJ_LEFT_FIRST, false, true> : fj_outer_join_kernel<FJ_OJ_LEFT, false, true>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    if (nb) hipLaunchKernelGGL(kern, dim3(nb), dim3(OJ_NT), lds, s, a, np, miss_cursor, bits);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_full_sweep(const FjChunkSet& build, const u64* bits, const u64* orig_vals, u32 row_ids, u64* out_keys, u64* out_vals,
+                                u64 base, u64 out_capacity, unsigned long long* cursor, u32* err, hipStream_t s) {
+    if (!bits || !out_keys || !out_vals || !cursor || !err) return hipErrorInvalidValue;
+    const u64 bound = build.list ? build.cap : (build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG;      // chunks at most
+    if (bound == 0) return hipSuccess;
+    const u32 grid = (u32)std::min<u64>(4096, (bound + OJ_NT / FJ_CHUNK - 1) / (OJ_NT / FJ_CHUNK));
+    hipLaunchKernelGGL(fj_full_sweep_kernel, dim3(grid), dim3(OJ_NT), 0, s, build, bits, orig_vals, row_ids, out_keys, out_vals, base, out_capacity, cursor, err);
     return hipGetLastError();
 }
 
@@ -214,8 +326,10 @@ namespace fjh {
 
 // the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
 // "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  LEFT builds with row indices (the smallest wins, first occurrence)
+// full_r != nullptr (LEFT only): the full outer join - the probe marks the slots it hits, a sweep over the flat build rows looks every
+// key up again and appends the rows of unmarked slots behind row np; *full_r = their number
 static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, hipStream_t s,
-                             fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid) {
+                             fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid, u64* full_r = nullptr) {
     const bool left = mode != FJ_OJ_ANTI;
     u64 cap = 64;
     while (cap < 2 * (u64)nb) cap <<= 1;
@@ -226,8 +340,16 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
     a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
     a.bk = bk; a.bv = (left && !rid) ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
     a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr; a.row_ids = rid ? 1u : 0u;
+    if (full_r) {
+        if (get_buf(c, W_FULL_BITS, (cap / 32 + 1) * 4, &p)) return 1;
+        a.matched = (u32*)p;
+    }
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    if (full_r) {
+        HIPCHK(hipMemsetAsync(a.matched, 0, (cap / 32 + 1) * 4, s));
+        HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));      // (the sweep's row cursor)
+    }
     HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));           // (row index minimum)
     HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
     if (left) HIPCHK(hipMemsetAsync(a.tvals, 0xFF, cap * 8, s));
@@ -236,6 +358,11 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_outer_probe(a, mode, &c->d_sc->expected, np, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (full_r) {
+        HIPCHK(hipEventRecord(c->ev[E_EMIT0], s));
+        HIPCHK(fj_launch_gt_full_sweep(a, np, (u64)np + nb, &c->d_sc->sample_hits, &c->d_sc->err, s));
+        HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
+    }
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join's global-table probe wrote out of its rows");
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
@@ -246,6 +373,11 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
     t->join_ms = ev_ms(c, E_PPART, E_JOIN);
     t->probe_phase_ms = t->join_ms;
     t->total_ms = ev_ms(c, E_START, E_JOIN);
+    if (full_r) {
+        *full_r = c->h_sc->sample_hits;
+        if (*full_r > nb) return set_err("internal error: full outer join kept %llu of %zu build rows", (unsigned long long)*full_r, nb);
+        t->emit_ms = ev_ms(c, E_EMIT0, E_EMIT1); t->total_ms += t->emit_ms;
+    }
     return 0;
 }
 
@@ -333,6 +465,109 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (left ? hits + misses != np : misses > np) return set_err("internal error: outer join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
     *out_count = left ? hits : misses;
+    return 0;
+}
+
+// FJ_ALGO_FULL_OUTER (fj_join_device has checked the arguments; d_ok / d_ov hold np + nb rows).  The partitioned plan of the left join,
+// run once: its kernel also marks the build rows it matched in a bitmap (one bit per row of the build side's final chunk pool, zeroed
+// per launch), and a sweep over the build side's final chunk lists appends the rows left unmarked.  A partition without probe rows has
+// no work item: its bits stay zero, all its rows are unmatched.  Duplicate build keys: as the left join, the whole output is rewritten
+// with row indices on the build side - new chunk pools, so the bitmap is cleared and filled again.
+int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
+              hipStream_t s, fj_timings* t, u64* out_counts, u64* d_ok, u64* d_ov, bool rid) {
+    out_counts[0] = out_counts[1] = 0;
+    if (nb == 0) return join_outer(c, FJ_OJ_LEFT, use_radix, bk, bv, nb, pk, np, top_bits, s, t, &out_counts[0], d_ok, d_ov, rid);
+    if (np == 0) {                                           // every build row is unmatched
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        if (rid) { HIPCHK(hipMemsetAsync(d_ok, 0xFF, nb * 8, s)); HIPCHK(fj_launch_iota(d_ov, nb, s)); }
+        else {
+            HIPCHK(hipMemcpyAsync(d_ok, bk, nb * 8, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_ov, bv, nb * 8, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        HIPCHK(hipStreamSynchronize(s));
+        t->path = use_radix ? 0 : 1; t->total_ms = t->emit_ms = ev_ms(c, E_START, E_JOIN);
+        out_counts[1] = nb;
+        return 0;
+    }
+    if (!use_radix) return join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, t, &out_counts[0], d_ok, d_ov, rid, &out_counts[1]);
+
+    const Plan plan = make_plan(nb, top_bits, false);
+    begin_plan(c);
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (clear_plan_scalars(c, s)) return 1;                  // (total = the hit cursor, expected = the miss cursor, sample_hits = the sweep's)
+    FjLdsJoinArgs ja{};
+    PassIter bit, pit;
+    pass_init(bit, 0, true, nb, plan, top_bits);
+    bit.vals_pos = rid;
+    int evc = 0;
+    if (run_passes(c, bit, bk, rid ? nullptr : bv, s, &ja.build, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    pass_init(pit, 1, rid, np, plan, top_bits);
+    pit.vals_pos = rid;
+    pit.want_items = true;
+    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
+    if (ja.probe.list) {
+        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
+    } else {                                                 // zero-pass plan: slices of the flat probe side
+        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
+        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
+    }
+    ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
+    ja.out_cursor = &c->d_sc->total; ja.out_capacity = np; ja.out_keys = d_ok; ja.out_vals = d_ov;
+    ja.row_ids = rid ? 1u : 0u;
+    const u64 out_cap = (u64)np + nb;
+    void* p;
+    // the join, then the sweep behind it on the same stream: one read-back serves both (a join that reports duplicates or a partition
+    // beyond its table leaves rows behind row np that the rerun overwrites)
+    auto join_and_sweep = [&](int mode) -> int {
+        const size_t bit_bytes = (ja.build.list ? (size_t)ja.build.cap : (nb + FJ_CHUNK - 1) / FJ_CHUNK) * (FJ_CHUNK / 8);
+        if (get_buf(c, W_FULL_BITS, bit_bytes, &p)) return 1;
+        u64* bits = (u64*)p;
+        HIPCHK(hipMemsetAsync(bits, 0, bit_bytes, s));
+        HIPCHK(fj_launch_outer_join_full(ja, mode, np, &c->d_sc->expected, bits, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        HIPCHK(hipEventRecord(c->ev[E_EMIT0], s));
+        HIPCHK(fj_launch_full_sweep(ja.build, bits, ja.orig_vals, ja.row_ids, d_ok, d_ov, np, out_cap, &c->d_sc->sample_hits, &c->d_sc->err, s));
+        HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
+        if (read_scalars(c, s)) return 1;
+        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        return 0;
+    };
+    if (join_and_sweep(rid ? FJ_OJ_LEFT_FIRST : FJ_OJ_LEFT)) return 1;
+    end_plan(c);
+    if (!rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
+        // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
+        if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
+        u64* rowidx = (u64*)p;
+        HIPCHK(fj_launch_iota(rowidx, nb, s));
+        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both cursors
+        HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));  // ... and the sweep's
+        HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
+        HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
+        PassIter bit2;
+        pass_init(bit2, 0, true, nb, plan, top_bits);
+        begin_plan(c);
+        if (run_passes(c, bit2, bk, rowidx, s, &ja.build, nullptr)) return 1;
+        end_plan(c);
+        ja.orig_vals = bv;
+        if (join_and_sweep(FJ_OJ_LEFT_FIRST)) return 1;
+    }
+    plan_timings(c, plan, ja.nparts, evc, t);
+    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
+        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
+        if (join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, &t2, &out_counts[0], d_ok, d_ov, rid, &out_counts[1])) return 1;
+        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
+        return 0;
+    }
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the full outer join wrote out of its rows");
+    const u64 hits = c->h_sc->total, misses = c->h_sc->expected, rest = c->h_sc->sample_hits;
+    if (hits + misses != np || rest > nb) return set_err("internal error: full outer join placed %llu + %llu of %zu probe rows and %llu of %zu build rows",
+                                                         (unsigned long long)hits, (unsigned long long)misses, np, (unsigned long long)rest, nb);
+    t->emit_ms = ev_ms(c, E_EMIT0, E_EMIT1); t->total_ms += t->emit_ms;
+    out_counts[0] = hits; out_counts[1] = rest;
     return 0;
 }
 

@@ -67,6 +67,22 @@ extern "C" {
  * work: materialize = 0, and with LEFT_OUTER or ANTI everything those flags refuse (FJ_ALGO_MANY_TO_MANY among it).  The multi-GPU
  * and stream joins take no algo word: they have no row-id form. */
 #define FJ_ALGO_ROW_IDS 0x80
+/* EXTENSION (no reference counterpart; csrc/fj_outer.hip): OR this into `algo` together with a base value (ADAPTIVE, SCALAR or RADIX:
+ * the partitioned plan or the global HBM table exactly as for FJ_ALGO_LEFT_OUTER) and optionally FJ_ALGO_ROW_IDS for the full outer
+ * join, fused into ONE call and one set of partition passes.  N:1 semantics as everywhere.  materialize = 1 only; d_out_keys and
+ * d_out_vals (8-byte aligned) hold >= np + nb rows (room for any result: the caller trims).
+ * With this flag out_count points to TWO words: out_count[0] = m, out_count[1] = r, and np + r rows are written in three ranges:
+ *   [0, m)        matched (probe_key, build_value), a duplicated build key with its FIRST occurrence's value
+ *                 (FJ_ALGO_ROW_IDS: probe position, build position of the first occurrence)
+ *   [m, np)       unmatched probe keys, value 0                       (FJ_ALGO_ROW_IDS: probe position, UINT64_MAX)
+ *   [np, np + r)  (build_key, build_value) of EVERY build row whose key is not among the probe keys, all copies of a duplicated
+ *                 key included                                       (FJ_ALGO_ROW_IDS: UINT64_MAX, build position)
+ * Rows [0, np) are what FJ_ALGO_LEFT_OUTER writes for the same inputs; order within each range unspecified.  bloom is ignored; never
+ * a pending result for fj_emit_pairs (a result that was pending is dropped).  fj_join_host: out_count likewise points to two words,
+ * *out_keys / *out_vals are malloc'ed arrays of np + r rows.  fj_timings: emit_ms is the sweep that appends the third range.
+ * Refused up front, before any device work: combined with FJ_ALGO_LEFT_OUTER, FJ_ALGO_ANTI or FJ_ALGO_MANY_TO_MANY; materialize = 0;
+ * an output capacity below np + nb; NULL or misaligned output buffers; d_build_vals == NULL without FJ_ALGO_ROW_IDS. */
+#define FJ_ALGO_FULL_OUTER 0x100
 
 typedef struct fj_ctx fj_ctx;
 
