@@ -37,6 +37,7 @@ ALGO_LEFT_OUTER = 0x20            # FJ_ALGO_LEFT_OUTER: left outer join, np rows
 ALGO_ANTI = 0x40                  # FJ_ALGO_ANTI: the probe rows without a partner (extension)
 ALGO_ROW_IDS = 0x80               # FJ_ALGO_ROW_IDS: output rows hold row positions (gather maps) instead of keys and values (extension)
 ALGO_FULL_OUTER = 0x100           # FJ_ALGO_FULL_OUTER: full outer join, np + r rows; the count is the pair (m, r) (extension)
+ALGO_ALL_COPIES = 0x200           # FJ_ALGO_ALL_COPIES: modifier of LEFT_OUTER / FULL_OUTER - every copy of a duplicated build key; the count is (P, r, u) (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -115,7 +116,7 @@ def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_array
     bv = _as_u64_host(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
     if bv is not None and bv.size < bk.size:
         raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
-    cnt = (ctypes.c_uint64 * 2)(0, 0)                   # (a full outer join fills both words: matched probe rows, unmatched build rows)
+    cnt = (ctypes.c_uint64 * 3)(0, 0, 0)                # (a full outer join fills two words: matched probe rows, unmatched build rows; ALL_COPIES three)
     sec = ctypes.c_double(0.0)
     ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
     want = bool(materialize and return_arrays)
@@ -126,6 +127,19 @@ def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_array
     L.fj_last_timings(ctypes.byref(t))
     _last = t
     n = int(cnt[0])
+    if algo & ALGO_ALL_COPIES:          # P + u + r rows; the count is the triple (P, r, u)
+        c3 = (n, int(cnt[1]), int(cnt[2]))
+        if not want:
+            return c3, float(sec.value)
+        rows = sum(c3)
+        try:
+            arr = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
+                             else np.empty(0, np.uint64))
+            keys, vals = arr(ok), arr(ov)
+        finally:
+            L.fj_free_host(ok)
+            L.fj_free_host(ov)
+        return c3, float(sec.value), keys, vals
     if algo & ALGO_FULL_OUTER:          # np + r rows; the count is the pair (m, r)
         r = int(cnt[1])
         if not want:
@@ -205,6 +219,23 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     cnt = ctypes.c_uint64(0)
     t = FjTimings()
     bv_ptr = bv.data_ptr() if bv is not None else None
+    if algo & ALGO_ALL_COPIES:
+        # every copy of a duplicated build key: the size is not known up front - count, allocate exactly P + u + r rows, emit;
+        # the two calls share the context's one pending result, so other threads stay out in between.  The count is (P, r, u)
+        cnt3 = (ctypes.c_uint64 * 3)(0, 0, 0)
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(), pk.numel(), stream,
+                                   hash_top_bits, cnt3, None, None, 0, ctypes.byref(t)))
+            c3 = (int(cnt3[0]), int(cnt3[1]), int(cnt3[2]))
+            rows = sum(c3)
+            ok = torch.empty(rows, dtype=torch.int64, device=bk.device)
+            ov = torch.empty(rows, dtype=torch.int64, device=bk.device)
+            if rows:
+                check(L.fj_emit_pairs(ctx, ok.data_ptr(), ov.data_ptr(), rows, stream, ctypes.byref(t)))
+        _last = t
+        if not return_arrays:
+            return c3, t.total_ms * 1e-3
+        return c3, t.total_ms * 1e-3, ok, ov
     if algo & ALGO_FULL_OUTER:
         # full outer join: room for every row of both sides, one call, never a pending result; the count is the pair (m, r)
         n_p, n_b = pk.numel(), bk.numel()
@@ -380,20 +411,38 @@ def inner_join(build_keys, build_values, probe_keys, return_arrays: bool = False
 
 
 # ---- extension: left outer and anti joins (N:1 semantics: a duplicated build key matches with its FIRST occurrence's value) ---------
-def _fill(vals, m: int, fill_value):
-    if fill_value == 0 or vals.shape[0] == m:
+def _fill(vals, m: int, fill_value, end: Optional[int] = None):
+    end = vals.shape[0] if end is None else end
+    if fill_value == 0 or end <= m:
         return vals
     if _is_torch_tensor(vals):
-        vals[m:] = int(np.array(fill_value, dtype=np.uint64).view(np.int64))     # int64 storage of the uint64 word
+        vals[m:end] = int(np.array(fill_value, dtype=np.uint64).view(np.int64))     # int64 storage of the uint64 word
     else:
-        vals[m:] = np.uint64(fill_value)
+        vals[m:end] = np.uint64(fill_value)
     return vals
 
 
-def left_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0):
+def _all_copies(duplicates: str, who: str) -> bool:
+    if duplicates not in ("first", "all"):
+        raise ValueError(f"{who}: duplicates must be 'first' or 'all', got {duplicates!r}")
+    return duplicates == "all"
+
+
+def left_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0, duplicates: str = "first"):
     """Left outer join: every probe row once.  Returns (m, seconds) or (m, seconds, keys, values), m = matched probe rows (what
     the counting joins return).  keys / values hold len(probe_keys) rows: rows [0, m) the matched (probe_key, build_value) pairs,
-    rows [m, n) the unmatched probe keys with value `fill_value`; order within either range unspecified."""
+    rows [m, n) the unmatched probe keys with value `fill_value`; order within either range unspecified.
+
+    duplicates="all" (SQL semantics; "first" is the N:1 rule above): a probe row yields one row per build row with its key.  Returns
+    (P, u, seconds) or (P, u, seconds, keys, values): P pairs (what inner_join_count returns), u probe rows without a partner (what
+    anti_join_count returns); P + u rows, `fill_value` in rows [P, P + u).  A build key with thousands of copies is refused, as by
+    inner_join."""
+    if _all_copies(duplicates, "left_join"):
+        res = _join(ALGO_ADAPTIVE | ALGO_LEFT_OUTER | ALGO_ALL_COPIES, 0, 1, build_keys, build_values, probe_keys, return_arrays)
+        (P, _, u), sec = res[0], res[1]
+        if not return_arrays:
+            return P, u, sec
+        return P, u, sec, res[2], _fill(res[3], P, fill_value, P + u)
     r = _join(ALGO_ADAPTIVE | ALGO_LEFT_OUTER, 0, 1, build_keys, build_values, probe_keys, return_arrays)
     if not return_arrays:
         return r
@@ -414,12 +463,22 @@ def anti_join_count(build_keys, probe_keys):
 
 
 # ---- extension: full outer join, fused into one call and one set of partition passes (csrc/fj_outer.hip) ---------------------------
-def full_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0):
+def full_join(build_keys, build_values, probe_keys, return_arrays: bool = False, fill_value: int = 0, duplicates: str = "first"):
     """Full outer join (N:1).  Returns (m, r, seconds) or (m, r, seconds, keys, values) with len(probe_keys) + r rows:
     rows [0, m) the matched (probe_key, build_value) pairs (a duplicated build key: its FIRST occurrence's value), rows
     [m, len(probe_keys)) the unmatched probe keys with value `fill_value` - together what left_join returns - and behind them the r
     build rows (build_key, build_value) whose key is not among the probe keys, every copy of a duplicated key included.  Order
-    within each range unspecified."""
+    within each range unspecified.
+
+    duplicates="all" (SQL semantics): every copy of a duplicated build key pairs with the probe rows of its key.  Returns
+    (P, u, r, seconds) or (P, u, r, seconds, keys, values) with P + u + r rows: rows [0, P) the pairs, rows [P, P + u) the unmatched
+    probe keys with `fill_value`, rows [P + u, P + u + r) the build rows whose key is not among the probe keys."""
+    if _all_copies(duplicates, "full_join"):
+        res = _join(ALGO_ADAPTIVE | ALGO_FULL_OUTER | ALGO_ALL_COPIES, 0, 1, build_keys, build_values, probe_keys, return_arrays)
+        (P, r, u), sec = res[0], res[1]
+        if not return_arrays:
+            return P, u, r, sec
+        return P, u, r, sec, res[2], _fill(res[3], P, fill_value, P + u)
     res = _join(ALGO_ADAPTIVE | ALGO_FULL_OUTER, 0, 1, build_keys, build_values, probe_keys, return_arrays)
     (m, r), sec = res[0], res[1]
     if not return_arrays:
@@ -450,7 +509,7 @@ def semi_join_count(build_keys, probe_keys):
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
 
-def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool = False):
+def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool = False, duplicates: str = "first"):
     """Row-index gather maps of a join: which probe row matched which build row, so that the caller can gather the other
     columns of both tables.  Positions are 0-based row numbers of the flattened inputs; order within each range unspecified.
 
@@ -462,14 +521,25 @@ def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool 
     how="semi"   (s, seconds, probe_idx, None): the s probe rows whose key IS among the build keys, each once.
     how="full"   (m, r, seconds, probe_idx, build_idx): len(probe_keys) + r rows - the rows of how="left", then the r build rows
                  whose key is not among the probe keys with probe_idx == -1 (every copy of a duplicated key).
+    duplicates="all" (every copy of a duplicated build key; "first" is the rule above):
+    how="left"   (P, u, seconds, probe_idx, build_idx): P + u rows - one per (probe row, build row) pair with equal keys, then the
+                 u probe rows without a partner with build_idx == -1.
+    how="full"   (P, u, r, seconds, probe_idx, build_idx): P + u + r rows - those, then the r build rows whose key is not among
+                 the probe keys with probe_idx == -1.
+    how="inner"  the same as many_to_many=True; how="semi" / "anti": as without it (multiplicity does not matter to them).
     The index arrays are int64: NumPy for host inputs, torch.int64 on the inputs' device for device tensors / DLPack."""
     if how not in _HOW:
         raise ValueError(f"join_indices: how must be one of {sorted(_HOW)}, got {how!r}")
     if many_to_many and how != "inner":
         raise ValueError(f"join_indices: many_to_many=True needs how='inner' (got how={how!r})")
+    all_copies = _all_copies(duplicates, "join_indices")
+    as_i64 = lambda a: a if a is None or _is_torch_tensor(a) else np.asarray(a).view(np.int64)
+    if all_copies and how in ("left", "full"):
+        (P, r, u), sec, pi, bi = _join(ALGO_ADAPTIVE | _HOW[how] | ALGO_ALL_COPIES | ALGO_ROW_IDS, 0, 1, build_keys, None, probe_keys, True)
+        return (P, u, sec, as_i64(pi), as_i64(bi)) if how == "left" else (P, u, r, sec, as_i64(pi), as_i64(bi))
+    many_to_many = many_to_many or (all_copies and how == "inner")
     algo = (ALGO_RADIX | ALGO_MANY_TO_MANY if many_to_many else ALGO_ADAPTIVE | _HOW[how]) | ALGO_ROW_IDS
     n, sec, pi, bi = _join(algo, 0, 1, build_keys, None, probe_keys, True)
-    as_i64 = lambda a: a if a is None or _is_torch_tensor(a) else np.asarray(a).view(np.int64)
     if how == "full":
         return n[0], n[1], sec, as_i64(pi), as_i64(bi)
     if how == "semi":

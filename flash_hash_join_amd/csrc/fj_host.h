@@ -110,6 +110,10 @@ struct Pending {
     // oversized partitions that skew_join re-partitioned: their sub-partitions are a second item set, emitted behind the first
     bool has_second = false; FjLdsJoinArgs lds2{}; u32 nitems2 = 0; u64 count_main = 0; std::vector<u32> flagged;
     bool dups_main = false; std::vector<u32> sk_parts; int sk_bits = 0, sk_plan_bits = 0, sk_npass = 0;     // ... which partitions, by how many more bits (the first-occurrence emit path repeats it with row indices)
+    // MANY, outer forms (FJ_ALGO_ALL_COPIES; mm_outer != FJ_MM_INNER): `count` is P + u + r; the emit scans the misses per item too, writes
+    // them behind the P pairs and - mm_r > 0 - sweeps the build rows the counting pass left unmarked in mm.bits behind those
+    int mm_outer = 0; FjMmOuterArgs mm{}; u64 mm_P = 0, mm_u = 0, mm_r = 0;
+    bool mm_trivial = false; const u64* mm_pk = nullptr;        // ... one side was empty: no partitions, the emit copies the other side's rows (bk / bv below, mm_pk)
     // duplicate build keys seen by the counting pass: the emitting pass must pick the FIRST occurrence's value
     bool has_dups = false;
     const u64* bk = nullptr; const u64* bv = nullptr; size_t nb = 0; int top_bits = 64;

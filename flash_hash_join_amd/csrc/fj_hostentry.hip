@@ -178,7 +178,13 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
+    if (allc) {                                                // (the checks of fj_join_device, before the context is created)
+        if (anti) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_ANTI (an anti join has no copies to keep)");
+        if (many_host) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
+        if (!left && !full) return set_err("fj_join_host: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo);
+    }
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
@@ -190,7 +196,12 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (nb && !bv && !rid) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER needs build values (only FJ_ALGO_ROW_IDS reads none)");
         if (!out_count) return set_err("fj_join_host: FJ_ALGO_FULL_OUTER needs out_count (two words: matched probe rows, unmatched build rows)");
     }
-    const bool outer_mat = (left || anti) && materialize;      // left outer / anti join writing rows: np-row device buffers, no emit step
+    if (allc) {
+        if (!materialize) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES needs materialize = 1 (there is no counting-only form)");
+        if (nb && !bv && !rid) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES needs build values (only FJ_ALGO_ROW_IDS reads none)");
+        if (!out_count) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES needs out_count (three words: pairs, unmatched build rows, unmatched probe rows)");
+    }
+    const bool outer_mat = (left || anti) && materialize && !allc;      // left outer / anti join writing rows: np-row device buffers, no emit step
     {
         static std::mutex create_mu;
         std::lock_guard<std::mutex> lk(create_mu);
@@ -255,7 +266,27 @@ int fj_join_host(int algo, int bloom, int materialize,
     const double h2d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     double d2h = 0;
     u64 full_r = 0;
-    if (full) {                                                                // full outer join: (np + nb)-row device buffers, np + r rows back
+    u64 ac[3] = {0, 0, 0};
+    if (allc) {                                                                // every copy of a duplicated build key: count, exact-size device buffers, emit
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
+                           ac, nullptr, nullptr, 0, &t)) return 1;
+        count = ac[0];
+        const size_t rows = (size_t)(ac[0] + ac[1] + ac[2]);
+        void *dok, *dov;
+        if (get_buf(c, W_H_OK, std::max<size_t>(rows, 1) * 8, &dok) || get_buf(c, W_H_OV, std::max<size_t>(rows, 1) * 8, &dov)) return 1;
+        if (emit_pending(c, (u64*)dok, (u64*)dov, rows, js, &t)) return 1;
+        if (out_keys && out_vals) {
+            u64* hk = (u64*)malloc(std::max<size_t>(rows, 1) * 8);
+            u64* hv = (u64*)malloc(std::max<size_t>(rows, 1) * 8);
+            if (!hk || !hv) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", rows); }
+            auto t1 = std::chrono::steady_clock::now();
+            if (rows) { HIPCHK(hipMemcpy(hk, dok, rows * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hv, dov, rows * 8, hipMemcpyDeviceToHost)); }
+            d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+            *out_keys = hk; *out_vals = hv;
+        }
+        joined = true;
+    }
+    if (full && !allc) {                                                                // full outer join: (np + nb)-row device buffers, np + r rows back
         void *dok, *dov;
         const size_t cap = np + nb;
         if (get_buf(c, W_H_OK, std::max<size_t>(cap, 1) * 8, &dok) || get_buf(c, W_H_OV, std::max<size_t>(cap, 1) * 8, &dov)) return 1;
@@ -314,10 +345,11 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined && !outer_mat && !full ? 1 : 0;
+    t.host_streamed = joined && !outer_mat && !full && !allc ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
-    if (full) out_count[1] = full_r;
+    if (full && !allc) out_count[1] = full_r;
+    if (allc) { out_count[1] = ac[1]; out_count[2] = ac[2]; }
     if (out_seconds) *out_seconds = t.total_ms * 1e-3;
     return 0;
 }

@@ -214,7 +214,21 @@ hipError_t fj_launch_sample_hits(const FjChunkSet& build, const u64* pk, u64 np,
                                  unsigned long long* hits, hipStream_t s);
 
 // many-to-many join of one work item's partition (csrc/fj_many.hip): counting (part_count / total) or emitting at out_off
-hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s);
+// outer forms (FJ_ALGO_ALL_COPIES): FJ_MM_LEFT also reports the probe rows without a partner; FJ_MM_FULL (counting pass) also marks
+// the build rows that have one in `bits`, the bitmap fj_launch_full_sweep reads (one bit per row of the build side's final chunk
+// pool, zeroed before the launch).  The emitting pass is the same for both: pairs at out_off[item], misses at miss_base + miss_off[item]
+#define FJ_MM_INNER 0
+#define FJ_MM_LEFT 1
+#define FJ_MM_FULL 2
+struct FjMmOuterArgs {
+    u32* miss_count;                 // [items] probe rows without a partner per work item (zeroed before the counting launch)
+    unsigned long long* miss_total;  // device scalar: their sum, u
+    const u64* miss_off;             // emitting pass: [items+1] exclusive scan of miss_count
+    u64 miss_base;                   // emitting pass: first row of the misses' range (P, the number of pairs)
+    u64* bits;                       // FULL, counting pass
+    unsigned long long* marked;      // FULL, counting pass: device scalar, build rows whose bit this launch turned on (r = nb - marked)
+};
+hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer = FJ_MM_INNER, const FjMmOuterArgs* oa = nullptr);
 
 struct FjGtArgs {                // global (non-partitioned) table
     u64* tkeys; u64* tvals; u32* bloom;    // bloom == nullptr: no precheck

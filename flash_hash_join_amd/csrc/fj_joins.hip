@@ -78,7 +78,29 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
             if (get_buf(c, W_OUT_OFF, ((size_t)pd.nitems + 1) * 8, &p)) return 1;
             HIPCHK(fj_launch_scan_u32_to_u64(pd.lds.part_count, (u64*)p, pd.nitems, s));
             pd.lds.out_off = (const u64*)p; pd.lds.out_keys = d_ok; pd.lds.out_vals = d_ov;
-            HIPCHK(fj_launch_mm_join(pd.lds, true, s));
+            if (pd.mm_outer == FJ_MM_INNER) HIPCHK(fj_launch_mm_join(pd.lds, true, s));
+            else if (pd.mm_trivial) {               // an empty side: the other side's rows as they are (row ids: their positions beside UINT64_MAX)
+                const bool rid = pd.lds.row_ids != 0;
+                if (pd.mm_u) {
+                    if (rid) HIPCHK(fj_launch_iota(d_ok, pd.mm_u, s)); else HIPCHK(hipMemcpyAsync(d_ok, pd.mm_pk, pd.mm_u * 8, hipMemcpyDeviceToDevice, s));
+                    HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, pd.mm_u * 8, s));
+                } else if (rid) {
+                    HIPCHK(hipMemsetAsync(d_ok, 0xFF, pd.mm_r * 8, s)); HIPCHK(fj_launch_iota(d_ov, pd.mm_r, s));
+                } else {
+                    HIPCHK(hipMemcpyAsync(d_ok, pd.bk, pd.mm_r * 8, hipMemcpyDeviceToDevice, s));
+                    HIPCHK(hipMemcpyAsync(d_ov, pd.bv, pd.mm_r * 8, hipMemcpyDeviceToDevice, s));
+                }
+            } else {                                  // outer forms: the misses' offsets too, then - FULL - the unmarked build rows behind both
+                if (get_buf(c, W_OUT_OFF2, ((size_t)pd.nitems + 1) * 8, &p)) return 1;
+                HIPCHK(fj_launch_scan_u32_to_u64(pd.mm.miss_count, (u64*)p, pd.nitems, s));
+                pd.mm.miss_off = (const u64*)p; pd.mm.miss_base = pd.mm_P;
+                HIPCHK(fj_launch_mm_join(pd.lds, true, s, pd.mm_outer, &pd.mm));
+                if (pd.mm_r) {
+                    HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));      // (the sweep's row cursor)
+                    HIPCHK(fj_launch_full_sweep(pd.lds.build, pd.mm.bits, nullptr, pd.lds.row_ids, d_ok, d_ov, pd.mm_P + pd.mm_u, pd.count,
+                                                &c->d_sc->sample_hits, &c->d_sc->err, s));
+                }
+            }
         } else if (pd.kind == Pending::HBM_TABLE) {
             if (get_buf(c, W_OUT_OFF, ((size_t)pd.gt_grid + 1) * 8, &p)) return 1;
             HIPCHK(fj_launch_scan_u32_to_u64(pd.gt.wg_count, (u64*)p, pd.gt_grid, s));
@@ -104,6 +126,8 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
         if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_POOL)) return set_err("fj_emit_pairs: the emitting pass could not place every partition in LDS (device error word 0x%x)", c->h_sc->err);
         if (pd.kind == Pending::BCAST && (c->h_sc->err & FJ_STAT_RETRY))
             return set_err("internal error: a partition the counting kernel accepted does not fit the pair writer's table (fj_emit_pairs)");
+        if (pd.kind == Pending::MANY && pd.mm_r && !pd.mm_trivial && ((c->h_sc->err & FJ_ERR_OUTCAP) || c->h_sc->sample_hits != pd.mm_r))
+            return set_err("internal error: the sweep appended %llu of %llu unmatched build rows (fj_emit_pairs)", c->h_sc->sample_hits, (unsigned long long)pd.mm_r);
     }
     HIPCHK(hipStreamSynchronize(s));
     if (t) { t->emit_ms = ev_ms(c, E_EMIT0, E_EMIT1); t->total_ms += t->emit_ms; t->probe_phase_ms += t->emit_ms; }
@@ -467,8 +491,12 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
 // EXTENSION: many-to-many inner join on the partitioned plan (csrc/fj_many.hip).  Build relation first (with its values when
 // materialising), then the probe relation, then one workgroup per work item; no bloom stage, no fallback: a partition of
 // more than 4096 build rows is an error.
+// outer = FJ_MM_LEFT / FJ_MM_FULL (FJ_ALGO_ALL_COPIES, materialising): out_count points to three words - P pairs, r build rows without
+// a probe partner (LEFT: 0), u probe rows without a build partner; the pending result holds P + u + r rows.  The counting launch
+// keeps the misses per item beside the pairs per item and - FULL - marks the matched build rows (bitmap in W_FULL_BITS, kept for the
+// emit's sweep) and counts them: r = nb - marked.
 int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
-              hipStream_t s, fj_timings* t, u64* out_count, bool rid = false) {
+              hipStream_t s, fj_timings* t, u64* out_count, bool rid = false, int outer = FJ_MM_INNER) {
     const Plan plan = make_plan(nb, top_bits, false, 2048);          // aim at half of the kernel's 4096 rows per partition
     begin_plan(c);
     HIPCHK(hipEventRecord(c->ev[E_START], s));
@@ -498,7 +526,19 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
         if (get_buf(c, W_PART_COUNT, (size_t)nitems * 4, &p)) return 1; ja.part_count = (u32*)p;
     }
     ja.total = &c->d_sc->total; ja.err = &c->d_sc->err;
-    HIPCHK(fj_launch_mm_join(ja, false, s));
+    FjMmOuterArgs oa{};
+    if (outer != FJ_MM_INNER) {                                      // (total = the pairs, expected = the misses, bloom_survivors = the marked build rows)
+        if (get_buf(c, W_PART_COUNT2, (size_t)nitems * 4, &p)) return 1;
+        oa.miss_count = (u32*)p; oa.miss_total = &c->d_sc->expected;
+        HIPCHK(hipMemsetAsync(oa.miss_count, 0, (size_t)nitems * 4, s));    // (entries past the number of items are never written)
+        if (outer == FJ_MM_FULL) {
+            const size_t bit_bytes = (ja.build.list ? (size_t)ja.build.cap : (nb + FJ_CHUNK - 1) / FJ_CHUNK) * (FJ_CHUNK / 8);
+            if (get_buf(c, W_FULL_BITS, bit_bytes, &p)) return 1;
+            oa.bits = (u64*)p; oa.marked = &c->d_sc->bloom_survivors;
+            HIPCHK(hipMemsetAsync(oa.bits, 0, bit_bytes, s));
+        }
+    }
+    HIPCHK(fj_launch_mm_join(ja, false, s, outer, &oa));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
@@ -508,6 +548,13 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
     *out_count = c->h_sc->total;
     plan_timings(c, plan, ja.nparts, evc, t);
     if (materialize) { c->pend.valid = true; c->pend.kind = Pending::MANY; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count; }
+    if (outer != FJ_MM_INNER) {
+        const u64 P = c->h_sc->total, u = c->h_sc->expected, marked = outer == FJ_MM_FULL ? c->h_sc->bloom_survivors : 0;
+        if (u > np || marked > nb) { drop_pending(c); return set_err("internal error: all-copies outer join counted %llu of %zu probe rows unmatched and %llu of %zu build rows matched", (unsigned long long)u, np, (unsigned long long)marked, nb); }
+        const u64 r = outer == FJ_MM_FULL ? nb - marked : 0;
+        out_count[0] = P; out_count[1] = r; out_count[2] = u;
+        c->pend.mm_outer = outer; c->pend.mm = oa; c->pend.mm_P = P; c->pend.mm_u = u; c->pend.mm_r = r; c->pend.count = P + u + r;
+    }
     return 0;
 }
 
@@ -525,6 +572,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
+    const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
+    const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     if (rid) {
         // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
@@ -533,7 +582,21 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (!d_bv) d_bv = d_bk;                             // never read: the build rows' positions are made on the device
         bloom = 0;                                          // (the filter kernel moves no payload)
     }
-    if (full) {
+    if (allc) {
+        // left / full outer join that keeps every copy of a duplicated build key (csrc/fj_many.hip): every check before any device
+        // work, so that it holds for a null context too.  The result's size is not known up front: no capacity check here, the
+        // two-phase rule of the materialising joins applies (count, then fj_emit_pairs - or both in this call)
+        algo &= ~(FJ_ALGO_ALL_COPIES | FJ_ALGO_LEFT_OUTER | FJ_ALGO_FULL_OUTER);
+        if (anti) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_ANTI (an anti join has no copies to keep)");
+        if (many) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
+        if (!left && !full) return set_err("fj_join_device: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo_word);
+        if (left && full) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_LEFT_OUTER");
+        if (!materialize) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs materialize = 1 (there is no counting-only form)");
+        if (!out_count) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs out_count (three words: pairs, unmatched build rows, unmatched probe rows)");
+        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
+        if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs d_build_vals (only FJ_ALGO_ROW_IDS reads no build value)");
+    }
+    if (full && !allc) {
         // full outer join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
         algo &= ~FJ_ALGO_FULL_OUTER;
         if (left || anti) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_%s", left ? "LEFT_OUTER" : "ANTI");
@@ -545,7 +608,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs d_build_vals (only FJ_ALGO_ROW_IDS reads no build value)");
         if (!out_count) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs out_count (two words: matched probe rows, unmatched build rows)");
     }
-    if (left || anti) {
+    if ((left || anti) && !allc) {
         // left outer / anti join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
         algo &= ~(FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI);
         if (left && anti) return set_err("fj_join_device: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
@@ -571,6 +634,23 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const Options& opt = options();
     bool use_radix = algo == FJ_ALGO_RADIX || (algo == FJ_ALGO_ADAPTIVE && nb >= opt.radix_threshold) ||
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
+    if (allc) {                                             // every copy of a duplicated build key: the many-to-many kernel's outer forms, always the partitioned plan
+        u64 c3[3] = {0, 0, 0};
+        if (nb == 0 || np == 0) {
+            // an empty side needs no join: every row of the other side is unmatched (emit_pending copies them)
+            if (clear_plan_scalars(c, s)) return 1;
+            c3[1] = (np == 0 && full) ? nb : 0; c3[2] = nb == 0 ? np : 0;
+            Pending& pd = c->pend;
+            pd.valid = true; pd.kind = Pending::MANY; pd.mm_outer = full ? FJ_MM_FULL : FJ_MM_LEFT; pd.mm_trivial = true;
+            pd.lds.row_ids = rid ? 1u : 0u; pd.bk = d_bk; pd.bv = d_bv; pd.mm_pk = d_pk;
+            pd.mm_P = 0; pd.mm_u = c3[2]; pd.mm_r = c3[1]; pd.count = c3[1] + c3[2];
+        } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, c3, rid, full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
+        out_count[0] = c3[0]; out_count[1] = c3[1]; out_count[2] = c3[2];
+        if (d_out_keys && d_out_vals && emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
     if (full) {                                             // the left join and the unmatched build rows in one plan, never a pending result
         u64 counts[2] = {0, 0};
         if (join_full(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, counts, (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;

@@ -83,6 +83,28 @@ extern "C" {
  * Refused up front, before any device work: combined with FJ_ALGO_LEFT_OUTER, FJ_ALGO_ANTI or FJ_ALGO_MANY_TO_MANY; materialize = 0;
  * an output capacity below np + nb; NULL or misaligned output buffers; d_build_vals == NULL without FJ_ALGO_ROW_IDS. */
 #define FJ_ALGO_FULL_OUTER 0x100
+/* EXTENSION (no reference counterpart; csrc/fj_many.hip): a MODIFIER - OR it into `algo` together with FJ_ALGO_LEFT_OUTER or
+ * FJ_ALGO_FULL_OUTER (and optionally FJ_ALGO_ROW_IDS) and the outer join keeps EVERY copy of a duplicated build key (SQL semantics,
+ * what FJ_ALGO_MANY_TO_MANY is to the inner join): a probe row yields one output row per build row with its key, and one row with
+ * the filler when there is none.  materialize = 1 only.  Partitioned plan only, like FJ_ALGO_MANY_TO_MANY: the base value (ADAPTIVE,
+ * SCALAR or RADIX) is accepted and never selects the HBM table, bloom is ignored, and a final partition of more than 4096 build rows
+ * is refused with the same error (the context stays usable).
+ * With this flag out_count points to THREE words, for both forms: out_count[0] = P, the matched pairs (what the many-to-many inner
+ * join counts), out_count[1] = r, the build rows whose key no probe row has (0 with FJ_ALGO_LEFT_OUTER), out_count[2] = u, the probe
+ * rows without a partner (what the counting anti join returns).  P + u + r rows are written, in three ranges:
+ *   [0, P)             (probe_key, build_value) of every pair                (FJ_ALGO_ROW_IDS: probe position, build position)
+ *   [P, P + u)         unmatched probe keys, value 0                         (FJ_ALGO_ROW_IDS: probe position, UINT64_MAX)
+ *   [P + u, P + u + r) (FULL only) (build_key, build_value), every copy      (FJ_ALGO_ROW_IDS: UINT64_MAX, build position)
+ * Order within each range unspecified.  The result's size is not known up front, so the two-phase rule of the materialising joins
+ * (fj_join_device below) applies unchanged: with d_out_keys == NULL the call counts, fills the three words and leaves ONE pending
+ * result on the context; fj_emit_pairs writes all P + u + r rows into buffers of at least that capacity.  With buffers and
+ * out_capacity >= P + u + r both steps happen in the one call.  fj_timings: emit_ms covers the emitting pass and the sweep that
+ * appends the third range.  fj_join_host: out_count likewise three words, *out_keys / *out_vals malloc'ed arrays of P + u + r rows.
+ * An empty side needs no join: nb == 0 gives P = r = 0, u = np; np == 0 gives P = u = 0 and, for FULL, r = nb.
+ * Refused up front, before any device work: the flag without FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER (an unknown algo: the inner
+ * form is FJ_ALGO_MANY_TO_MANY), or with FJ_ALGO_ANTI (an anti join has no copies to keep) or FJ_ALGO_MANY_TO_MANY; materialize = 0;
+ * out_count == NULL; misaligned output buffers; d_build_vals == NULL without FJ_ALGO_ROW_IDS. */
+#define FJ_ALGO_ALL_COPIES 0x200
 
 typedef struct fj_ctx fj_ctx;
 
