@@ -351,7 +351,9 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
                     const u64 key = bk[j];
                     if (key == FJ_EMPTY_KEY) {
                         hdr->has_empty = 1;
-                        if (MAT) hdr->empty_val = bv[j];
+                        if (MAT) {                           // dedup: bv is the row index and, as for every stored key, the smallest copy's wins
+                            if (dedup) atomicMin((unsigned long long*)&hdr->empty_val, (unsigned long long)bv[j]); else hdr->empty_val = bv[j];
+                        }
                     } else if (!(a.dbg_flags & 2u)) {
                         claimed += lds_insert<MAT>(tkeys, tvals, ttags, gcnt, hdr, key, bv[j], dedup) ? 1u : 0u;
                     }
@@ -1121,8 +1123,9 @@ __global__ __launch_bounds__(NT, 4) void fj_emit_join_persistent(FjLdsJoinArgs a
 #pragma unroll
                     for (u32 j = 0; j < BKPT; ++j) {
                         if (bok & (1u << j)) {
-                            if (bk[j] == FJ_EMPTY_KEY) hdr->has_empty = 1;
-                            else cuckoo_claim(tkeys, bits, ovf, hdr, bk[j]);
+                            if (bk[j] == FJ_EMPTY_KEY) {             // never stored: a second copy is a duplicate no table sweep can see
+                                if (SINGLE) { if (atomicExch(&hdr->has_empty, 1u)) hdr->dups = 1; } else hdr->has_empty = 1;
+                            } else cuckoo_claim(tkeys, bits, ovf, hdr, bk[j]);
                         }
                     }
                 }

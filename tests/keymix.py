@@ -42,6 +42,38 @@ def unmix(h):
     return (hi << np.uint64(32)) | lo
 
 
+# ---- the keys the kernels treat out of band -----------------------------------------------------------------------------------
+# Chunk pools and LDS tables hold MIXED keys, so the partitioned kernels' empty marker (FJ_EMPTY_KEY, csrc/fj_common.h) and the
+# wide kernel's filler (W_POISON2, csrc/fj_join_wide.hip) are the raw keys whose mixed forms are these words; the HBM table
+# stores raw keys, so there the marker is raw 2^64 - 1.  tests/test_special_keys.py pins the two constants to the sources.
+EMPTY_MIXED = 0xFFFFFFFFFFFFFFFF
+FILLER_MIXED = 0x00000000FFFFFFFF
+EMPTY_RAW = int(unmix(np.array([EMPTY_MIXED], dtype=np.uint64))[0])
+FILLER_RAW = int(unmix(np.array([FILLER_MIXED], dtype=np.uint64))[0])
+
+
+def special_mixed_words(radix_bits):
+    """[(name, mixed word)] of the keys special_raw_keys(radix_bits) plants in the hash domain.  The two partition keys share
+    the low word (home slot) of the marker and the filler and differ from them in the first bit below the plan's radix_bits
+    partition bits (the top bits of the high word): the last / first partition of every plan of at most radix_bits bits."""
+    if not 0 <= radix_bits <= 31:
+        raise ValueError("radix_bits must be 0..31")
+    below = 1 << (31 - radix_bits)
+    return [("marker", EMPTY_MIXED), ("marker_minus_1", EMPTY_MIXED - 1), ("mixed_zero", 0), ("mixed_one", 1),
+            ("wide_filler", FILLER_MIXED), ("high_word_ones", 0xFFFFFFFF00000000),
+            (f"last_partition_low_ones_{radix_bits}", ((0xFFFFFFFF ^ below) << 32) | 0xFFFFFFFF),
+            (f"first_partition_low_ones_{radix_bits}", (below << 32) | 0xFFFFFFFF)]
+
+
+def special_raw_keys(radix_bits):
+    """(names, raw keys as a uint64 array): the raw keys whose mixed forms are special_mixed_words(radix_bits), then raw 2^64 - 1
+    and raw 0 - the marker and the zero of the HBM-table path, ordinary keys everywhere else.  The names serve as test ids."""
+    words = special_mixed_words(radix_bits)
+    names = [n for n, _ in words] + ["raw_all_ones", "raw_zero"]
+    raw = np.concatenate([unmix(np.array([w for _, w in words], dtype=np.uint64)), np.array([2**64 - 1, 0], dtype=np.uint64)])
+    return names, raw
+
+
 def hash_w1(k):
     """hash word 1 of raw keys (csrc/fj_common.h fj_hash_w1) as uint32"""
     return (mix(k) >> np.uint64(32)).astype(np.uint32)

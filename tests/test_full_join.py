@@ -13,6 +13,7 @@ import zlib
 import numpy as np
 import pytest
 
+import keymix
 from conftest import ROOT
 
 U64_MAX = np.uint64(2**64 - 1)
@@ -152,10 +153,11 @@ def _case(nb, n_p, hit, seed, probed=0.7):
     bk = rng.integers(0, 2**64, size=nb, dtype=np.uint64)
     npr = max(1, int(nb * probed)) if nb else 0
     if nb >= 40:
-        bk[0], bk[1] = 0, U64_MAX                                         # the empty marker and zero, probed
+        bk[0], bk[1] = 0, U64_MAX                                         # raw zero and raw 2^64 - 1 (the HBM table's empty marker), probed
+        bk[2], bk[3] = keymix.EMPTY_RAW, keymix.FILLER_RAW                # the LDS tables' empty marker and the wide kernel's filler, probed
         bk[nb - 1], bk[nb - 2] = 1, U64_MAX - np.uint64(1)                # their neighbours, never probed
         d = max(1, nb // 20)
-        bk[npr - d:npr] = bk[2:2 + d]                                     # duplicated build keys inside the probed share
+        bk[npr - d:npr] = bk[4:4 + d]                                     # duplicated build keys inside the probed share
         bk[nb - 2 - d:nb - 2] = bk[npr:npr + d]                           # ... and outside it: every copy is unmatched
     bv = rng.integers(0, 2**64, size=nb, dtype=np.uint64)
     nhit = int(n_p * hit) if nb else 0
@@ -164,8 +166,9 @@ def _case(nb, n_p, hit, seed, probed=0.7):
     pk = np.concatenate(parts)[:n_p]
     if n_p >= 16 and 0.0 < hit < 1.0:
         pk[:2] = np.array([0, 2**64 - 1], dtype=np.uint64)                # ... on the probe side too
+        pk[3:5] = np.array([keymix.EMPTY_RAW, keymix.FILLER_RAW], dtype=np.uint64)
         if nb >= 40:
-            pk[2] = bk[2]                                                 # a duplicated key is matched for certain
+            pk[2] = bk[4]                                                 # a duplicated key is matched for certain
     rng.shuffle(pk)
     return bk, bv, pk
 

@@ -13,6 +13,7 @@ import re
 import numpy as np
 import pytest
 
+import keymix
 from conftest import ROOT
 
 U64_MAX = np.uint64(2**64 - 1)
@@ -189,15 +190,20 @@ def fj():
 
 def _mm_case(nb, dom, npk):
     """The input family of test_many_to_many_extension_matches_the_numpy_oracle (tests/test_gpu_parity.py): duplicates on both
-    sides, about half of the probe rows without a partner, 2^64 - 1 (the tables' empty marker) and 0 as duplicated keys."""
+    sides, about half of the probe rows without a partner; raw 2^64 - 1 (the HBM table's empty marker, an ordinary key in the hash
+    domain), 0, the LDS tables' empty marker (keymix.EMPTY_RAW) and the wide kernel's filler as duplicated keys."""
     rng = np.random.default_rng(nb + 7)
     ids = rng.integers(0, dom, size=nb, dtype=np.uint64)
     bk = ids * GOLDEN
     bk[ids == 1] = U64_MAX
+    bk[ids == 2] = keymix.EMPTY_RAW
+    bk[ids == 3] = keymix.FILLER_RAW
     bv = np.arange(nb, dtype=np.uint64) + np.uint64(5 * 10**12)               # value = row id: every row distinguishable
     pids = rng.integers(0, 2 * dom + 1, size=npk, dtype=np.uint64)
     pk = pids * GOLDEN
     pk[pids == 1] = U64_MAX
+    pk[pids == 2] = keymix.EMPTY_RAW
+    pk[pids == 3] = keymix.FILLER_RAW
     return bk, bv, pk
 
 

@@ -13,6 +13,7 @@ import zlib
 import numpy as np
 import pytest
 
+import keymix
 from conftest import ROOT
 
 U64_MAX = np.uint64(2**64 - 1)
@@ -136,15 +137,16 @@ def _case(nb, n_p, hit, seed):
     rng = np.random.default_rng(seed)
     bk = rng.integers(0, 2**64, size=nb, dtype=np.uint64)
     if nb >= 8:
-        bk[0], bk[1] = 0, U64_MAX                                         # the empty marker and zero
+        bk[0], bk[1] = 0, U64_MAX                                         # raw zero and raw 2^64 - 1: the HBM table's empty marker (an ordinary key in the hash domain)
+        bk[2], bk[3] = keymix.EMPTY_RAW, keymix.FILLER_RAW                # the LDS tables' empty marker and the wide kernel's filler (mixed 2^64 - 1, 2^32 - 1)
         d = max(1, nb // 20)
-        bk[nb - d:] = bk[2:2 + d]                                         # duplicated build keys
+        bk[nb - d:] = bk[4:4 + d]                                         # duplicated build keys
     nhit = int(n_p * hit) if nb else 0
     parts = [rng.choice(bk, nhit)] if nhit else []
     parts.append(rng.integers(1, 2**63, size=n_p - nhit, dtype=np.uint64) * np.uint64(2) + np.uint64(2**63))   # ~never a build key
     pk = np.concatenate(parts)[:n_p] if parts else np.empty(0, np.uint64)
     if n_p >= 16 and 0.0 < hit < 1.0:
-        pk[:2] = np.array([0, 2**64 - 1], dtype=np.uint64)                # ... on the probe side too
+        pk[:4] = np.array([0, 2**64 - 1, keymix.EMPTY_RAW, keymix.FILLER_RAW], dtype=np.uint64)   # ... on the probe side too
     rng.shuffle(pk)
     return bk, pk
 
