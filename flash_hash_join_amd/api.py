@@ -93,7 +93,8 @@ def trim_workspace(device: Optional[int] = None) -> None:
 
 
 def set_option(name: str, value: int) -> None:
-    """Process-wide dispatch option of the native library: "radix_threshold", "scalar_hbm_table" (include/flashjoin.h)."""
+    """Process-wide dispatch option of the native library: "radix_threshold", "scalar_hbm_table", "mm_heavy_keys", ...
+    (the list: include/flashjoin.h)."""
     check(_lib.load().fj_set_option(name.encode(), int(value)))
 
 
@@ -401,12 +402,15 @@ def hash_join_count_bloom(build_keys, build_values, probe_keys):
 # ---- extension: many-to-many inner join (the reference deduplicates build keys, hash_join.cpp:125) -------------------
 def inner_join_count(build_keys, build_values, probe_keys):
     """Number of (probe row, build row) pairs with equal keys - every duplicate build row counts (SQL inner join).
-    Not part of the reference's API; same argument and return conventions as the other joins."""
+    Not part of the reference's API; same argument and return conventions as the other joins.
+    A final partition of more than 4096 build rows (a key with thousands of copies) is refused unless
+    set_option("mm_heavy_keys", 1): then it is joined in tiles of at most 4096 build rows."""
     return _join(ALGO_RADIX | ALGO_MANY_TO_MANY, 0, 0, build_keys, build_values, probe_keys, False)
 
 
 def inner_join(build_keys, build_values, probe_keys, return_arrays: bool = False):
-    """Materialises every (probe_key, build_value) pair of the many-to-many inner join; `return_arrays=True` returns them."""
+    """Materialises every (probe_key, build_value) pair of the many-to-many inner join; `return_arrays=True` returns them.
+    Build keys with thousands of copies need set_option("mm_heavy_keys", 1) (inner_join_count)."""
     return _join(ALGO_RADIX | ALGO_MANY_TO_MANY, 0, 1, build_keys, build_values, probe_keys, return_arrays)
 
 
@@ -527,6 +531,8 @@ def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool 
     how="full"   (P, u, r, seconds, probe_idx, build_idx): P + u + r rows - those, then the r build rows whose key is not among
                  the probe keys with probe_idx == -1.
     how="inner"  the same as many_to_many=True; how="semi" / "anti": as without it (multiplicity does not matter to them).
+    A final partition of more than 4096 build rows is refused by the many-to-many forms; set_option("mm_heavy_keys", 1) lifts that
+    for how="inner" (many_to_many=True or duplicates="all"), not for duplicates="all" with how="left" / "full".
     The index arrays are int64: NumPy for host inputs, torch.int64 on the inputs' device for device tensors / DLPack."""
     if how not in _HOW:
         raise ValueError(f"join_indices: how must be one of {sorted(_HOW)}, got {how!r}")

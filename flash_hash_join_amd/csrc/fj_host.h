@@ -86,6 +86,7 @@ enum Slot {
     W_PK_FI, W_PK_BKEYS, W_PK_OBASE,                                   // fj_shuffle_pack_*: output-chunk index, keys per bucket, output chunks before a bucket
     W_RX_REL, W_RX_LIST, W_RX_SEGOFF, W_RX_BCH, W_RX_BOFF, W_RX_TOFF, W_RX_TILES,   // a received piece as a chunk set
     W_SK_TILES_B, W_SK_TILES_P, W_SK_NT, W_PART_COUNT2, W_OUT_OFF2,                 // re-partitioning of oversized final partitions (skew_join)
+    W_MM_TILES,                                                                     // many-to-many join, option "mm_heavy_keys": the (probe item, build tile) items of oversized partitions (their counts and offsets: W_PART_COUNT2, W_OUT_OFF2)
     W_FULL_BITS,                                                                    // full outer join: matched bits of the build rows / of the global table's slots
     W_NSLOTS
 };
@@ -108,6 +109,8 @@ struct Pending {
     u32 nitems = 0, gt_grid = 0;
     u64 count = 0;
     // oversized partitions that skew_join re-partitioned: their sub-partitions are a second item set, emitted behind the first
+    // (MANY, inner form under the option "mm_heavy_keys": the (probe item, build tile) items of partitions beyond 4096 build rows are
+    //  the second set - has_second, lds2, nitems2, count_main; the flagged items' counts are zeroed when the set is made)
     bool has_second = false; FjLdsJoinArgs lds2{}; u32 nitems2 = 0; u64 count_main = 0; std::vector<u32> flagged;
     bool dups_main = false; std::vector<u32> sk_parts; int sk_bits = 0, sk_plan_bits = 0, sk_npass = 0;     // ... which partitions, by how many more bits (the first-occurrence emit path repeats it with row indices)
     // MANY, outer forms (FJ_ALGO_ALL_COPIES; mm_outer != FJ_MM_INNER): `count` is P + u + r; the emit scans the misses per item too, writes
@@ -246,6 +249,7 @@ struct Options {
     int join_wide = 2;                 // counting joins on the bucketed 16384-slot table (fj_join_wide.hip): 0 never, 1 whenever eligible, 2 (default) when at most ~3 probe rows per build row reach the join (wide_join_planned)
     u32 lab_hooks = 0;                 // FJ_HOOK_* bits
     u32 join_items_target = 2048;      // work items the join of a plan with few partitions is cut into (tuning knob)
+    int mm_heavy_keys = 0;             // many-to-many inner join: 0 (default) a final partition of more than 4096 build rows is refused; 1 it is joined in tiles of <= 4096 build rows (join_many, fj_mm_tile_kernel).  The outer forms (FJ_ALGO_ALL_COPIES) refuse either way
     Options();                         // initial values: FJ_OPTIONS="name=value,name=value" (the names of fj_set_option), the ONE environment variable behind all of them
 };
 Options& options();

@@ -168,7 +168,7 @@ struct FjLdsJoinArgs {
     unsigned long long* out_cursor;
     u64 out_capacity;
     u32 retry_only;              // tagged-table counting kernel: process only the items the cuckoo kernel marked FJ_ITEM_RETRY
-    u32 mark_toobig;             // tagged-table counting kernel: a partition beyond the table marks its item FJ_ITEM_TOOBIG (FJ_STAT_TOOBIG) instead of raising FJ_ERR_LDS_FULL
+    u32 mark_toobig;             // tagged-table counting kernel, many-to-many counting kernel (inner form): a partition beyond the table marks its item FJ_ITEM_TOOBIG (FJ_STAT_TOOBIG) instead of raising FJ_ERR_LDS_FULL
     u32 want_dups;               // counting pass of a materialising join: report duplicate build keys (FJ_STAT_DUPS)
     u32 dedup;                   // materialising pass: build 'values' are row indices, the smallest wins, then orig_vals[idx]
     const u64* orig_vals;        // the caller's build_values (dedup only)
@@ -229,6 +229,11 @@ struct FjMmOuterArgs {
     unsigned long long* marked;      // FULL, counting pass: device scalar, build rows whose bit this launch turned on (r = nb - marked)
 };
 hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer = FJ_MM_INNER, const FjMmOuterArgs* oa = nullptr);
+// the inner form over (probe item, build tile) work items of partitions beyond 4096 build rows (a.mark_toobig made the counting launch
+// above mark their items FJ_ITEM_TOOBIG): a.items[i] = {first probe list index, probe chunks, partition, first build chunk of the tile
+// within the partition's chunk list}, a tile = FJ_MM_TILE_CHUNKS chunks; exactly a.items_cap items (a.nitems_dev is not read)
+#define FJ_MM_TILE_CHUNKS 16u
+hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s);
 
 struct FjGtArgs {                // global (non-partitioned) table
     u64* tkeys; u64* tvals; u32* bloom;    // bloom == nullptr: no precheck

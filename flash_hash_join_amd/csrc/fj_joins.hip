@@ -78,7 +78,15 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
             if (get_buf(c, W_OUT_OFF, ((size_t)pd.nitems + 1) * 8, &p)) return 1;
             HIPCHK(fj_launch_scan_u32_to_u64(pd.lds.part_count, (u64*)p, pd.nitems, s));
             pd.lds.out_off = (const u64*)p; pd.lds.out_keys = d_ok; pd.lds.out_vals = d_ov;
-            if (pd.mm_outer == FJ_MM_INNER) HIPCHK(fj_launch_mm_join(pd.lds, true, s));
+            if (pd.mm_outer == FJ_MM_INNER) {
+                HIPCHK(fj_launch_mm_join(pd.lds, true, s));
+                if (pd.has_second) {            // second item set: the tiles of the partitions beyond 4096 build rows (mm_tile_join), behind the first set's pairs
+                    if (get_buf(c, W_OUT_OFF2, ((size_t)pd.nitems2 + 1) * 8, &p)) return 1;
+                    HIPCHK(fj_launch_scan_u32_to_u64(pd.lds2.part_count, (u64*)p, pd.nitems2, s));
+                    pd.lds2.out_off = (const u64*)p; pd.lds2.out_keys = d_ok + pd.count_main; pd.lds2.out_vals = d_ov + pd.count_main;
+                    HIPCHK(fj_launch_mm_tile_join(pd.lds2, true, s));
+                }
+            }
             else if (pd.mm_trivial) {               // an empty side: the other side's rows as they are (row ids: their positions beside UINT64_MAX)
                 const bool rid = pd.lds.row_ids != 0;
                 if (pd.mm_u) {
@@ -488,9 +496,57 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
     return 0;
 }
 
+// Many-to-many inner join, option "mm_heavy_keys": the counting launch marked the items whose partition holds more than 4096 build
+// rows (FJ_ITEM_TOOBIG; further radix bits cannot help: the copies of one key share every digit) and joined everything else.  Each
+// such item is cut into (probe item, build tile) work items, a tile being FJ_MM_TILE_CHUNKS consecutive entries of the partition's
+// build chunk list - at most 4096 rows whatever the chunks' fill.  Every pair is found exactly once, in the tile that holds its
+// build row, so the tiles' counts add to the same device total and - materialising - their pairs follow the first set's
+// (Pending::has_second, as skew_join's sub-partitions do for the N:1 joins).  Queues the tiles' counting launch, records E_JOIN
+// behind it and reads the scalars back.
+static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int materialize, hipStream_t s, Pending* pend) {
+    u32 nlive = 0;
+    std::vector<u32> pc(nitems), boff((size_t)ja.build.nb + 1);
+    std::vector<uint4> items(nitems);
+    HIPCHK(hipMemcpyAsync(&nlive, ja.nitems_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pc.data(), ja.part_count, (size_t)nitems * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(items.data(), ja.items, (size_t)nitems * sizeof(uint4), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(boff.data(), ja.build.boff, boff.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nlive > nitems) nlive = nitems;
+    std::vector<uint4> tiles;
+    for (u32 i = 0; i < nlive; ++i) {
+        if (pc[i] != FJ_ITEM_TOOBIG) continue;
+        pc[i] = 0;                                                   // the item emits nothing itself: its tiles do
+        const u32 part = items[i].z;
+        if (part >= ja.build.nb) return set_err("internal error: work item %u of a many-to-many join names partition %u of %u", i, part, ja.build.nb);
+        const u32 nbc = boff[part + 1] - boff[part];
+        for (u32 c_lo = 0; c_lo < nbc; c_lo += FJ_MM_TILE_CHUNKS) tiles.push_back(make_uint4(items[i].x, items[i].y, part, c_lo));
+    }
+    if (tiles.empty()) return set_err("internal error: the many-to-many counting pass reported an oversized partition and marked no item");
+    if (tiles.size() > (1u << 26)) return set_err("many-to-many join: %zu (probe item, build tile) work items for the partitions beyond 4096 build rows; not supported", tiles.size());
+    const u32 n2 = (u32)tiles.size();
+    void* p;
+    FjLdsJoinArgs j2 = ja;
+    if (get_buf(c, W_MM_TILES, (size_t)n2 * sizeof(uint4), &p)) return 1;
+    HIPCHK(hipMemcpyAsync(p, tiles.data(), (size_t)n2 * sizeof(uint4), hipMemcpyHostToDevice, s));
+    j2.items = (const uint4*)p; j2.nitems_dev = nullptr; j2.items_cap = n2; j2.mark_toobig = 0;
+    if (get_buf(c, W_PART_COUNT2, (size_t)n2 * 4, &p)) return 1;
+    j2.part_count = (u32*)p;
+    HIPCHK(hipMemcpyAsync(ja.part_count, pc.data(), (size_t)nlive * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, 4, s));                  // the first launch's status bits have been acted on
+    const u64 count_main = c->h_sc->total;                           // what the partitions that fit found
+    HIPCHK(fj_launch_mm_tile_join(j2, false, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;                                // (a synchronisation: `tiles` and `pc` live on this stack frame)
+    if (materialize) { pend->has_second = true; pend->lds2 = j2; pend->nitems2 = n2; pend->count_main = count_main; }
+    return 0;
+}
+
 // EXTENSION: many-to-many inner join on the partitioned plan (csrc/fj_many.hip).  Build relation first (with its values when
 // materialising), then the probe relation, then one workgroup per work item; no bloom stage, no fallback: a partition of
-// more than 4096 build rows is an error.
+// more than 4096 build rows is an error - unless the option "mm_heavy_keys" is 1 and the join is the inner form over chunk lists
+// (every plan with a partition pass): then such a partition is joined tile by tile (mm_tile_join), and only then anything more
+// than today's one counting launch is queued.
 // outer = FJ_MM_LEFT / FJ_MM_FULL (FJ_ALGO_ALL_COPIES, materialising): out_count points to three words - P pairs, r build rows without
 // a probe partner (LEFT: 0), u probe rows without a build partner; the pending result holds P + u + r rows.  The counting launch
 // keeps the misses per item beside the pairs per item and - FULL - marks the matched build rows (bitmap in W_FULL_BITS, kept for the
@@ -538,15 +594,22 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
             HIPCHK(hipMemsetAsync(oa.bits, 0, bit_bytes, s));
         }
     }
+    ja.mark_toobig = (outer == FJ_MM_INNER && options().mm_heavy_keys && ja.items && ja.build.list) ? 1u : 0u;
     HIPCHK(fj_launch_mm_join(ja, false, s, outer, &oa));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
+    bool tiled = false;
+    if ((c->h_sc->err & FJ_STAT_TOOBIG) && !(c->h_sc->err & (FJ_ERR_POOL | FJ_ERR_LDS_FULL))) {
+        if (mm_tile_join(c, ja, nitems, materialize, s, &c->pend)) return 1;
+        tiled = true;
+    }
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
     end_plan(c);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)
         return set_err("many-to-many join: a final partition holds more than 4096 build rows (a build key with thousands of duplicates?); not supported");
     *out_count = c->h_sc->total;
     plan_timings(c, plan, ja.nparts, evc, t);
+    if (tiled) t->lds_retries = FJ_LDS_RETRIES_MM_TILED;
     if (materialize) { c->pend.valid = true; c->pend.kind = Pending::MANY; c->pend.lds = ja; c->pend.nitems = nitems; c->pend.count = *out_count; }
     if (outer != FJ_MM_INNER) {
         const u64 P = c->h_sc->total, u = c->h_sc->expected, marked = outer == FJ_MM_FULL ? c->h_sc->bloom_survivors : 0;

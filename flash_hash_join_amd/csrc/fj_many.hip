@@ -21,6 +21,17 @@
 // empty-marker key's head), then walks its partition's build chunks once more and ORs the rows of hit slots into the per-build-row
 // bitmap in HBM - one 64-bit atomic per non-zero ballot of 64 rows, the scheme of fj_outer_join_kernel<.., FULL>; the bits an atomic
 // newly set are counted, so the launch also yields r = nb - marked rows.  fj_full_sweep_kernel appends the unmarked rows.
+//
+// Partitions of more than 4096 build rows (option "mm_heavy_keys" = 1, inner form only; more radix bits cannot split the copies of
+// one key): the counting launch marks such an item FJ_ITEM_TOOBIG instead of raising FJ_ERR_LDS_FULL, the host cuts it into
+// (probe item, build tile) work items - a tile = MT_CHUNKS consecutive chunks of the partition's build chunk list, at most 4096
+// rows - and fj_mm_tile_kernel joins each of them.  Every pair is found exactly once, in the tile that holds its build row: counts
+// add, outputs concatenate, no state crosses tiles.  A heavy key means few probe rows with thousands of partners each, so the tile
+// kernel does not walk chains: a counting sort by table slot (count, scan, place) turns a key's rows into one contiguous run of
+// values, a hit is (start, length), and the WORKGROUP writes a round's concatenated runs - thread j of a stride-1024 loop finds
+// its hit by binary search over the scanned lengths - so that consecutive lanes write consecutive output rows of both planes.
+// The outer forms keep refusing such a partition whatever the option says: a probe row's "no partner" verdict would have to be
+// combined across the build tiles (a per-probe-row bitmap and a sweep of its own) - the follow-up.
 #include "fj_internal.h"
 
 namespace {
@@ -103,7 +114,11 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
         }
     }
     __syncthreads();
-    if (hdr->full) {                                   // more rows than the LDS tables hold: the host reports it (no fallback for this extension)
+    if (hdr->full) {                                   // more rows than the LDS tables hold: the host reports it (no fallback for this extension) ...
+        if (!MAT && OUTER == FJ_MM_INNER && a.mark_toobig) {   // ... or - option "mm_heavy_keys" - joins the item tile by tile (fj_mm_tile_kernel)
+            if (tid == 0) { a.part_count[item] = FJ_ITEM_TOOBIG; atomicOr(a.err, FJ_STAT_TOOBIG); }
+            return;
+        }
         if (tid == 0) { atomicOr(a.err, FJ_ERR_LDS_FULL); if (!MAT) { a.part_count[item] = 0; if (OUTER) oa.miss_count[item] = 0; } }
         return;
     }
@@ -232,6 +247,179 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
     }
 }
 
+// ---- one (probe item, build tile) work item of an oversized partition: items[] = {first probe list index, probe chunks, partition,
+// first build chunk of the tile (relative to the partition's list)}; the grid is exactly items_cap workgroups ----
+constexpr u32 MT_CHUNKS = FJ_MM_TILE_CHUNKS;                  // build chunks per tile: whatever their fill, never more than MM_ROWS rows
+constexpr u32 MT_NOSLOT = 0xFFFFFFFFu;
+struct MtHdr { u32 wsum[MM_NT / 64]; unsigned long long cnt; u64 pad_; };
+// LDS: header, tkeys[MM_S], soff[MM_S + 4] (per slot: row count, then start, then - after the placing - end of the slot's run; entry
+// MM_S is the empty marker key's, which never enters the table), and for the emitting form rvals[MM_ROWS] (the values, run by run)
+// and a round's hits: hraw[MM_NT] (probe key / position), hsc[MM_NT] (inclusive scan of the lengths), hpk[MM_NT] (start | length << 16)
+constexpr u32 MT_LDS_COUNT = sizeof(MtHdr) + MM_S * 8 + (MM_S + 4) * 4;
+constexpr u32 MT_LDS_MAT = MT_LDS_COUNT + MM_ROWS * 8 + MM_NT * 8 + MM_NT * 4 + MM_NT * 4;
+static_assert(sizeof(MtHdr) % 16 == 0 && MT_LDS_COUNT % 16 == 0, "every carve offset is a multiple of 16 bytes");
+static_assert(MT_LDS_MAT <= 160 * 1024, "one workgroup's LDS on a CU");
+static_assert(MT_CHUNKS * FJ_CHUNK <= MM_ROWS && MM_S == 8 * MM_NT && MM_ROWS <= 0xFFFF, "the slot scan takes 8 slots per thread; start and length share a word");
+
+// inclusive scan of v over the workgroup, *total = the sum; one barrier inside, and the caller keeps another one between two calls
+__device__ __forceinline__ u32 mt_block_scan(u32 v, u32* wsum, u32 tid, u32 lane, u32* total) {
+    u32 inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const u32 y = __shfl_up(inc, d, 64); if ((int)lane >= d) inc += y; }
+    if (lane == 63) wsum[tid >> 6] = inc;
+    __syncthreads();
+    u32 before = 0, tot = 0;
+#pragma unroll
+    for (u32 w = 0; w < MM_NT / 64; ++w) { const u32 x = wsum[w]; tot += x; if (w < (tid >> 6)) before += x; }
+    *total = tot;
+    return inc + before;
+}
+
+template <bool MAT, bool RID = false>
+__global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    MtHdr* hdr = reinterpret_cast<MtHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(MtHdr));
+    u32* soff = reinterpret_cast<u32*>(tkeys + MM_S);
+    u64* rvals = reinterpret_cast<u64*>(soff + MM_S + 4);      // (MAT only, and what follows)
+    u64* hraw = rvals + MM_ROWS;
+    u32* hsc = reinterpret_cast<u32*>(hraw + MM_NT);
+    u32* hpk = hsc + MM_NT;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 item = blockIdx.x;
+    const uint4 it = a.items[item];
+    const u32 p = it.z, s_lo = it.x, s_hi = it.x + it.y;
+    const u32 b0 = a.build.boff[p], nbc = a.build.boff[p + 1] - b0;
+    const u32 c_lo = it.w, c_hi = nbc - c_lo < MT_CHUNKS ? nbc : c_lo + MT_CHUNKS;
+    if (c_lo >= nbc || s_lo >= s_hi) { if (!MAT && tid == 0) a.part_count[item] = 0; return; }
+    if (MAT && a.part_count[item] == 0) return;
+
+    for (u32 i = tid; i < MM_S; i += MM_NT) { tkeys[i] = FJ_EMPTY_KEY; soff[i] = 0; }
+    if (tid < 4) soff[MM_S + tid] = 0;
+    if (tid == 0) hdr->cnt = 0;
+    __syncthreads();
+
+    // ---- build, first sweep over the tile: find-or-insert the key, count the slot's rows ----
+    for (u32 cl0 = 0; cl0 < MT_CHUNKS; cl0 += MM_NT / FJ_CHUNK) {
+        const u32 c = c_lo + cl0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        if (c < c_hi) {
+            const u32 e = a.build.list[b0 + c];
+            if (off < FJ_LIST_CNT(e)) {
+                const u64 key = a.build.keys[(u64)FJ_LIST_ID(e) * FJ_CHUNK + off];      // (chunk pools hold mixed keys)
+                u32 slot = MM_S;
+                if (key != FJ_EMPTY_KEY) {
+                    u32 pos = FJ_HW2(key) & (MM_S - 1);
+                    for (;;) {                                      // <= 4096 distinct keys in 8192 slots: always terminates
+                        const u64 old = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+                        if (old == FJ_EMPTY_KEY || old == key) break;
+                        pos = (pos + 1) & (MM_S - 1);
+                    }
+                    slot = pos;
+                }
+                atomicAdd(&soff[slot], 1u);
+            }
+        }
+    }
+    __syncthreads();
+
+    if (MAT) {
+        // ---- counts -> starts (8 slots per thread; the empty marker's run comes last) ----
+        uint4* so4 = reinterpret_cast<uint4*>(soff);
+        uint4 x0 = so4[2 * tid], x1 = so4[2 * tid + 1];
+        const u32 sum = x0.x + x0.y + x0.z + x0.w + x1.x + x1.y + x1.z + x1.w;
+        u32 total;
+        u32 run = mt_block_scan(sum, hdr->wsum, tid, lane, &total) - sum;
+        u32 t;
+        t = x0.x; x0.x = run; run += t;  t = x0.y; x0.y = run; run += t;  t = x0.z; x0.z = run; run += t;  t = x0.w; x0.w = run; run += t;
+        t = x1.x; x1.x = run; run += t;  t = x1.y; x1.y = run; run += t;  t = x1.z; x1.z = run; run += t;  t = x1.w; x1.w = run; run += t;
+        so4[2 * tid] = x0; so4[2 * tid + 1] = x1;
+        if (tid == MM_NT - 1) soff[MM_S] = total;
+        __syncthreads();
+        // ---- second sweep: every row's value goes to the next free place of its slot's run; afterwards soff[slot] is the END of the
+        // run and the end of the slot before it (0 for slot 0) its start ----
+        for (u32 cl0 = 0; cl0 < MT_CHUNKS; cl0 += MM_NT / FJ_CHUNK) {
+            const u32 c = c_lo + cl0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            if (c < c_hi) {
+                const u32 e = a.build.list[b0 + c];
+                if (off < FJ_LIST_CNT(e)) {
+                    const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+                    const u64 key = a.build.keys[src];
+                    u32 slot = MM_S;
+                    if (key != FJ_EMPTY_KEY) {
+                        u32 pos = FJ_HW2(key) & (MM_S - 1);
+                        while (tkeys[pos] != key) pos = (pos + 1) & (MM_S - 1);       // (the first sweep put it there)
+                        slot = pos;
+                    }
+                    const u32 dst = atomicAdd(&soff[slot], 1u);
+                    if (dst < MM_ROWS) rvals[dst] = a.build.vals[src];                // (always: a tile holds <= MM_ROWS rows)
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- probe: one key per thread and round ----
+    const u64 obase = MAT ? a.out_off[item] : 0;
+    unsigned long long local = 0;
+    u32 written = 0;                                           // (MAT) pairs of the earlier rounds
+    for (u32 pc = s_lo; pc < s_hi; pc += MM_NT / FJ_CHUNK) {
+        const u32 c = pc + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        u64 key = 0, psrc = 0; bool ok = false;
+        if (c < s_hi) {
+            const u32 e = a.probe.list[c];
+            psrc = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            if (off < FJ_LIST_CNT(e)) { key = a.probe.keys[psrc]; ok = true; }
+        }
+        u32 slot = MT_NOSLOT;
+        if (ok) {
+            if (key == FJ_EMPTY_KEY) slot = MM_S;
+            else {
+                u32 pos = FJ_HW2(key) & (MM_S - 1);
+                for (;;) {
+                    const u64 t = tkeys[pos];
+                    if (t == key) { slot = pos; break; }
+                    if (t == FJ_EMPTY_KEY) break;
+                    pos = (pos + 1) & (MM_S - 1);
+                }
+            }
+        }
+        if (!MAT) { if (slot != MT_NOSLOT) local += soff[slot]; continue; }
+        u32 start = 0, len = 0;
+        if (slot != MT_NOSLOT) { start = slot ? soff[slot - 1] : 0u; len = soff[slot] - start; }
+        // ---- the round's hits as (start, length) beside the scanned lengths; then the workgroup writes the concatenated runs:
+        // output row j of the round belongs to the first hit whose inclusive scan exceeds j ----
+        u32 round_total;
+        const u32 incl = mt_block_scan(len, hdr->wsum, tid, lane, &round_total);
+        hsc[tid] = incl; hpk[tid] = start | (len << 16);
+        if (len) hraw[tid] = RID ? (a.probe.vals ? a.probe.vals[psrc] : psrc) : fj_key_unmix(key);
+        __syncthreads();
+        for (u32 j = tid; j < round_total; j += MM_NT) {
+            u32 lo = 0;
+#pragma unroll
+            for (u32 w = MM_NT / 2; w; w >>= 1) if (hsc[lo + w - 1] <= j) lo += w;      // lo = hits whose scan is <= j (< MM_NT: the last scan is round_total > j)
+            const u32 pk2 = hpk[lo];
+            const u32 k = j - (hsc[lo] - (pk2 >> 16));
+            const u64 o = obase + written + j;
+            a.out_keys[o] = hraw[lo];
+            a.out_vals[o] = rvals[(pk2 & 0xFFFFu) + k];
+        }
+        written += round_total;
+        __syncthreads();
+    }
+    if (!MAT) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d, 64);
+        if (lane == 0 && local) atomicAdd(&hdr->cnt, local);
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long n = hdr->cnt;
+            if (n > 0xFFFFFFFFull) atomicOr(a.err, FJ_ERR_POOL);       // (cannot happen: <= 131072 probe rows x 4096 build rows per (item, tile))
+            a.part_count[item] = (u32)n;
+            if (n) atomicAdd(a.total, n);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer, const FjMmOuterArgs* oa) {
@@ -255,5 +443,16 @@ hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(MM_NT), lds, s, a, o);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s) {
+    if (!a.items || !a.items_cap || !a.build.list || !a.probe.list || !a.part_count) return hipErrorInvalidValue;
+    if (materialize && (!a.out_off || !a.out_keys || !a.out_vals || !a.build.vals)) return hipErrorInvalidValue;
+    const u32 lds = materialize ? MT_LDS_MAT : MT_LDS_COUNT;
+    auto kern = materialize ? (a.row_ids ? fj_mm_tile_kernel<true, true> : fj_mm_tile_kernel<true>) : fj_mm_tile_kernel<false>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(a.items_cap), dim3(MM_NT), lds, s, a);
     return hipGetLastError();
 }

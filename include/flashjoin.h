@@ -35,7 +35,9 @@ extern "C" {
 /* EXTENSION (no reference counterpart: the reference deduplicates build keys, hash_join.cpp:125): OR this into `algo` for a
  * many-to-many inner join - every build row is kept, a probe row yields one pair per build row with its key, the count is the
  * number of pairs.  Partitioned plan only; fails when a final partition would hold more than 4096 build rows (a key with
- * thousands of duplicates).  `bloom` is ignored. */
+ * thousands of duplicates) - unless the option "mm_heavy_keys" is 1 (below): then such a partition is joined in tiles of at most
+ * 4096 build rows, in every form of the call (counting, one call with buffers, count + fj_emit_pairs, FJ_ALGO_ROW_IDS,
+ * fj_join_host).  `bloom` is ignored. */
 #define FJ_ALGO_MANY_TO_MANY 0x10
 /* EXTENSIONS (no reference counterpart; csrc/fj_outer.hip): OR one of these into `algo` together with a base value (ADAPTIVE, SCALAR
  * or RADIX: it picks the partitioned plan or the global HBM table exactly as for the inner join).  N:1 semantics as everywhere: a
@@ -88,7 +90,9 @@ extern "C" {
  * what FJ_ALGO_MANY_TO_MANY is to the inner join): a probe row yields one output row per build row with its key, and one row with
  * the filler when there is none.  materialize = 1 only.  Partitioned plan only, like FJ_ALGO_MANY_TO_MANY: the base value (ADAPTIVE,
  * SCALAR or RADIX) is accepted and never selects the HBM table, bloom is ignored, and a final partition of more than 4096 build rows
- * is refused with the same error (the context stays usable).
+ * is refused with the same error (the context stays usable) - whatever the option "mm_heavy_keys" says: it serves the inner form
+ * only.  (Across the build tiles of such a partition a probe row's "no partner" verdict would have to be combined - a bitmap per
+ * probe row and a sweep of its own: not built.)
  * With this flag out_count points to THREE words, for both forms: out_count[0] = P, the matched pairs (what the many-to-many inner
  * join counts), out_count[1] = r, the build rows whose key no probe row has (0 with FJ_ALGO_LEFT_OUTER), out_count[2] = u, the probe
  * rows without a partner (what the counting anti join returns).  P + u + r rows are written, in three ranges:
@@ -124,7 +128,11 @@ typedef struct fj_timings {
     uint64_t partitions;
     int overlapped;              /* always 0: build_phase_ms and probe_phase_ms are disjoint intervals (the two-stream schedules of
                                     rounds 1-2 are gone; the field keeps the struct layout)                              */
-    int lds_retries;             /* 1 if some partitions overflowed the counting join's cuckoo table and were redone on the tagged table */
+    int lds_retries;             /* 1 if some partitions overflowed the counting join's cuckoo table and were redone on the tagged table;
+                                    1 + n if n oversized partitions were re-partitioned alone; FJ_LDS_RETRIES_MM_TILED (no other path
+                                    reports it) if a many-to-many join ran partitions of more than 4096 build rows tile by tile
+                                    (option "mm_heavy_keys") */
+#define FJ_LDS_RETRIES_MM_TILED 4096
     /* bloom precheck of the partitioned plan (the *_bloom functions): */
     double filter_ms;            /* the filter kernel between the probe side's passes (part of probe_phase_ms)              */
     uint64_t filter_survivors;   /* probe keys that passed it (hits + false positives); 0 when bloom_level == 0             */
@@ -175,6 +183,10 @@ int fj_abi_version(void);
  *   "join_wide"        - counting joins on the bucketed 16384-slot LDS table kernel (csrc/fj_join_wide.hip): 0 never, 1 whenever
  *                        eligible, 2 (default) when at most ~3 probe rows per build row reach the join (behind a filter: an estimate).
  *   "join_items_target" - work items the join of a plan with few partitions is cut into (default 2048; a tuning knob).
+ *   "mm_heavy_keys"    - many-to-many inner join (FJ_ALGO_MANY_TO_MANY): 0 (default) a final partition of more than 4096 build rows
+ *                        is refused; 1 it is joined in tiles of at most 4096 build rows, so that a build key may have any number of
+ *                        copies (a join without such a partition launches nothing more than with 0).  Other values are refused.
+ *                        The outer forms (FJ_ALGO_ALL_COPIES) refuse such a partition at either setting.
  *   "lab_hooks"        - test / measurement hooks, one bit each (csrc/fj_host.h FJ_HOOK_*; default 0): 1 a rank's own share of a
  *                        multi-GPU exchange travels through ncclSend / ncclRecv too, 2 injected failure of a local append, 4 split a
  *                        1-rank communicator, 8 one communicator, 16 the CU reserve on one rank too, 32 emitting pass on the tagged
