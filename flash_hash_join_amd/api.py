@@ -93,8 +93,10 @@ def trim_workspace(device: Optional[int] = None) -> None:
 
 
 def set_option(name: str, value: int) -> None:
-    """Process-wide dispatch option of the native library: "radix_threshold", "scalar_hbm_table", "mm_heavy_keys", ...
-    (the list: include/flashjoin.h)."""
+    """Process-wide dispatch option of the native library: "radix_threshold", "scalar_hbm_table", "mm_heavy_keys",
+    "mm_heavy_outer", ... (the list: include/flashjoin.h).  "mm_heavy_keys" = 1 lets the many-to-many INNER join take a build key with
+    thousands of copies; "mm_heavy_outer" = 1 does the same for left_join / full_join / join_indices with duplicates="all".  The two
+    are independent, both default to 0 and accept only 0 and 1."""
     check(_lib.load().fj_set_option(name.encode(), int(value)))
 
 
@@ -439,8 +441,8 @@ def left_join(build_keys, build_values, probe_keys, return_arrays: bool = False,
 
     duplicates="all" (SQL semantics; "first" is the N:1 rule above): a probe row yields one row per build row with its key.  Returns
     (P, u, seconds) or (P, u, seconds, keys, values): P pairs (what inner_join_count returns), u probe rows without a partner (what
-    anti_join_count returns); P + u rows, `fill_value` in rows [P, P + u).  A build key with thousands of copies is refused, as by
-    inner_join."""
+    anti_join_count returns); P + u rows, `fill_value` in rows [P, P + u).  A build key with thousands of copies (a final partition
+    of more than 4096 build rows) is refused unless set_option("mm_heavy_outer", 1): then that partition is joined in tiles."""
     if _all_copies(duplicates, "left_join"):
         res = _join(ALGO_ADAPTIVE | ALGO_LEFT_OUTER | ALGO_ALL_COPIES, 0, 1, build_keys, build_values, probe_keys, return_arrays)
         (P, _, u), sec = res[0], res[1]
@@ -476,7 +478,8 @@ def full_join(build_keys, build_values, probe_keys, return_arrays: bool = False,
 
     duplicates="all" (SQL semantics): every copy of a duplicated build key pairs with the probe rows of its key.  Returns
     (P, u, r, seconds) or (P, u, r, seconds, keys, values) with P + u + r rows: rows [0, P) the pairs, rows [P, P + u) the unmatched
-    probe keys with `fill_value`, rows [P + u, P + u + r) the build rows whose key is not among the probe keys."""
+    probe keys with `fill_value`, rows [P + u, P + u + r) the build rows whose key is not among the probe keys.  A build key with
+    thousands of copies is refused unless set_option("mm_heavy_outer", 1) (left_join)."""
     if _all_copies(duplicates, "full_join"):
         res = _join(ALGO_ADAPTIVE | ALGO_FULL_OUTER | ALGO_ALL_COPIES, 0, 1, build_keys, build_values, probe_keys, return_arrays)
         (P, r, u), sec = res[0], res[1]
@@ -532,7 +535,8 @@ def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool 
                  the probe keys with probe_idx == -1.
     how="inner"  the same as many_to_many=True; how="semi" / "anti": as without it (multiplicity does not matter to them).
     A final partition of more than 4096 build rows is refused by the many-to-many forms; set_option("mm_heavy_keys", 1) lifts that
-    for how="inner" (many_to_many=True or duplicates="all"), not for duplicates="all" with how="left" / "full".
+    for how="inner" (many_to_many=True or duplicates="all"), set_option("mm_heavy_outer", 1) for duplicates="all" with
+    how="left" / "full"; the two options are independent.
     The index arrays are int64: NumPy for host inputs, torch.int64 on the inputs' device for device tensors / DLPack."""
     if how not in _HOW:
         raise ValueError(f"join_indices: how must be one of {sorted(_HOW)}, got {how!r}")

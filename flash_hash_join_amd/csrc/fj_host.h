@@ -87,6 +87,9 @@ enum Slot {
     W_RX_REL, W_RX_LIST, W_RX_SEGOFF, W_RX_BCH, W_RX_BOFF, W_RX_TOFF, W_RX_TILES,   // a received piece as a chunk set
     W_SK_TILES_B, W_SK_TILES_P, W_SK_NT, W_PART_COUNT2, W_OUT_OFF2,                 // re-partitioning of oversized final partitions (skew_join)
     W_MM_TILES,                                                                     // many-to-many join, option "mm_heavy_keys": the (probe item, build tile) items of oversized partitions (their counts and offsets: W_PART_COUNT2, W_OUT_OFF2)
+                                                                                    // ... option "mm_heavy_outer": W_PART_COUNT2 and W_OUT_OFF2 hold the first set's misses, so one buffer here carries the tiles, the oversized
+                                                                                    // probe items, both sets' counts and both sets' offsets (mm_tile_join)
+    W_MM_PBITS,                                                                     // ... option "mm_heavy_outer": "found a partner in some tile" bits of the probe rows (one per row of the probe side's final chunk pool)
     W_FULL_BITS,                                                                    // full outer join: matched bits of the build rows / of the global table's slots
     W_NSLOTS
 };
@@ -116,6 +119,13 @@ struct Pending {
     // MANY, outer forms (FJ_ALGO_ALL_COPIES; mm_outer != FJ_MM_INNER): `count` is P + u + r; the emit scans the misses per item too, writes
     // them behind the P pairs and - mm_r > 0 - sweeps the build rows the counting pass left unmarked in mm.bits behind those
     int mm_outer = 0; FjMmOuterArgs mm{}; u64 mm_P = 0, mm_u = 0, mm_r = 0;
+    // ... under the option "mm_heavy_outer" with a partition beyond 4096 build rows (has_second, lds2, nitems2, count_main as for the inner
+    // form: the tiles' pairs follow the first set's, written by the inner tile kernel): the oversized probe items are a third item set, mm_sweep,
+    // whose rows without a partner in ANY tile fj_launch_mm_miss_sweep counted and writes.  The two sets share the range [P, P + u) in
+    // this order: the first set's mm_u_main misses at P + miss_off[item] (its emitting launch skips the oversized items: both their
+    // counts are 0), the sweep's behind them at P + mm_u_main + mm_sweep_off[item].  mm_tile_off / mm_sweep_off: where the emit scans
+    // the second and third sets' counts to (W_OUT_OFF2 holds the first set's miss offsets)
+    FjMmSweepArgs mm_sweep{}; u64 mm_u_main = 0; u64* mm_tile_off = nullptr; u64* mm_sweep_off = nullptr;
     bool mm_trivial = false; const u64* mm_pk = nullptr;        // ... one side was empty: no partitions, the emit copies the other side's rows (bk / bv below, mm_pk)
     // duplicate build keys seen by the counting pass: the emitting pass must pick the FIRST occurrence's value
     bool has_dups = false;
@@ -228,6 +238,9 @@ namespace fjh {
 //                      workgroup over the flat inputs), so the switch point is 0 (tools/sweep_adaptive.py).
 //   (schedule: build relation first, then the probe relation, on the caller's stream.  The two-stream and interleaved
 //    schedules of rounds 1-2 were measured slower once the level bookkeeping was fused - EXPERIMENTS.md - and are gone.)
+//   mm_heavy_keys / mm_heavy_outer : a final partition of more than 4096 build rows in a many-to-many join - inner form / all-copies
+//                      outer forms: 0 (default) refused, 1 joined in tiles (join_many, mm_tile_join).  Independent of each other; two
+//                      options only because the outer forms' refusal at mm_heavy_keys = 1 is pinned behaviour.
 //   persistent_min_items : counting joins with at least this many (partition, slice) items run the persistent join
 //                      kernel (resident workgroups that prefetch the next item); below it one workgroup per item.
 //   scalar_hbm_table : 1 = the reference's "scalar" functions (hash_join*, one table for the whole build side) use the
@@ -250,6 +263,7 @@ struct Options {
     u32 lab_hooks = 0;                 // FJ_HOOK_* bits
     u32 join_items_target = 2048;      // work items the join of a plan with few partitions is cut into (tuning knob)
     int mm_heavy_keys = 0;             // many-to-many inner join: 0 (default) a final partition of more than 4096 build rows is refused; 1 it is joined in tiles of <= 4096 build rows (join_many, fj_mm_tile_kernel).  The outer forms (FJ_ALGO_ALL_COPIES) refuse either way
+    int mm_heavy_outer = 0;            // the same for the all-copies outer forms (FJ_ALGO_ALL_COPIES with LEFT_OUTER / FULL_OUTER): 0 (default) refused, 1 joined in tiles, the probe rows' "no partner" verdicts combined across the tiles (mm_tile_join, fj_mm_miss_sweep_kernel).  Independent of mm_heavy_keys; two options only because tests pin the outer forms' refusal at mm_heavy_keys = 1
     Options();                         // initial values: FJ_OPTIONS="name=value,name=value" (the names of fj_set_option), the ONE environment variable behind all of them
 };
 Options& options();

@@ -168,7 +168,7 @@ struct FjLdsJoinArgs {
     unsigned long long* out_cursor;
     u64 out_capacity;
     u32 retry_only;              // tagged-table counting kernel: process only the items the cuckoo kernel marked FJ_ITEM_RETRY
-    u32 mark_toobig;             // tagged-table counting kernel, many-to-many counting kernel (inner form): a partition beyond the table marks its item FJ_ITEM_TOOBIG (FJ_STAT_TOOBIG) instead of raising FJ_ERR_LDS_FULL
+    u32 mark_toobig;             // tagged-table counting kernel, many-to-many counting kernel (every form): a partition beyond the table marks its item FJ_ITEM_TOOBIG (FJ_STAT_TOOBIG) instead of raising FJ_ERR_LDS_FULL
     u32 want_dups;               // counting pass of a materialising join: report duplicate build keys (FJ_STAT_DUPS)
     u32 dedup;                   // materialising pass: build 'values' are row indices, the smallest wins, then orig_vals[idx]
     const u64* orig_vals;        // the caller's build_values (dedup only)
@@ -227,13 +227,35 @@ struct FjMmOuterArgs {
     u64 miss_base;                   // emitting pass: first row of the misses' range (P, the number of pairs)
     u64* bits;                       // FULL, counting pass
     unsigned long long* marked;      // FULL, counting pass: device scalar, build rows whose bit this launch turned on (r = nb - marked)
+    u64* pbits;                      // tile kernel, counting pass of LEFT and FULL: one bit per row of the PROBE side's final chunk pool (indexed as `bits`
+                                     // indexes the build pool), zeroed before the launch; a probe row that finds a partner in a tile sets its bit
 };
 hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer = FJ_MM_INNER, const FjMmOuterArgs* oa = nullptr);
-// the inner form over (probe item, build tile) work items of partitions beyond 4096 build rows (a.mark_toobig made the counting launch
+// the same over (probe item, build tile) work items of partitions beyond 4096 build rows (a.mark_toobig made the counting launch
 // above mark their items FJ_ITEM_TOOBIG): a.items[i] = {first probe list index, probe chunks, partition, first build chunk of the tile
-// within the partition's chunk list}, a tile = FJ_MM_TILE_CHUNKS chunks; exactly a.items_cap items (a.nitems_dev is not read)
+// within the partition's chunk list}, a tile = FJ_MM_TILE_CHUNKS chunks; exactly a.items_cap items (a.nitems_dev is not read).
+// outer = FJ_MM_LEFT / FJ_MM_FULL, counting pass only (the pairs of an outer form are emitted by the inner form: a pair lives in one
+// tile): a probe row that finds a partner in the tile sets its bit in oa->pbits - "no partner" is a verdict over ALL tiles of the
+// partition, fj_launch_mm_miss_sweep reads it off the bitmap afterwards - and FULL marks the tile's matched build rows in oa->bits and
+// adds the newly set bits to oa->marked, as fj_launch_mm_join's FULL form does (miss_count, miss_total, miss_off are not read)
 #define FJ_MM_TILE_CHUNKS 16u
-hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s);
+hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer = FJ_MM_INNER, const FjMmOuterArgs* oa = nullptr);
+// the probe rows of the oversized items that no tile gave a partner: one workgroup per item of items[] = {first probe list index, probe
+// chunks, -, -} (the items the counting launch marked FJ_ITEM_TOOBIG, nothing else: the cost follows them, not the probe side).
+// Counting: miss_count[i] = rows of item i whose bit in pbits is zero, their sum added to *miss_total.  Emitting: the same rows as
+// (probe key, 0) - row ids: (probe position, ~0) - at miss_base + miss_off[i] + rank within the item
+struct FjMmSweepArgs {
+    FjChunkSet probe;
+    const uint4* items; u32 nitems;
+    const u64* pbits;
+    u32* miss_count;                 // [nitems]
+    unsigned long long* miss_total;  // counting
+    const u64* miss_off;             // emitting: [nitems + 1] exclusive scan of miss_count
+    u64 miss_base;
+    u64* out_keys; u64* out_vals;
+    u32 row_ids;
+};
+hipError_t fj_launch_mm_miss_sweep(const FjMmSweepArgs& w, bool materialize, hipStream_t s);
 
 struct FjGtArgs {                // global (non-partitioned) table
     u64* tkeys; u64* tvals; u32* bloom;    // bloom == nullptr: no precheck

@@ -103,6 +103,17 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
                 HIPCHK(fj_launch_scan_u32_to_u64(pd.mm.miss_count, (u64*)p, pd.nitems, s));
                 pd.mm.miss_off = (const u64*)p; pd.mm.miss_base = pd.mm_P;
                 HIPCHK(fj_launch_mm_join(pd.lds, true, s, pd.mm_outer, &pd.mm));
+                if (pd.has_second) {
+                    // option "mm_heavy_outer": the tiles' pairs behind the first set's (the inner tile kernel: a pair lives in one tile),
+                    // then the oversized items' rows without a partner in any tile behind the first set's misses
+                    HIPCHK(fj_launch_scan_u32_to_u64(pd.lds2.part_count, pd.mm_tile_off, pd.nitems2, s));
+                    pd.lds2.out_off = pd.mm_tile_off; pd.lds2.out_keys = d_ok + pd.count_main; pd.lds2.out_vals = d_ov + pd.count_main;
+                    HIPCHK(fj_launch_mm_tile_join(pd.lds2, true, s));
+                    HIPCHK(fj_launch_scan_u32_to_u64(pd.mm_sweep.miss_count, pd.mm_sweep_off, pd.mm_sweep.nitems, s));
+                    pd.mm_sweep.miss_off = pd.mm_sweep_off; pd.mm_sweep.miss_base = pd.mm_P + pd.mm_u_main;
+                    pd.mm_sweep.out_keys = d_ok; pd.mm_sweep.out_vals = d_ov;
+                    HIPCHK(fj_launch_mm_miss_sweep(pd.mm_sweep, true, s));
+                }
                 if (pd.mm_r) {
                     HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));      // (the sweep's row cursor)
                     HIPCHK(fj_launch_full_sweep(pd.lds.build, pd.mm.bits, nullptr, pd.lds.row_ids, d_ok, d_ov, pd.mm_P + pd.mm_u, pd.count,
@@ -496,14 +507,20 @@ int join_radix(fj_ctx* c, int materialize, int bloom, const u64* bk, const u64* 
     return 0;
 }
 
-// Many-to-many inner join, option "mm_heavy_keys": the counting launch marked the items whose partition holds more than 4096 build
+// Many-to-many join, options "mm_heavy_keys" (inner form) and "mm_heavy_outer" (outer forms): the counting launch marked the items whose partition holds more than 4096 build
 // rows (FJ_ITEM_TOOBIG; further radix bits cannot help: the copies of one key share every digit) and joined everything else.  Each
 // such item is cut into (probe item, build tile) work items, a tile being FJ_MM_TILE_CHUNKS consecutive entries of the partition's
 // build chunk list - at most 4096 rows whatever the chunks' fill.  Every pair is found exactly once, in the tile that holds its
 // build row, so the tiles' counts add to the same device total and - materialising - their pairs follow the first set's
 // (Pending::has_second, as skew_join's sub-partitions do for the N:1 joins).  Queues the tiles' counting launch, records E_JOIN
 // behind it and reads the scalars back.
-static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int materialize, hipStream_t s, Pending* pend) {
+// outer = FJ_MM_LEFT / FJ_MM_FULL (oa: the first launch's arguments): a probe row of a marked item has no partner only if NO tile has
+// one for it.  The tiles' counting launch therefore sets a bit per probe row that found one (a bitmap over the probe side's final
+// chunk pool, W_MM_PBITS, allocated and zeroed only here) and - FULL - marks the tiles' matched build rows in oa->bits, adding to the
+// same `marked` scalar; fj_launch_mm_miss_sweep, one workgroup per MARKED item, then adds the rows whose bit stayed zero to the same
+// misses' total.  P, u and marked are read from the three device scalars they always came from.
+static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int materialize, hipStream_t s, Pending* pend,
+                        int outer = FJ_MM_INNER, const FjMmOuterArgs* oa = nullptr) {
     u32 nlive = 0;
     std::vector<u32> pc(nitems), boff((size_t)ja.build.nb + 1);
     std::vector<uint4> items(nitems);
@@ -513,10 +530,11 @@ static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int mate
     HIPCHK(hipMemcpyAsync(boff.data(), ja.build.boff, boff.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (nlive > nitems) nlive = nitems;
-    std::vector<uint4> tiles;
+    std::vector<uint4> tiles, big;
     for (u32 i = 0; i < nlive; ++i) {
         if (pc[i] != FJ_ITEM_TOOBIG) continue;
         pc[i] = 0;                                                   // the item emits nothing itself: its tiles do
+        if (outer != FJ_MM_INNER) big.push_back(items[i]);           // ... and the miss sweep (the counting launch left its miss count 0)
         const u32 part = items[i].z;
         if (part >= ja.build.nb) return set_err("internal error: work item %u of a many-to-many join names partition %u of %u", i, part, ja.build.nb);
         const u32 nbc = boff[part + 1] - boff[part];
@@ -527,25 +545,54 @@ static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int mate
     const u32 n2 = (u32)tiles.size();
     void* p;
     FjLdsJoinArgs j2 = ja;
-    if (get_buf(c, W_MM_TILES, (size_t)n2 * sizeof(uint4), &p)) return 1;
-    HIPCHK(hipMemcpyAsync(p, tiles.data(), (size_t)n2 * sizeof(uint4), hipMemcpyHostToDevice, s));
-    j2.items = (const uint4*)p; j2.nitems_dev = nullptr; j2.items_cap = n2; j2.mark_toobig = 0;
-    if (get_buf(c, W_PART_COUNT2, (size_t)n2 * 4, &p)) return 1;
-    j2.part_count = (u32*)p;
+    FjMmOuterArgs o2{};
+    FjMmSweepArgs sw{};
+    u64* tile_off = nullptr; u64* sweep_off = nullptr;
+    const u32 nbig = (u32)big.size();
+    if (outer == FJ_MM_INNER) {
+        if (get_buf(c, W_MM_TILES, (size_t)n2 * sizeof(uint4), &p)) return 1;
+        HIPCHK(hipMemcpyAsync(p, tiles.data(), (size_t)n2 * sizeof(uint4), hipMemcpyHostToDevice, s));
+        j2.items = (const uint4*)p; j2.nitems_dev = nullptr; j2.items_cap = n2; j2.mark_toobig = 0;
+        if (get_buf(c, W_PART_COUNT2, (size_t)n2 * 4, &p)) return 1;
+        j2.part_count = (u32*)p;
+    } else {
+        // one buffer, every section a multiple of 16 bytes: tiles | marked items | tiles' counts | marked items' miss counts | the two
+        // offset arrays the emit scans them to (W_PART_COUNT2 / W_OUT_OFF2 belong to the first set's misses in the outer forms)
+        auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        const size_t o_big = (size_t)n2 * sizeof(uint4), o_tc = o_big + (size_t)nbig * sizeof(uint4), o_sc = o_tc + r16((size_t)n2 * 4),
+                     o_to = o_sc + r16((size_t)nbig * 4), o_so = o_to + r16(((size_t)n2 + 1) * 8), bytes = o_so + r16(((size_t)nbig + 1) * 8);
+        if (get_buf(c, W_MM_TILES, bytes, &p)) return 1;
+        unsigned char* base = (unsigned char*)p;
+        HIPCHK(hipMemcpyAsync(base, tiles.data(), (size_t)n2 * sizeof(uint4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(base + o_big, big.data(), (size_t)nbig * sizeof(uint4), hipMemcpyHostToDevice, s));
+        j2.items = (const uint4*)base; j2.nitems_dev = nullptr; j2.items_cap = n2; j2.mark_toobig = 0;
+        j2.part_count = (u32*)(base + o_tc);
+        tile_off = (u64*)(base + o_to); sweep_off = (u64*)(base + o_so);
+        const size_t pbit_bytes = (size_t)ja.probe.cap * (FJ_CHUNK / 8);
+        if (get_buf(c, W_MM_PBITS, pbit_bytes, &p)) return 1;
+        HIPCHK(hipMemsetAsync(p, 0, pbit_bytes, s));
+        o2 = *oa; o2.pbits = (u64*)p;
+        sw.probe = ja.probe; sw.items = (const uint4*)(base + o_big); sw.nitems = nbig; sw.pbits = o2.pbits;
+        sw.miss_count = (u32*)(base + o_sc); sw.miss_total = oa->miss_total; sw.row_ids = ja.row_ids;
+    }
     HIPCHK(hipMemcpyAsync(ja.part_count, pc.data(), (size_t)nlive * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, 4, s));                  // the first launch's status bits have been acted on
-    const u64 count_main = c->h_sc->total;                           // what the partitions that fit found
-    HIPCHK(fj_launch_mm_tile_join(j2, false, s));
+    const u64 count_main = c->h_sc->total, u_main = c->h_sc->expected;       // what the partitions that fit found (outer forms: and their misses)
+    HIPCHK(fj_launch_mm_tile_join(j2, false, s, outer, &o2));
+    if (outer != FJ_MM_INNER) HIPCHK(fj_launch_mm_miss_sweep(sw, false, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;                                // (a synchronisation: `tiles` and `pc` live on this stack frame)
-    if (materialize) { pend->has_second = true; pend->lds2 = j2; pend->nitems2 = n2; pend->count_main = count_main; }
+    if (read_scalars(c, s)) return 1;                                // (a synchronisation: `tiles`, `big` and `pc` live on this stack frame)
+    if (materialize) {
+        pend->has_second = true; pend->lds2 = j2; pend->nitems2 = n2; pend->count_main = count_main;
+        if (outer != FJ_MM_INNER) { pend->mm_sweep = sw; pend->mm_u_main = u_main; pend->mm_tile_off = tile_off; pend->mm_sweep_off = sweep_off; }
+    }
     return 0;
 }
 
 // EXTENSION: many-to-many inner join on the partitioned plan (csrc/fj_many.hip).  Build relation first (with its values when
 // materialising), then the probe relation, then one workgroup per work item; no bloom stage, no fallback: a partition of
-// more than 4096 build rows is an error - unless the option "mm_heavy_keys" is 1 and the join is the inner form over chunk lists
-// (every plan with a partition pass): then such a partition is joined tile by tile (mm_tile_join), and only then anything more
+// more than 4096 build rows is an error - unless the form's option ("mm_heavy_keys": inner, "mm_heavy_outer": the outer forms) is 1
+// and the join runs over chunk lists (every plan with a partition pass): then such a partition is joined tile by tile (mm_tile_join), and only then anything more
 // than today's one counting launch is queued.
 // outer = FJ_MM_LEFT / FJ_MM_FULL (FJ_ALGO_ALL_COPIES, materialising): out_count points to three words - P pairs, r build rows without
 // a probe partner (LEFT: 0), u probe rows without a build partner; the pending result holds P + u + r rows.  The counting launch
@@ -594,13 +641,13 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
             HIPCHK(hipMemsetAsync(oa.bits, 0, bit_bytes, s));
         }
     }
-    ja.mark_toobig = (outer == FJ_MM_INNER && options().mm_heavy_keys && ja.items && ja.build.list) ? 1u : 0u;
+    ja.mark_toobig = ((outer == FJ_MM_INNER ? options().mm_heavy_keys : options().mm_heavy_outer) && ja.items && ja.build.list) ? 1u : 0u;
     HIPCHK(fj_launch_mm_join(ja, false, s, outer, &oa));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     bool tiled = false;
     if ((c->h_sc->err & FJ_STAT_TOOBIG) && !(c->h_sc->err & (FJ_ERR_POOL | FJ_ERR_LDS_FULL))) {
-        if (mm_tile_join(c, ja, nitems, materialize, s, &c->pend)) return 1;
+        if (mm_tile_join(c, ja, nitems, materialize, s, &c->pend, outer, &oa)) return 1;
         tiled = true;
     }
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");

@@ -22,16 +22,22 @@
 // bitmap in HBM - one 64-bit atomic per non-zero ballot of 64 rows, the scheme of fj_outer_join_kernel<.., FULL>; the bits an atomic
 // newly set are counted, so the launch also yields r = nb - marked rows.  fj_full_sweep_kernel appends the unmarked rows.
 //
-// Partitions of more than 4096 build rows (option "mm_heavy_keys" = 1, inner form only; more radix bits cannot split the copies of
-// one key): the counting launch marks such an item FJ_ITEM_TOOBIG instead of raising FJ_ERR_LDS_FULL, the host cuts it into
+// Partitions of more than 4096 build rows (option "mm_heavy_keys" = 1 for the inner form, "mm_heavy_outer" = 1 for the outer forms;
+// more radix bits cannot split the copies of one key): the counting launch marks such an item FJ_ITEM_TOOBIG instead of raising FJ_ERR_LDS_FULL, the host cuts it into
 // (probe item, build tile) work items - a tile = MT_CHUNKS consecutive chunks of the partition's build chunk list, at most 4096
 // rows - and fj_mm_tile_kernel joins each of them.  Every pair is found exactly once, in the tile that holds its build row: counts
 // add, outputs concatenate, no state crosses tiles.  A heavy key means few probe rows with thousands of partners each, so the tile
 // kernel does not walk chains: a counting sort by table slot (count, scan, place) turns a key's rows into one contiguous run of
 // values, a hit is (start, length), and the WORKGROUP writes a round's concatenated runs - thread j of a stride-1024 loop finds
 // its hit by binary search over the scanned lengths - so that consecutive lanes write consecutive output rows of both planes.
-// The outer forms keep refusing such a partition whatever the option says: a probe row's "no partner" verdict would have to be
-// combined across the build tiles (a per-probe-row bitmap and a sweep of its own) - the follow-up.
+// Outer forms over tiles (fj_mm_tile_kernel<false, false, FJ_MM_LEFT / FJ_MM_FULL>, counting pass only - the pairs are the inner form's,
+// counted and emitted as above): a probe row's "no partner" is a verdict over ALL tiles of its partition, so a tile records the
+// opposite - per round one ballot of "found a partner here" and one 64-bit atomicOr by lane 0 into a bitmap over the probe side's
+// final chunk pool (a wave covers 64 consecutive rows of one probe chunk).  fj_mm_miss_sweep_kernel, one workgroup per oversized
+// probe item, then counts (and, emitting, writes) the item's rows whose bit stayed zero.  FULL: the tile remembers the table slots
+// its probe rows hit (one bit per slot, one word for the empty marker's slot MM_S, behind soff) and walks its chunks once more to
+// OR the rows of hit slots into the per-build-row bitmap, counting the newly set bits - fj_mm_join_kernel<.., FULL>'s scheme on
+// the tile; the tiles of a partition hold disjoint rows, so r = nb - marked holds as before.
 #include "fj_internal.h"
 
 namespace {
@@ -115,8 +121,8 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
     }
     __syncthreads();
     if (hdr->full) {                                   // more rows than the LDS tables hold: the host reports it (no fallback for this extension) ...
-        if (!MAT && OUTER == FJ_MM_INNER && a.mark_toobig) {   // ... or - option "mm_heavy_keys" - joins the item tile by tile (fj_mm_tile_kernel)
-            if (tid == 0) { a.part_count[item] = FJ_ITEM_TOOBIG; atomicOr(a.err, FJ_STAT_TOOBIG); }
+        if (!MAT && a.mark_toobig) {                   // ... or - options "mm_heavy_keys" / "mm_heavy_outer" - joins the item tile by tile (fj_mm_tile_kernel)
+            if (tid == 0) { a.part_count[item] = FJ_ITEM_TOOBIG; if (OUTER) oa.miss_count[item] = 0; atomicOr(a.err, FJ_STAT_TOOBIG); }
             return;
         }
         if (tid == 0) { atomicOr(a.err, FJ_ERR_LDS_FULL); if (!MAT) { a.part_count[item] = 0; if (OUTER) oa.miss_count[item] = 0; } }
@@ -251,10 +257,12 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
 // first build chunk of the tile (relative to the partition's list)}; the grid is exactly items_cap workgroups ----
 constexpr u32 MT_CHUNKS = FJ_MM_TILE_CHUNKS;                  // build chunks per tile: whatever their fill, never more than MM_ROWS rows
 constexpr u32 MT_NOSLOT = 0xFFFFFFFFu;
-struct MtHdr { u32 wsum[MM_NT / 64]; unsigned long long cnt; u64 pad_; };
+struct MtHdr { u32 wsum[MM_NT / 64]; unsigned long long cnt; u32 marked, pad_; };     // marked: (FULL) build rows whose bit this work item turned on
 // LDS: header, tkeys[MM_S], soff[MM_S + 4] (per slot: row count, then start, then - after the placing - end of the slot's run; entry
 // MM_S is the empty marker key's, which never enters the table), and for the emitting form rvals[MM_ROWS] (the values, run by run)
-// and a round's hits: hraw[MM_NT] (probe key / position), hsc[MM_NT] (inclusive scan of the lengths), hpk[MM_NT] (start | length << 16)
+// and a round's hits: hraw[MM_NT] (probe key / position), hsc[MM_NT] (inclusive scan of the lengths), hpk[MM_NT] (start | length << 16);
+// the counting form of FULL keeps sbits[MM_SBITS_WORDS] behind soff instead: bit `slot` = a probe row of this work item hit the slot
+// (slot MM_S, the empty marker's, is bit 0 of word MM_S / 32)
 constexpr u32 MT_LDS_COUNT = sizeof(MtHdr) + MM_S * 8 + (MM_S + 4) * 4;
 constexpr u32 MT_LDS_MAT = MT_LDS_COUNT + MM_ROWS * 8 + MM_NT * 8 + MM_NT * 4 + MM_NT * 4;
 static_assert(sizeof(MtHdr) % 16 == 0 && MT_LDS_COUNT % 16 == 0, "every carve offset is a multiple of 16 bytes");
@@ -275,13 +283,17 @@ __device__ __forceinline__ u32 mt_block_scan(u32 v, u32* wsum, u32 tid, u32 lane
     return inc + before;
 }
 
-template <bool MAT, bool RID = false>
-__global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a) {
+// OUTER: FJ_MM_INNER, or - counting pass only - FJ_MM_LEFT / FJ_MM_FULL (oa.pbits; FULL: oa.bits, oa.marked)
+template <bool MAT, bool RID = false, int OUTER = FJ_MM_INNER>
+__global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a, FjMmOuterArgs oa) {
+    static_assert(!(MAT && OUTER != FJ_MM_INNER), "the verdicts and the marks belong to the counting pass; the inner form emits the pairs");
+    constexpr bool FULL = OUTER == FJ_MM_FULL;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MtHdr* hdr = reinterpret_cast<MtHdr*>(smem);
     u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(MtHdr));
     u32* soff = reinterpret_cast<u32*>(tkeys + MM_S);
     u64* rvals = reinterpret_cast<u64*>(soff + MM_S + 4);      // (MAT only, and what follows)
+    u32* sbits = soff + MM_S + 4;                              // (FULL only, in rvals' place)
     u64* hraw = rvals + MM_ROWS;
     u32* hsc = reinterpret_cast<u32*>(hraw + MM_NT);
     u32* hpk = hsc + MM_NT;
@@ -296,7 +308,8 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a) {
 
     for (u32 i = tid; i < MM_S; i += MM_NT) { tkeys[i] = FJ_EMPTY_KEY; soff[i] = 0; }
     if (tid < 4) soff[MM_S + tid] = 0;
-    if (tid == 0) hdr->cnt = 0;
+    if (FULL) for (u32 i = tid; i < MM_SBITS_WORDS; i += MM_NT) sbits[i] = 0;
+    if (tid == 0) { hdr->cnt = 0; if (FULL) hdr->marked = 0; }
     __syncthreads();
 
     // ---- build, first sweep over the tile: find-or-insert the key, count the slot's rows ----
@@ -383,6 +396,18 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a) {
                 }
             }
         }
+        if (!MAT && OUTER) {
+            // ---- the row's partners in this tile, and the verdict "found some" for the wave's 64 consecutive rows of probe chunk c
+            // (c is wave-uniform, lane 0's psrc is the first of them; a wave beyond the item's chunks has no ok lane) ----
+            static_assert(FJ_CHUNK % 64 == 0, "a wave covers 64 consecutive rows of one chunk");
+            const u32 n = slot != MT_NOSLOT ? soff[slot] : 0u;     // (the empty marker's slot MM_S is in every tile's table: 0 rows = no partner here)
+            local += n;
+            // (read first: most hits find their slot's bit set already and skip the LDS atomic)
+            if (FULL && n && !((sbits[slot >> 5] >> (slot & 31)) & 1u)) atomicOr(&sbits[slot >> 5], 1u << (slot & 31));
+            const u64 bal = __ballot(n != 0);
+            if (lane == 0 && bal) atomicOr((unsigned long long*)&oa.pbits[psrc >> 6], (unsigned long long)bal);
+            continue;
+        }
         if (!MAT) { if (slot != MT_NOSLOT) local += soff[slot]; continue; }
         u32 start = 0, len = 0;
         if (slot != MT_NOSLOT) { start = slot ? soff[slot - 1] : 0u; len = soff[slot] - start; }
@@ -417,6 +442,88 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_tile_kernel(FjLdsJoinArgs a) {
             a.part_count[item] = (u32)n;
             if (n) atomicAdd(a.total, n);
         }
+        if (FULL) {
+            // ---- the tile's build rows that this work item's probe rows found (the slot bits are complete: the barrier above);
+            // uniform control flow up to the ballot, one 64-bit atomic per non-zero ballot of 64 rows of one chunk ----
+            u32 newly = 0;                                 // (lane 0) bits this wave's atomics turned on
+            for (u32 cl0 = 0; cl0 < MT_CHUNKS; cl0 += MM_NT / FJ_CHUNK) {
+                const u32 c = c_lo + cl0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+                bool mt = false;
+                u64 src = 0;
+                if (c < c_hi) {
+                    const u32 e = a.build.list[b0 + c];
+                    src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+                    if (off < FJ_LIST_CNT(e)) {
+                        const u64 key = a.build.keys[src];
+                        u32 slot = MM_S;
+                        if (key != FJ_EMPTY_KEY) {
+                            u32 pos = FJ_HW2(key) & (MM_S - 1);
+                            while (tkeys[pos] != key) pos = (pos + 1) & (MM_S - 1);       // (the first sweep put it there)
+                            slot = pos;
+                        }
+                        mt = (sbits[slot >> 5] >> (slot & 31)) & 1u;
+                    }
+                }
+                const u64 bal = __ballot(mt);
+                if (lane == 0 && bal) {                      // another probe item of the partition may have set some of them already
+                    const u64 old = atomicOr((unsigned long long*)&oa.bits[src >> 6], (unsigned long long)bal);
+                    newly += (u32)__popcll(bal & ~old);
+                }
+            }
+            if (lane == 0 && newly) atomicAdd(&hdr->marked, newly);
+            __syncthreads();
+            if (tid == 0 && hdr->marked) atomicAdd(oa.marked, (unsigned long long)hdr->marked);
+        }
+    }
+}
+
+// ---- the "no partner" verdicts of the oversized probe items, read off the bitmap the tiles' counting pass filled: one workgroup per
+// item (w.items holds only the items marked FJ_ITEM_TOOBIG).  Counting: the item's rows whose bit is zero -> miss_count[item], their
+// sum -> *miss_total.  Emitting: the same rows as (probe key, 0) / (probe position, ~0) at miss_base + miss_off[item] + rank, rank from
+// ballot + popcount and one LDS cursor bump per wave (fj_mm_join_kernel's miss writer): consecutive lanes write consecutive rows ----
+template <bool MAT, bool RID = false>
+__global__ __launch_bounds__(MM_NT) void fj_mm_miss_sweep_kernel(FjMmSweepArgs w) {
+    static_assert(FJ_CHUNK % 64 == 0, "a wave covers 64 consecutive rows of one chunk");
+    __shared__ u32 cur;                                        // the item's misses (counting) / its miss cursor (emitting)
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 item = blockIdx.x;
+    const uint4 it = w.items[item];
+    const u32 s_lo = it.x, s_hi = it.x + it.y;
+    if (MAT && w.miss_count[item] == 0) return;
+    if (tid == 0) cur = 0;
+    __syncthreads();
+    const u64 mbase = MAT ? w.miss_base + w.miss_off[item] : 0;
+    u32 lmiss = 0;
+    for (u32 pc = s_lo; pc < s_hi; pc += MM_NT / FJ_CHUNK) {
+        const u32 c = pc + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        bool miss = false;
+        u64 psrc = 0;
+        if (c < s_hi) {
+            const u32 e = w.probe.list[c];
+            psrc = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            if (off < FJ_LIST_CNT(e)) miss = !((w.pbits[psrc >> 6] >> (psrc & 63)) & 1ull);
+        }
+        const u64 mbal = __ballot(miss);
+        if (!MAT) { lmiss += (u32)__popcll(mbal); continue; }
+        if (mbal) {
+            u32 wm = 0;
+            if (lane == 0) wm = atomicAdd(&cur, (u32)__popcll(mbal));
+            wm = __shfl(wm, 0, 64);
+            if (miss) {
+                const u64 o = mbase + wm + (u32)__popcll(mbal & ((1ull << lane) - 1ull));
+                w.out_keys[o] = RID ? (w.probe.vals ? w.probe.vals[psrc] : psrc) : fj_key_unmix(w.probe.keys[psrc]);      // (chunk pools hold mixed keys)
+                w.out_vals[o] = RID ? ~0ull : 0ull;
+            }
+        }
+    }
+    if (!MAT) {
+        if (lane == 0 && lmiss) atomicAdd(&cur, lmiss);
+        __syncthreads();
+        if (tid == 0) {
+            const u32 m = cur;
+            w.miss_count[item] = m;
+            if (m) atomicAdd(w.miss_total, (unsigned long long)m);
+        }
     }
 }
 
@@ -446,13 +553,30 @@ hipError_t fj_launch_mm_join(const FjLdsJoinArgs& a, bool materialize, hipStream
     return hipGetLastError();
 }
 
-hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s) {
+hipError_t fj_launch_mm_tile_join(const FjLdsJoinArgs& a, bool materialize, hipStream_t s, int outer, const FjMmOuterArgs* oa) {
     if (!a.items || !a.items_cap || !a.build.list || !a.probe.list || !a.part_count) return hipErrorInvalidValue;
     if (materialize && (!a.out_off || !a.out_keys || !a.out_vals || !a.build.vals)) return hipErrorInvalidValue;
-    const u32 lds = materialize ? MT_LDS_MAT : MT_LDS_COUNT;
+    u32 lds = materialize ? MT_LDS_MAT : MT_LDS_COUNT;
     auto kern = materialize ? (a.row_ids ? fj_mm_tile_kernel<true, true> : fj_mm_tile_kernel<true>) : fj_mm_tile_kernel<false>;
+    FjMmOuterArgs o{};
+    if (outer != FJ_MM_INNER) {                              // (counting pass only: the pairs of an outer form are emitted by the inner form)
+        if ((outer != FJ_MM_LEFT && outer != FJ_MM_FULL) || materialize || !oa || !oa->pbits) return hipErrorInvalidValue;
+        if (outer == FJ_MM_FULL && (!oa->bits || !oa->marked)) return hipErrorInvalidValue;
+        o = *oa;
+        kern = outer == FJ_MM_FULL ? fj_mm_tile_kernel<false, false, FJ_MM_FULL> : fj_mm_tile_kernel<false, false, FJ_MM_LEFT>;
+        if (outer == FJ_MM_FULL) lds += MM_SBITS_WORDS * 4;
+    }
+    static_assert(MT_LDS_COUNT + MM_SBITS_WORDS * 4 <= MT_LDS_MAT, "the outer counting forms stay below the emitting form's footprint");
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.items_cap), dim3(MM_NT), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.items_cap), dim3(MM_NT), lds, s, a, o);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_mm_miss_sweep(const FjMmSweepArgs& w, bool materialize, hipStream_t s) {
+    if (!w.items || !w.nitems || !w.probe.list || !w.probe.keys || !w.pbits || !w.miss_count) return hipErrorInvalidValue;
+    if (materialize ? (!w.miss_off || !w.out_keys || !w.out_vals) : !w.miss_total) return hipErrorInvalidValue;
+    auto kern = materialize ? (w.row_ids ? fj_mm_miss_sweep_kernel<true, true> : fj_mm_miss_sweep_kernel<true>) : fj_mm_miss_sweep_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(w.nitems), dim3(MM_NT), 0, s, w);
     return hipGetLastError();
 }

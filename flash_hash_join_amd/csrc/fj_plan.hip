@@ -432,6 +432,7 @@ static int set_option_value(Options& o, const char* name, long long value) {
     if (!strcmp(name, "lab_hooks")) { if (value < 0 || value > 0xFFFF) return set_err("fj_set_option: lab_hooks is a mask of FJ_HOOK_* bits"); o.lab_hooks = (u32)value; return 0; }
     if (!strcmp(name, "join_items_target")) { if (value < 1 || value > (1 << 20)) return set_err("fj_set_option: join_items_target must be 1..1048576"); o.join_items_target = (u32)value; return 0; }
     if (!strcmp(name, "mm_heavy_keys")) { if (value < 0 || value > 1) return set_err("fj_set_option: mm_heavy_keys must be 0 or 1"); o.mm_heavy_keys = (int)value; return 0; }
+    if (!strcmp(name, "mm_heavy_outer")) { if (value < 0 || value > 1) return set_err("fj_set_option: mm_heavy_outer must be 0 or 1"); o.mm_heavy_outer = (int)value; return 0; }
     return set_err("fj_set_option: unknown option '%s'", name);
 }
 
@@ -465,6 +466,7 @@ long long fj_get_option(const char* name) {
     if (name && !strcmp(name, "lab_hooks")) return o.lab_hooks;
     if (name && !strcmp(name, "join_items_target")) return o.join_items_target;
     if (name && !strcmp(name, "mm_heavy_keys")) return o.mm_heavy_keys;
+    if (name && !strcmp(name, "mm_heavy_outer")) return o.mm_heavy_outer;
     set_err("fj_get_option: unknown option '%s'", name ? name : "(null)");
     return -1;
 }

@@ -91,8 +91,9 @@ extern "C" {
  * the filler when there is none.  materialize = 1 only.  Partitioned plan only, like FJ_ALGO_MANY_TO_MANY: the base value (ADAPTIVE,
  * SCALAR or RADIX) is accepted and never selects the HBM table, bloom is ignored, and a final partition of more than 4096 build rows
  * is refused with the same error (the context stays usable) - whatever the option "mm_heavy_keys" says: it serves the inner form
- * only.  (Across the build tiles of such a partition a probe row's "no partner" verdict would have to be combined - a bitmap per
- * probe row and a sweep of its own: not built.)
+ * only - unless the option "mm_heavy_outer" is 1 (below): then such a partition is joined in tiles of at most 4096 build rows, in
+ * every form of the call, with the contract stated here.  (Across the build tiles a probe row's "no partner" verdict is combined in a
+ * bitmap per probe row, which a sweep over the oversized partitions' probe rows reads: csrc/fj_many.hip.)
  * With this flag out_count points to THREE words, for both forms: out_count[0] = P, the matched pairs (what the many-to-many inner
  * join counts), out_count[1] = r, the build rows whose key no probe row has (0 with FJ_ALGO_LEFT_OUTER), out_count[2] = u, the probe
  * rows without a partner (what the counting anti join returns).  P + u + r rows are written, in three ranges:
@@ -131,7 +132,7 @@ typedef struct fj_timings {
     int lds_retries;             /* 1 if some partitions overflowed the counting join's cuckoo table and were redone on the tagged table;
                                     1 + n if n oversized partitions were re-partitioned alone; FJ_LDS_RETRIES_MM_TILED (no other path
                                     reports it) if a many-to-many join ran partitions of more than 4096 build rows tile by tile
-                                    (option "mm_heavy_keys") */
+                                    (options "mm_heavy_keys", "mm_heavy_outer") */
 #define FJ_LDS_RETRIES_MM_TILED 4096
     /* bloom precheck of the partitioned plan (the *_bloom functions): */
     double filter_ms;            /* the filter kernel between the probe side's passes (part of probe_phase_ms)              */
@@ -186,7 +187,13 @@ int fj_abi_version(void);
  *   "mm_heavy_keys"    - many-to-many inner join (FJ_ALGO_MANY_TO_MANY): 0 (default) a final partition of more than 4096 build rows
  *                        is refused; 1 it is joined in tiles of at most 4096 build rows, so that a build key may have any number of
  *                        copies (a join without such a partition launches nothing more than with 0).  Other values are refused.
- *                        The outer forms (FJ_ALGO_ALL_COPIES) refuse such a partition at either setting.
+ *                        The outer forms (FJ_ALGO_ALL_COPIES) refuse such a partition at either setting of THIS option.
+ *   "mm_heavy_outer"   - the same for the all-copies outer joins (FJ_ALGO_ALL_COPIES with FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER):
+ *                        0 (default) a final partition of more than 4096 build rows is refused, message as ever; 1 it is joined in
+ *                        tiles of at most 4096 build rows (a join without such a partition launches nothing more than with 0).  Other
+ *                        values are refused.  Independent of "mm_heavy_keys", which keeps serving the inner form only: the two options
+ *                        exist side by side only because existing behaviour is pinned - the outer forms' refusal at "mm_heavy_keys" = 1
+ *                        and that option's refusal of any value but 0 and 1 are what callers and tests rely on today.
  *   "lab_hooks"        - test / measurement hooks, one bit each (csrc/fj_host.h FJ_HOOK_*; default 0): 1 a rank's own share of a
  *                        multi-GPU exchange travels through ncclSend / ncclRecv too, 2 injected failure of a local append, 4 split a
  *                        1-rank communicator, 8 one communicator, 16 the CU reserve on one rank too, 32 emitting pass on the tagged

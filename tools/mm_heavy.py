@@ -1,10 +1,14 @@
-"""The many-to-many inner join by the option "mm_heavy_keys" on device tensors, fixed seeds:
+"""The many-to-many inner join by the option "mm_heavy_keys" - and the all-copies outer joins by "mm_heavy_outer" - on device tensors, fixed seeds:
   a0 / a1   6M build rows over 3M ids x 5M probe rows (no partition beyond 4096 build rows) with the option 0 / 1
   b         one build key with 100 000 copies among 200 000 background rows, met by 50 probe rows of that key (about a's pair count)
   c         1M build rows with Zipf(1) key frequencies x 1500 probe rows of the same distribution
+A case name with the suffix .left or .full (a0.full, b.left, c.full, ...) runs left_join / full_join(duplicates="all") on the same input
+with "mm_heavy_outer" in the place of "mm_heavy_keys"; "rows" is then P + u + r and "pairs" P.  The yardstick of an outer case is the inner
+case of the same input in the same invocation (the untiled outer joins cost 1.06-1.35x their inner join, EXPERIMENTS.md).
 Per run: join_ms (counting launches), emit_ms (the writing pass), total_ms and pairs/s of the emitting pass and of the whole join.
 Every case is a child process under its own time limit; the first failure ends the tool.
     python tools/mm_heavy.py [cases, default a0,a1,b,c] [runs, default 5]
+    python tools/mm_heavy.py b,b.left,b.full,c,c.left,c.full
     FJ_LIB_VARIANT=<name> python tools/mm_heavy.py a0     # the same on lib/ab/<name>.so (a same-box A/B)"""
 import json
 import os
@@ -43,19 +47,26 @@ def run_case(name, runs):
     sys.path.insert(0, ROOT)
     import flash_join
     flash_join.initialize()
-    bk, bv, pk = case_inputs(name)
+    base, _, form = name.partition(".")
+    bk, bv, pk = case_inputs(base)
     try:
-        flash_join.set_option("mm_heavy_keys", 0 if name == "a0" else 1)
+        flash_join.set_option("mm_heavy_outer" if form else "mm_heavy_keys", 0 if base == "a0" else 1)
     except RuntimeError:                 # a library from before the option: case a0 is what it can run
         assert name == "a0", name
-    n_count = flash_join.inner_join_count(bk, bv, pk)[0]
-    flash_join.inner_join(bk, bv, pk)                                         # warm-up: workspace, kernel attributes
+    if form:                                                                  # the outer forms: (P, u[, r], seconds)
+        fn = flash_join.left_join if form == "left" else flash_join.full_join
+        join = lambda: fn(bk, bv, pk, duplicates="all")
+    else:
+        join = lambda: flash_join.inner_join(bk, bv, pk)
+    n_count = flash_join.inner_join_count(bk, bv, pk)[0] if not form else join()[0]
+    join()                                                                    # warm-up: workspace, kernel attributes
     for r in range(runs):
-        n, sec = flash_join.inner_join(bk, bv, pk)
+        res = join()
+        n, rows = res[0], sum(res[:-1])
         t = flash_join.last_timings()
         assert n == n_count, (n, n_count)
         print(json.dumps({"case": name, "run": r, "lib": os.environ.get("FJ_LIB_VARIANT", "") or "in-tree", "nb": bk.numel(), "np": pk.numel(),
-                          "pairs": n, "join_ms": round(t["join_ms"], 4), "emit_ms": round(t["emit_ms"], 4), "total_ms": round(t["total_ms"], 4),
+                          "pairs": n, "rows": rows, "join_ms": round(t["join_ms"], 4), "emit_ms": round(t["emit_ms"], 4), "total_ms": round(t["total_ms"], 4),
                           "lds_retries": t["lds_retries"], "emit_gpairs_s": round(n / t["emit_ms"] / 1e6, 3) if t["emit_ms"] > 0 else None,
                           "emit_write_gb_s": round(16 * n / t["emit_ms"] / 1e6, 1) if t["emit_ms"] > 0 else None,
                           "total_gpairs_s": round(n / t["total_ms"] / 1e6, 3)}), flush=True)
@@ -68,10 +79,11 @@ def main():
     cases = sys.argv[1].split(",") if len(sys.argv) > 1 else ["a0", "a1", "b", "c"]
     runs = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     for name in cases:
-        if name not in LIMITS:
-            print(f"unknown case {name!r} (a0, a1, b, c)", file=sys.stderr)
+        base, _, form = name.partition(".")
+        if base not in LIMITS or form not in ("", "left", "full"):
+            print(f"unknown case {name!r} (a0, a1, b, c, each also with .left or .full)", file=sys.stderr)
             return 2
-        rc = subprocess.call(["timeout", "-k", "10", str(LIMITS[name]), sys.executable, os.path.abspath(__file__), "--case", name, str(runs)], cwd=ROOT)
+        rc = subprocess.call(["timeout", "-k", "10", str(LIMITS[base]), sys.executable, os.path.abspath(__file__), "--case", name, str(runs)], cwd=ROOT)
         if rc != 0:
             print(f"case {name}: exit status {rc}; stopping", file=sys.stderr)
             return rc
