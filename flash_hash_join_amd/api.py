@@ -38,6 +38,7 @@ ALGO_ANTI = 0x40                  # FJ_ALGO_ANTI: the probe rows without a partn
 ALGO_ROW_IDS = 0x80               # FJ_ALGO_ROW_IDS: output rows hold row positions (gather maps) instead of keys and values (extension)
 ALGO_FULL_OUTER = 0x100           # FJ_ALGO_FULL_OUTER: full outer join, np + r rows; the count is the pair (m, r) (extension)
 ALGO_ALL_COPIES = 0x200           # FJ_ALGO_ALL_COPIES: modifier of LEFT_OUTER / FULL_OUTER - every copy of a duplicated build key; the count is (P, r, u) (extension)
+ALGO_PROBE_ORDER = 0x800          # FJ_ALGO_PROBE_ORDER: one row per probe row at the probe row's position - np values and / or an np-byte mask (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -207,8 +208,9 @@ def _room_for(np_rows: int, dev: int) -> bool:
 
 
 def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arrays: bool = False,
-                hash_top_bits: int = 64):
-    """Device-resident join on torch ROCm tensors (int64 storage, bit-identical to uint64)."""
+                hash_top_bits: int = 64, want_values: bool = True, want_mask: bool = False):
+    """Device-resident join on torch ROCm tensors (int64 storage, bit-identical to uint64).
+    want_values / want_mask: which outputs a probe-order join (ALGO_PROBE_ORDER) writes; not read otherwise."""
     global _last
     import torch
     L = _lib.load()
@@ -222,6 +224,20 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     cnt = ctypes.c_uint64(0)
     t = FjTimings()
     bv_ptr = bv.data_ptr() if bv is not None else None
+    if algo & ALGO_PROBE_ORDER:
+        # probe-order join: exactly np int64 and / or np uint8, one call, never a pending result, no emit.  Returns
+        # (m, seconds, values or None, mask or None) whatever return_arrays says: the arrays ARE the result
+        if not (want_values or want_mask):
+            raise ValueError("probe-order join: want_values, want_mask or both")
+        n_p = pk.numel()
+        ov = torch.empty(n_p, dtype=torch.int64, device=bk.device) if want_values else None
+        om = torch.empty(n_p, dtype=torch.uint8, device=bk.device) if want_mask else None
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(), n_p, stream,
+                                   hash_top_bits, ctypes.byref(cnt), om.data_ptr() if want_mask else None,
+                                   ov.data_ptr() if want_values else None, n_p, ctypes.byref(t)))
+        _last = t
+        return int(cnt.value), t.total_ms * 1e-3, ov, om
     if algo & ALGO_ALL_COPIES:
         # every copy of a duplicated build key: the size is not known up front - count, allocate exactly P + u + r rows, emit;
         # the two calls share the context's one pending result, so other threads stay out in between.  The count is (P, r, u)
@@ -512,6 +528,83 @@ def semi_join_count(build_keys, probe_keys):
     return _join(ALGO_ADAPTIVE, 0, 0, build_keys, build_keys, probe_keys, False)
 
 
+# ---- extension: probe-order joins (one row per probe row, at the probe row's position; csrc/fj_aligned.hip) -------------------------
+def _probe_order_host(algo: int, bk, bv, pk, want_values: bool, want_mask: bool):
+    global _last
+    L = _lib.load()
+    bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
+    bv = _as_u64_host(bv, "build_values") if bv is not None else None
+    if bv is not None and bv.size < bk.size:
+        raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
+    cnt, sec = ctypes.c_uint64(0), ctypes.c_double(0.0)
+    om, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, bk.ctypes.data, bv.ctypes.data if bv is not None else None, bk.size, pk.ctypes.data, pk.size,
+                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(om) if want_mask else None, ctypes.byref(ov) if want_values else None))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    n = pk.size
+    try:
+        vals = mask = None
+        if want_values:
+            vals = (np.ctypeslib.as_array(ctypes.cast(ov, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy() if n else np.empty(0, np.uint64))
+        if want_mask:
+            mask = (np.ctypeslib.as_array(ctypes.cast(om, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy() if n else np.empty(0, np.uint8))
+    finally:
+        L.fj_free_host(om)
+        L.fj_free_host(ov)
+    return int(cnt.value), float(sec.value), vals, mask
+
+
+def _probe_order(algo: int, build_keys, build_values, probe_keys, want_values: bool, want_mask: bool):
+    """(m, seconds, values or None, mask or None): int64 values and a uint8 mask of len(probe_keys), where the inputs live"""
+    build_keys, build_values, probe_keys = (_from_dlpack_if_device(x) if x is not None else None for x in (build_keys, build_values, probe_keys))
+    if _is_torch_tensor(build_keys) and build_keys.is_cuda:
+        return join_device(algo | ALGO_PROBE_ORDER, 0, 1, build_keys, build_values, probe_keys, want_values=want_values, want_mask=want_mask)
+    if _is_torch_tensor(build_keys):
+        build_keys, build_values, probe_keys = (x.numpy() if x is not None else None for x in (build_keys, build_values, probe_keys))
+    m, sec, vals, mask = _probe_order_host(algo | ALGO_PROBE_ORDER, build_keys, build_values, probe_keys, want_values, want_mask)
+    return m, sec, (vals.view(np.int64) if vals is not None else None), mask
+
+
+def lookup(build_keys, build_values, probe_keys, fill_value: int = 0, return_mask: bool = False):
+    """Dictionary / foreign-key lookup in probe order: values[i] is the build value of probe_keys[i] (a duplicated build key: its
+    FIRST occurrence's), `fill_value` where the key is not among the build keys.  Returns (m, seconds, values) or, return_mask=True,
+    (m, seconds, values, mask): m = probe rows with a partner (what the counting joins return), values int64 of len(probe_keys) (the
+    storage of the uint64 words), mask uint8 1 / 0 per probe row.  One pass over the probe side: no counting pass, no compaction.
+    NumPy arrays in, NumPy arrays out; torch ROCm tensors / DLPack are joined in place and the outputs live on their device."""
+    if isinstance(fill_value, bool) or not isinstance(fill_value, (int, np.integer)):
+        raise TypeError(f"lookup: fill_value must be an integer, got {type(fill_value).__name__}")
+    fill_value = int(fill_value)
+    if not -(1 << 63) <= fill_value < (1 << 64):
+        raise ValueError("lookup: fill_value does not fit 64 bits")
+    if build_values is None:
+        raise ValueError("lookup: build_values is required (isin / lookup_indices take none)")
+    need_mask = return_mask or fill_value != 0
+    m, sec, vals, mask = _probe_order(ALGO_ADAPTIVE, build_keys, build_values, probe_keys, True, need_mask)
+    if fill_value != 0 and m < vals.shape[0]:                # applied through the mask, as _fill does for left_join's ranges
+        word = int(np.array(fill_value % (1 << 64), dtype=np.uint64).view(np.int64))     # int64 storage of the uint64 word
+        if _is_torch_tensor(vals):
+            vals.masked_fill_(mask == 0, word)
+        else:
+            vals[mask == 0] = word
+    return (m, sec, vals, mask) if return_mask else (m, sec, vals)
+
+
+def isin(probe_keys, build_keys):
+    """Membership mask in probe order (torch.isin / the mark join of IN and EXISTS): (m, seconds, mask), mask[i] = 1 if probe_keys[i]
+    is among the build keys, uint8 of len(probe_keys); m = mask.sum().  The mask-only form: no build value is read or asked for."""
+    m, sec, _, mask = _probe_order(ALGO_ADAPTIVE, build_keys, None, probe_keys, False, True)
+    return m, sec, mask
+
+
+def lookup_indices(build_keys, probe_keys):
+    """Gather map in probe order: (m, seconds, build_idx), build_idx[i] = 0-based row of the FIRST occurrence of probe_keys[i] among
+    the build keys, -1 where there is none; int64 of len(probe_keys).  join_indices(how="left") without the compaction."""
+    m, sec, idx, _ = _probe_order(ALGO_ADAPTIVE | ALGO_ROW_IDS, build_keys, None, probe_keys, True, False)
+    return m, sec, idx
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
@@ -599,5 +692,5 @@ REFERENCE_EXPORTS = [
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
-              "full_join", "semi_join", "semi_join_count"]
+              "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

@@ -310,6 +310,11 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
 int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
               hipStream_t s, fj_timings* t, u64* out_counts, u64* d_ok, u64* d_ov, bool rid);
 
+// ---- probe-order joins (fj_aligned.hip): FJ_ALGO_PROBE_ORDER; d_ov[i] (np words) and / or d_mask[i] (np bytes) for every probe row i,
+// either may be null; *out_count = probe rows with a partner; rid: d_ov holds first-occurrence build positions (~0: none) ----
+int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
+                     hipStream_t s, fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid);
+
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,
                 size_t probe_piece_rows = 0);

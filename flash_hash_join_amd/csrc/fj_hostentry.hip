@@ -179,12 +179,21 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
+    const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
+    if (po) {                                                  // probe-order join: *out_vals np words, *out_keys np BYTES (the mask)
+        if (many_host || left || anti || full || allc)
+            return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
+                           many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : "ALL_COPIES");
+        if (!materialize) return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER needs materialize = 1 (its match count is the counting join's)");
+        if (!out_keys && !out_vals) return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER needs an output (out_vals, the byte mask out_keys, or both)");
+        if (nb && out_vals && !rid && !bv) return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER with out_vals needs build values (only FJ_ALGO_ROW_IDS and the mask alone read none)");
+    }
     if (allc) {                                                // (the checks of fj_join_device, before the context is created)
         if (anti) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_ANTI (an anti join has no copies to keep)");
         if (many_host) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
         if (!left && !full) return set_err("fj_join_host: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo);
     }
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
@@ -235,7 +244,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // A counting join of the partitioned plan starts on the first piece: the build side is copied and partitioned, then every
     // probe piece gets its first partition pass while the next one crosses PCIe (the join hides under the copy; the bloom
     // precheck is skipped here - it saves device time the copy does not leave on the critical path).
-    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti && !full;
+    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti && !full && !po;
     hipStream_t js = nullptr;
     auto t0 = std::chrono::steady_clock::now();
     unsigned cursor = 0;
@@ -244,7 +253,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     bool joined = false;
     if (h2d_pipelined(c, dbk, bk, nb * 8, piece, &cursor, nullptr)) return 1;
     if (!streamed) {
-        if ((anti && !bv) || rid) dbv = dbk;                                    // (an anti join reads no value, a row-id join none either)
+        if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
         else if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
         if (h2d_pipelined(c, dpk, pk, np * 8, piece, &cursor, nullptr)) return 1;
         HIPCHK(hipStreamSynchronize(c->side));
@@ -324,6 +333,22 @@ int fj_join_host(int algo, int bloom, int materialize,
         }
         joined = true;
     }
+    if (po) {                                                                  // np words and / or np bytes, in probe order; no emit step
+        void *dmask = nullptr, *dov = nullptr;
+        if ((out_keys && get_buf(c, W_H_OK, std::max<size_t>(np, 1), &dmask)) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(np, 1) * 8, &dov))) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
+                           &count, (u64*)dmask, (u64*)dov, np, &t)) return 1;
+        void* hm = out_keys ? malloc(std::max<size_t>(np, 1)) : nullptr;
+        u64* hv = out_vals ? (u64*)malloc(std::max<size_t>(np, 1) * 8) : nullptr;
+        if ((out_keys && !hm) || (out_vals && !hv)) { free(hm); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", np); }
+        auto t1 = std::chrono::steady_clock::now();
+        if (np && hm) HIPCHK(hipMemcpy(hm, dmask, np, hipMemcpyDeviceToHost));
+        if (np && hv) HIPCHK(hipMemcpy(hv, dov, np * 8, hipMemcpyDeviceToHost));
+        d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (out_keys) *out_keys = (uint64_t*)hm;
+        if (out_vals) *out_vals = hv;
+        joined = true;
+    }
     if (!joined) {
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
                            &count, nullptr, nullptr, 0, &t)) return 1;
@@ -345,7 +370,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined && !outer_mat && !full && !allc ? 1 : 0;
+    t.host_streamed = joined && !outer_mat && !full && !allc && !po ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
     if (full && !allc) out_count[1] = full_r;

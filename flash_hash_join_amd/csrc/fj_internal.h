@@ -322,6 +322,15 @@ hipError_t fj_launch_outer_join(const FjLdsJoinArgs& a, int mode, u64 np, unsign
 hipError_t fj_launch_gt_build_first(const FjGtArgs& a, bool vals, hipStream_t s);
 hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long long* miss_cursor, u64 out_capacity, hipStream_t s);
 
+// ---- probe-order joins (csrc/fj_aligned.hip; FJ_ALGO_PROBE_ORDER of include/flashjoin.h) -----------------------------------------
+// One output row per probe row at the row's own position (the probe chunk pool's vals plane; flat arrays: the index): a.out_vals[pos]
+// (nullptr: the mask form, the build side carries no values) and / or mask[pos] = 1 / 0.  first: the build 'values' are row indices,
+// the smallest wins, then a.orig_vals[idx] - or, a.row_ids, the index itself (a miss: ~0 instead of 0); !first: unique build keys
+// expected (duplicates: FJ_STAT_DUPS).  a.total counts the hits, miss_total the misses; positions >= np are not written (FJ_ERR_OUTCAP).
+hipError_t fj_launch_probe_order_join(const FjLdsJoinArgs& a, bool first, u64 np, unsigned long long* miss_total, unsigned char* mask, hipStream_t s);
+// global table built by fj_launch_gt_build_first (vals = a.out_vals != nullptr): thread i serves probe row i
+hipError_t fj_launch_gt_probe_order(const FjGtArgs& a, unsigned long long* miss_total, unsigned char* mask, hipStream_t s);
+
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat
 // arrays: the row index), zeroed before the launch.  Every work item ORs in the rows whose key one of its probe rows hit (mode

@@ -1653,6 +1653,49 @@ __global__ __launch_bounds__(1024) void fj_gt_outer_probe_kernel(FjGtArgs a, uns
     }
 }
 
+// probe-order join on the global table (FJ_ALGO_PROBE_ORDER, csrc/fj_aligned.hip): thread i serves probe row i, so the probe is in
+// order by itself - a.out_vals[i] (VALS: the value gathered by the slot's first-occurrence row index; RID: that index, ~0 for a miss)
+// and / or mask[i] (MASK), coalesced stores, no reservation.  Hits and misses are counted per wave, added once per workgroup.
+template <bool RID, bool VALS, bool MASK>
+__global__ __launch_bounds__(1024) void fj_gt_probe_order_kernel(FjGtArgs a, unsigned long long* miss_total, unsigned char* __restrict__ mask) {
+    static_assert(VALS || MASK, "an output");
+    static_assert(!RID || VALS, "row ids are values");
+    __shared__ u32 s_hits, s_misses;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) { s_hits = 0; s_misses = 0; }
+    __syncthreads();
+    const bool has_empty = a.flags[0] != 0;
+    const u64 np = a.np;
+    u32 nh = 0, nm = 0;                                                           // (wave-uniform)
+    for (u64 base = (u64)blockIdx.x * 1024; base < np; base += (u64)gridDim.x * 1024) {     // (uniform per workgroup)
+        const u64 i = base + tid;
+        const bool ok = i < np;
+        bool h = false;
+        u64 where = 0, key = 0;
+        if (ok) {
+            key = a.pk[i];
+            if (key == FJ_EMPTY_KEY) h = has_empty;
+            else h = gt_lookup(a.tkeys, a.cap_mask, key, fj_hash64(key), where);
+            if (VALS) {
+                u64 v = RID ? ~0ull : 0ull;
+                if (h) {
+                    const u64 row = key == FJ_EMPTY_KEY ? *a.empty_val : a.tvals[where];
+                    v = RID ? row : a.bv[row];
+                }
+                a.out_vals[i] = v;
+            }
+            if (MASK) mask[i] = h ? 1 : 0;
+        }
+        nh += (u32)__popcll(__ballot(h)); nm += (u32)__popcll(__ballot(ok && !h));
+    }
+    if (lane == 0) { if (nh) atomicAdd(&s_hits, nh); if (nm) atomicAdd(&s_misses, nm); }
+    __syncthreads();
+    if (tid == 0) {
+        if (s_hits) atomicAdd(a.total, (unsigned long long)s_hits);
+        if (s_misses) atomicAdd(miss_total, (unsigned long long)s_misses);
+    }
+}
+
 // full outer join, last step on the global table: every build row looks its key up again; the rows of slots no probe row hit are
 // appended behind row `base` ((key, value), or (~0, row index) in the row-id form).  Reservation as in fj_full_sweep_kernel.
 __global__ __launch_bounds__(1024) void fj_gt_full_sweep_kernel(FjGtArgs a, u64 base, u64 out_capacity, unsigned long long* cursor, u32* err) {
@@ -1980,6 +2023,20 @@ hipError_t fj_launch_gt_outer_probe(const FjGtArgs& a, int mode, unsigned long l
     }
     if (mode == FJ_OJ_ANTI) hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_ANTI>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
     else hipLaunchKernelGGL(fj_gt_outer_probe_kernel<FJ_OJ_LEFT>, dim3(grid), dim3(1024), 0, s, a, miss_cursor, out_capacity);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_probe_order(const FjGtArgs& a, unsigned long long* miss_total, unsigned char* mask, hipStream_t s) {
+    if (a.np == 0) return hipSuccess;
+    const bool vals = a.out_vals != nullptr;
+    if (!miss_total || !a.total || (!vals && !mask) || (vals && (!a.tvals || (!a.bv && !a.row_ids))) || (a.row_ids && !vals)) return hipErrorInvalidValue;
+    const u64 rounds = (a.np + 1023) / 1024;
+    const u32 grid = (u32)(rounds < 4096 ? rounds : 4096);
+    void (*kern)(FjGtArgs, unsigned long long*, unsigned char*);
+    if (!vals) kern = fj_gt_probe_order_kernel<false, false, true>;
+    else if (a.row_ids) kern = mask ? fj_gt_probe_order_kernel<true, true, true> : fj_gt_probe_order_kernel<true, true, false>;
+    else kern = mask ? fj_gt_probe_order_kernel<false, true, true> : fj_gt_probe_order_kernel<false, true, false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), 0, s, a, miss_total, mask);
     return hipGetLastError();
 }
 

@@ -683,8 +683,23 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
+    const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
+    if (po) {
+        // probe-order join (csrc/fj_aligned.hip): every check before any device work, so that it holds for a null context too.
+        // d_out_keys is the byte mask here: no alignment asked of it
+        algo &= ~FJ_ALGO_PROBE_ORDER;
+        if (many || left || anti || full || allc)
+            return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
+                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : "ALL_COPIES");
+        if (!materialize) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER needs materialize = 1 (its match count is the counting join's)");
+        if (np && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER needs an output (d_out_vals, the byte mask d_out_keys, or both)");
+        if (out_capacity < np) return set_err("fj_join_device: output capacity %zu < %zu probe rows (FJ_ALGO_PROBE_ORDER writes every probe row)", out_capacity, np);
+        if ((uintptr_t)d_out_vals & 7) return set_err("fj_join_device: d_out_vals must be 8-byte aligned");
+        if (nb && d_out_vals && !rid && !d_bv) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER with d_out_vals needs d_build_vals (only FJ_ALGO_ROW_IDS and the mask alone read no build value)");
+        if (!d_bv) d_bv = d_bk;                             // the mask alone reads no value (the checks below want a pointer)
+    }
     if (rid) {
         // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
         algo &= ~FJ_ALGO_ROW_IDS;
@@ -757,6 +772,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, c3, rid, full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
         out_count[0] = c3[0]; out_count[1] = c3[1]; out_count[2] = c3[2];
         if (d_out_keys && d_out_vals && emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (po) {                                               // one row per probe row at its own position, never a pending result
+        if (join_probe_order(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, (unsigned char*)d_out_keys,
+                             (u64*)d_out_vals, rid)) return 1;
+        if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;
         return 0;

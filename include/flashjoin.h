@@ -110,6 +110,26 @@ extern "C" {
  * form is FJ_ALGO_MANY_TO_MANY), or with FJ_ALGO_ANTI (an anti join has no copies to keep) or FJ_ALGO_MANY_TO_MANY; materialize = 0;
  * out_count == NULL; misaligned output buffers; d_build_vals == NULL without FJ_ALGO_ROW_IDS. */
 #define FJ_ALGO_ALL_COPIES 0x200
+/* EXTENSION (no reference counterpart; csrc/fj_aligned.hip): OR this into `algo` together with a base value (ADAPTIVE, SCALAR or RADIX:
+ * the partitioned plan or the global HBM table exactly as for FJ_ALGO_LEFT_OUTER) and optionally FJ_ALGO_ROW_IDS for a PROBE-ORDER
+ * join: one output row per probe row, AT the probe row's position - a dictionary lookup, a foreign-key column, an isin mask, a mark
+ * join.  N:1 semantics as everywhere: a duplicated build key answers with its FIRST occurrence, on every path.  materialize = 1 only;
+ * bloom is ignored.  With np probe rows:
+ *   d_out_vals   optional; 8-byte aligned, np words: d_out_vals[i] = the build value of the first occurrence of d_probe_keys[i], 0 when
+ *                the key has no partner.  With FJ_ALGO_ROW_IDS: that build row's position, UINT64_MAX when there is none; d_build_vals
+ *                may then be NULL and is never read.
+ *   d_out_keys   optional; no alignment asked, np BYTES (the parameter is reused as a byte pointer - there is no key to return, row i
+ *                IS probe row i): ((uint8_t*)d_out_keys)[i] = 1 if probe row i has a partner, else 0.
+ * At least one of the two is non-NULL; with the mask alone d_build_vals may be NULL (the semi / mark form).  *out_count = m, the probe
+ * rows with a partner (what the counting join returns).  out_capacity >= np.  Every one of the np positions is written exactly once
+ * per launch, nothing at or beyond row np (byte np of the mask) is touched, and the caller need not clear anything.  nb == 0: zeros
+ * (FJ_ALGO_ROW_IDS: all ones), a zero mask, m = 0; np == 0: nothing happens.  Never a pending result for fj_emit_pairs (a result that
+ * was pending is dropped).  fj_join_host: *out_vals is a malloc'ed array of np words, *out_keys one of np bytes; either pointer may be
+ * NULL to drop that output.  fj_timings as for FJ_ALGO_LEFT_OUTER; emit_ms = 0.
+ * Refused up front, before any device work: combined with FJ_ALGO_MANY_TO_MANY, FJ_ALGO_LEFT_OUTER, FJ_ALGO_ANTI, FJ_ALGO_FULL_OUTER or
+ * FJ_ALGO_ALL_COPIES; materialize = 0; both outputs NULL; an output capacity below np; a misaligned d_out_vals; d_out_vals with
+ * d_build_vals == NULL and no FJ_ALGO_ROW_IDS. */
+#define FJ_ALGO_PROBE_ORDER 0x800
 
 typedef struct fj_ctx fj_ctx;
 
