@@ -39,6 +39,7 @@ ALGO_ROW_IDS = 0x80               # FJ_ALGO_ROW_IDS: output rows hold row positi
 ALGO_FULL_OUTER = 0x100           # FJ_ALGO_FULL_OUTER: full outer join, np + r rows; the count is the pair (m, r) (extension)
 ALGO_ALL_COPIES = 0x200           # FJ_ALGO_ALL_COPIES: modifier of LEFT_OUTER / FULL_OUTER - every copy of a duplicated build key; the count is (P, r, u) (extension)
 ALGO_PROBE_ORDER = 0x800          # FJ_ALGO_PROBE_ORDER: one row per probe row at the probe row's position - np values and / or an np-byte mask (extension)
+ALGO_BUILD_ORDER = 0x1000         # FJ_ALGO_BUILD_ORDER: one word per build row at the build row's position - nb counts and / or nb sums of a probe-side column (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -208,15 +209,16 @@ def _room_for(np_rows: int, dev: int) -> bool:
 
 
 def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arrays: bool = False,
-                hash_top_bits: int = 64, want_values: bool = True, want_mask: bool = False):
+                hash_top_bits: int = 64, want_values: bool = True, want_mask: bool = False, want_counts: bool = True):
     """Device-resident join on torch ROCm tensors (int64 storage, bit-identical to uint64).
-    want_values / want_mask: which outputs a probe-order join (ALGO_PROBE_ORDER) writes; not read otherwise."""
+    want_values / want_mask: which outputs a probe-order join (ALGO_PROBE_ORDER) writes; not read otherwise.
+    ALGO_BUILD_ORDER: bv is the PROBE side's value column (len(pk) words, or None); want_counts / want_values: the counts and the sums."""
     global _last
     import torch
     L = _lib.load()
     bk, pk = _dev_tensor(bk, "build_keys"), _dev_tensor(pk, "probe_keys")
-    bv = _dev_tensor(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
-    if bv is not None and bv.numel() < bk.numel():
+    bv = _dev_tensor(bv, "probe_values" if algo & ALGO_BUILD_ORDER else "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
+    if bv is not None and not algo & ALGO_BUILD_ORDER and bv.numel() < bk.numel():
         raise ValueError(f"build_values has {bv.numel()} elements, build_keys has {bk.numel()}")
     dev = bk.device.index if bk.device.index is not None else torch.cuda.current_device()
     ctx = context(dev)
@@ -224,6 +226,23 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     cnt = ctypes.c_uint64(0)
     t = FjTimings()
     bv_ptr = bv.data_ptr() if bv is not None else None
+    if algo & ALGO_BUILD_ORDER:
+        # build-order aggregate join: exactly nb int64 counts and / or nb int64 sums, one call, never a pending result, no emit.
+        # Returns (P, seconds, counts or None, sums or None)
+        want_sums = want_values and bv is not None
+        if not (want_counts or want_sums):
+            raise ValueError("build-order join: want_counts, probe values with want_values, or both")
+        if bv is not None and bv.numel() != pk.numel():
+            raise ValueError(f"probe_values has {bv.numel()} elements, probe_keys has {pk.numel()}")
+        n_b = bk.numel()
+        oc = torch.empty(n_b, dtype=torch.int64, device=bk.device) if want_counts else None
+        osum = torch.empty(n_b, dtype=torch.int64, device=bk.device) if want_sums else None
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr if want_sums else None, n_b, pk.data_ptr(), pk.numel(), stream,
+                                   hash_top_bits, ctypes.byref(cnt), oc.data_ptr() if want_counts else None,
+                                   osum.data_ptr() if want_sums else None, n_b, ctypes.byref(t)))
+        _last = t
+        return int(cnt.value), t.total_ms * 1e-3, oc, osum
     if algo & ALGO_PROBE_ORDER:
         # probe-order join: exactly np int64 and / or np uint8, one call, never a pending result, no emit.  Returns
         # (m, seconds, values or None, mask or None) whatever return_arrays says: the arrays ARE the result
@@ -605,6 +624,62 @@ def lookup_indices(build_keys, probe_keys):
     return m, sec, idx
 
 
+# ---- extension: build-order aggregate joins (one word per build row, at the build row's position; csrc/fj_group.hip) -----------------
+def _group_host(algo: int, bk, pk, pv, want_counts: bool):
+    global _last
+    L = _lib.load()
+    bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
+    pv = _as_u64_host(pv, "probe_values") if pv is not None else None
+    if pv is not None and pv.size != pk.size:
+        raise ValueError(f"probe_values has {pv.size} elements, probe_keys has {pk.size}")
+    cnt, sec = ctypes.c_uint64(0), ctypes.c_double(0.0)
+    oc, osum = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, bk.ctypes.data, pv.ctypes.data if pv is not None else None, bk.size, pk.ctypes.data, pk.size,
+                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(oc) if want_counts else None, ctypes.byref(osum) if pv is not None else None))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    n = bk.size
+    try:
+        take = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy() if n else np.empty(0, np.uint64)).view(np.int64)
+        counts = take(oc) if want_counts else None
+        sums = take(osum) if pv is not None else None
+    finally:
+        L.fj_free_host(oc)
+        L.fj_free_host(osum)
+    return int(cnt.value), float(sec.value), counts, sums
+
+
+def _group(build_keys, probe_keys, probe_values, want_counts: bool):
+    """(P, seconds, counts or None, sums or None): int64 of len(build_keys), where the inputs live"""
+    build_keys, probe_keys, probe_values = (_from_dlpack_if_device(x) if x is not None else None for x in (build_keys, probe_keys, probe_values))
+    algo = ALGO_ADAPTIVE | ALGO_BUILD_ORDER
+    if _is_torch_tensor(build_keys) and build_keys.is_cuda:
+        return join_device(algo, 0, 1, build_keys, probe_values, probe_keys, want_counts=want_counts)
+    if _is_torch_tensor(build_keys):
+        build_keys, probe_keys, probe_values = (x.numpy() if x is not None else None for x in (build_keys, probe_keys, probe_values))
+    return _group_host(algo, build_keys, probe_keys, probe_values, want_counts)
+
+
+def group_join_count(build_keys, probe_keys):
+    """The join that feeds a GROUP BY on the build side, count form: (P, seconds, counts), counts[i] = the probe rows whose key equals
+    build_keys[i], int64 of len(build_keys), aligned with the build rows; every copy of a duplicated build key carries the key's count.
+    P = counts.sum(), the pairs of the many-to-many inner join.  No pairs are made and the probe side moves its keys only.
+    NumPy arrays in, NumPy arrays out; torch ROCm tensors / DLPack are joined in place and the outputs live on their device."""
+    P, sec, counts, _ = _group(build_keys, probe_keys, None, True)
+    return P, sec, counts
+
+
+def group_join_sum(build_keys, probe_keys, probe_values, return_counts: bool = False):
+    """Sum form: (P, seconds, sums) or, return_counts=True, (P, seconds, sums, counts).  sums[i] = the sum modulo 2^64 of
+    probe_values[j] over the probe rows j whose key equals build_keys[i] (int64 storage of the uint64 words), 0 where there are none;
+    probe_values has one word per probe row.  The mean is sums / counts."""
+    if probe_values is None:
+        raise ValueError("group_join_sum: probe_values is required (group_join_count takes none)")
+    P, sec, counts, sums = _group(build_keys, probe_keys, probe_values, bool(return_counts))
+    return (P, sec, sums, counts) if return_counts else (P, sec, sums)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
@@ -692,5 +767,5 @@ REFERENCE_EXPORTS = [
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
-              "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices"]
+              "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

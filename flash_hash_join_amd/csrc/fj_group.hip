@@ -1,0 +1,382 @@
+// fj_group.hip -- build-order aggregate joins (an EXTENSION: FJ_ALGO_BUILD_ORDER, include/flashjoin.h): one output word per BUILD row,
+// at the build row's position.  counts[i] = the probe rows whose key equals build key i, sums[i] = the sum (mod 2^64) of a probe-side
+// value column over those rows: the join that feeds a GROUP BY on the build side, without the pairs in between.
+//
+// Like the probe-order joins (csrc/fj_aligned.hip) its size and layout are known before it starts, so nothing is reserved and nothing
+// stays pending.  The build side carries its rows' positions through the passes (PassIter::vals_pos); the probe side carries its
+// values when sums are asked for and NOTHING when only counts are (the keys-only pass).  Per work item the join kernel builds the
+// partition's distinct keys into the 8192-slot LDS table with one 8-byte accumulator per slot (128 KiB), streams the slice's probe
+// rows adding 1 or the row's value to the slot with an LDS atomic, and then walks the partition's build rows again: every row looks
+// its slot up and adds a non-zero accumulator to out[position] with a global atomic (a partition may be cut into several items; the
+// outputs are zeroed once per call).  Every copy of a duplicated build key reads the same slot, so it receives the same aggregate.
+//
+// Both outputs in one call: the passes run once and the kernel is launched twice over the same partitions, once per accumulator (keys
+// plus two accumulators would be 192 KiB of LDS).
+//
+// P, the sum of all counts: the count form adds up what it flushes.  The sum form keeps no counts; it counts its hits, which is P when
+// the partition's build keys are distinct, and reports duplicates (FJ_STAT_DUPS) otherwise - the host then runs the count form once
+// without an output, for P alone.
+//
+// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole join on the global HBM table (the kernels at
+// the end of this file), timings.fell_back = 1.
+#include "fj_host.h"
+
+namespace {
+
+constexpr u32 GJ_NT = 1024, GJ_KPT = 8, GJ_ROUND_CHUNKS = GJ_NT * GJ_KPT / FJ_CHUNK;
+constexpr u32 GJ_TS = 8192, GJ_LIMIT = GJ_TS - GJ_TS / 16;
+struct GjHdr { u32 full, dups, empty_cnt, nkeys, hits, pad0; u64 empty_acc, total; };
+
+__device__ __forceinline__ u32 gj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
+    if (cs.list) return cs.list[idx];
+    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
+    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
+    return ((cnt - 1u) << 24) | idx;
+}
+
+__device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (u64)__shfl_xor((unsigned long long)v, d, 64);
+    return v;
+}
+
+// SUM: the accumulators take the probe rows' values (a.probe.vals), else 1 per row.  out: nb words, zeroed before the launch (nullptr,
+// count form only: nothing is flushed, the launch is for P alone).  a.total (may be null) receives P - count form: what the flush read;
+// sum form: the hits, and FJ_STAT_DUPS tells the host that this is not P.
+template <bool SUM>
+__global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a, u64* __restrict__ out, u64 nb) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    GjHdr* hdr = reinterpret_cast<GjHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(GjHdr));
+    u64* acc = tkeys + GJ_TS;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 item = blockIdx.x;
+    u32 p, b0 = 0, nbc, s_lo, s_hi;
+    if (a.items) {
+        if (item >= *a.nitems_dev) return;
+        const uint4 it = a.items[item];
+        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
+    } else {
+        const u32 slice = item % a.nsplit;
+        p = item / a.nsplit;
+        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
+    }
+    if (s_lo >= s_hi) return;
+    if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
+    else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; acc[i] = 0; }
+    if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->hits = 0; hdr->empty_acc = 0; hdr->total = 0; }
+    __syncthreads();
+
+    // ---- build: distinct keys; a copy finds its key in place ----
+    for (u32 c0 = 0; c0 < nbc; c0 += GJ_NT / FJ_CHUNK) {
+        const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        if (c >= nbc) continue;
+        const u32 e = gj_entry(a.build, b0 + c);
+        if (off >= FJ_LIST_CNT(e)) continue;
+        const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+        const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
+        if (key == FJ_EMPTY_KEY) {                           // the empty marker is never stored in the table
+            if (atomicAdd(&hdr->empty_cnt, 1u) != 0 && SUM) hdr->dups = 1;
+            continue;
+        }
+        u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+        bool placed = false;
+        for (u32 step = 0; step < GJ_TS; ++step) {
+            const u64 old = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+            if (old == FJ_EMPTY_KEY) {
+                if (atomicAdd(&hdr->nkeys, 1u) >= GJ_LIMIT) hdr->full = 1;
+                placed = true;
+                break;
+            }
+            if (old == key) { if (SUM) hdr->dups = 1; placed = true; break; }
+            pos = (pos + 1) & (GJ_TS - 1);
+        }
+        if (!placed) hdr->full = 1;
+    }
+    __syncthreads();
+    if (hdr->full) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }     // the host re-runs the join on the HBM table
+    const bool has_empty = hdr->empty_cnt != 0;
+
+    // ---- probe: rounds of GJ_NT * GJ_KPT rows; the next round's loads are requested before this round's lookups.  A hit adds to
+    // its slot's accumulator in LDS: no global traffic ----
+    u64 k[GJ_KPT], pv[SUM ? GJ_KPT : 1];
+    u32 okm = 0, nh = 0;                                     // nh: wave-uniform count of this wave's hits (SUM)
+    auto load_round = [&](u32 pc, u64 (&kk)[GJ_KPT], u64 (&vv)[SUM ? GJ_KPT : 1], u32& ok) {
+        ok = 0;
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) {
+            const u32 c = pc + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            kk[u] = 0; if (SUM) vv[SUM ? u : 0] = 0;
+            if (c >= s_hi) continue;
+            const u32 e = gj_entry(a.probe, c);
+            if (off >= FJ_LIST_CNT(e)) continue;
+            const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            kk[u] = a.probe.keys[src];
+            if (SUM) vv[SUM ? u : 0] = a.probe.vals[src];
+            ok |= 1u << u;
+        }
+    };
+    load_round(s_lo, k, pv, okm);
+    for (u32 pc = s_lo; pc < s_hi; pc += GJ_ROUND_CHUNKS) {
+        u64 kn[GJ_KPT], pvn[SUM ? GJ_KPT : 1];
+        u32 okn = 0;
+        if (pc + GJ_ROUND_CHUNKS < s_hi) load_round(pc + GJ_ROUND_CHUNKS, kn, pvn, okn);
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) {
+            bool h = false;
+            if ((okm >> u) & 1u) {
+                const u64 key = a.probe.list ? k[u] : fj_key_mix(k[u]);
+                const unsigned long long add = SUM ? (unsigned long long)pv[SUM ? u : 0] : 1ull;
+                if (key == FJ_EMPTY_KEY) {
+                    h = has_empty;
+                    if (h) atomicAdd((unsigned long long*)&hdr->empty_acc, add);
+                } else {
+                    u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+                    for (;;) {                               // the build left >= 1/16 of the slots empty: always terminates
+                        const u64 t = tkeys[pos];
+                        if (t == key) { h = true; atomicAdd((unsigned long long*)&acc[pos], add); break; }
+                        if (t == FJ_EMPTY_KEY) break;
+                        pos = (pos + 1) & (GJ_TS - 1);
+                    }
+                }
+            }
+            if (SUM) nh += (u32)__popcll(__ballot(h));
+        }
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) { k[u] = kn[u]; if (SUM) pv[SUM ? u : 0] = pvn[SUM ? u : 0]; }
+        okm = okn;
+    }
+    if (SUM && lane == 0 && nh) atomicAdd(&hdr->hits, nh);
+    __syncthreads();
+
+    // ---- flush: the partition's build rows once more; every copy of a key reads the same slot ----
+    u64 flushed = 0;
+    if (out || !SUM) {
+        const u64 empty_acc = hdr->empty_acc;
+        for (u32 c0 = 0; c0 < nbc; c0 += GJ_NT / FJ_CHUNK) {
+            const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            if (c >= nbc) continue;
+            const u32 e = gj_entry(a.build, b0 + c);
+            if (off >= FJ_LIST_CNT(e)) continue;
+            const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);
+            u64 v = empty_acc;
+            if (key != FJ_EMPTY_KEY) {
+                u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+                while (tkeys[pos] != key) pos = (pos + 1) & (GJ_TS - 1);      // (the build phase placed it)
+                v = acc[pos];
+            }
+            if (v == 0) continue;
+            flushed += v;
+            if (!out) continue;
+            const u64 o = a.build.vals ? a.build.vals[src] : src;             // (zero-pass plan: the flat index IS the position)
+            if (o < nb) atomicAdd((unsigned long long*)&out[o], (unsigned long long)v);   // (always: positions are 0 .. nb - 1)
+            else atomicOr(a.err, FJ_ERR_OUTCAP);
+        }
+    }
+    if (!a.total) return;
+    if (SUM) {
+        if (tid == 0) {
+            if (hdr->hits) atomicAdd(a.total, (unsigned long long)hdr->hits);
+            if (hdr->dups) atomicOr(a.err, FJ_STAT_DUPS);
+        }
+    } else {
+        flushed = gj_wave_sum64(flushed);
+        if (lane == 0 && flushed) atomicAdd((unsigned long long*)&hdr->total, (unsigned long long)flushed);
+        __syncthreads();
+        if (tid == 0 && hdr->total) atomicAdd(a.total, (unsigned long long)hdr->total);
+    }
+}
+
+// ---- the global-table form.  The table is fj_gt_build_first_kernel's, keys only (csrc/fj_join.hip: group-aligned home slot, linear
+// probing, the raw empty key out of band); the accumulators are arrays of capacity + 1 words, the last one the empty key's ----
+__device__ __forceinline__ bool gj_gt_find(const u64* __restrict__ tkeys, u64 cap_mask, u64 key, u64& where) {
+    u64 pos = (fj_hash64(key) & cap_mask) & ~(u64)(FJ_GT_GROUP - 1);
+    for (u64 step = 0; step <= cap_mask; ++step) {
+        const u64 t = tkeys[pos];
+        if (t == key) { where = pos; return true; }
+        if (t == FJ_EMPTY_KEY) return false;
+        pos = (pos + 1) & cap_mask;
+    }
+    return false;
+}
+
+// thread per probe row: a hit adds 1 to cnt[slot] and (sum != nullptr) the row's value to sum[slot]
+__global__ __launch_bounds__(1024) void fj_gt_group_probe_kernel(FjGtArgs a, const u64* __restrict__ pv, unsigned long long* cnt, unsigned long long* sum) {
+    const bool has_empty = a.flags[0] != 0;
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < a.np; i += stride) {
+        const u64 key = a.pk[i];
+        u64 where = a.cap_mask + 1;
+        if (key == FJ_EMPTY_KEY ? !has_empty : !gj_gt_find(a.tkeys, a.cap_mask, key, where)) continue;
+        atomicAdd(&cnt[where], 1ull);
+        if (sum) atomicAdd(&sum[where], (unsigned long long)pv[i]);
+    }
+}
+
+// thread i per build row i: out_cnt[i] / out_sum[i] = the slot's accumulators (coalesced stores, every row); a.total += the counts
+__global__ __launch_bounds__(1024) void fj_gt_group_flush_kernel(FjGtArgs a, const unsigned long long* cnt, const unsigned long long* sum,
+                                                                 u64* __restrict__ out_cnt, u64* __restrict__ out_sum) {
+    __shared__ unsigned long long s_total;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_total = 0;
+    __syncthreads();
+    u64 mine = 0;
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + tid; i < a.nb; i += stride) {
+        const u64 key = a.bk[i];
+        u64 where = a.cap_mask + 1;
+        if (key != FJ_EMPTY_KEY) gj_gt_find(a.tkeys, a.cap_mask, key, where);     // (the build placed it)
+        const u64 n = cnt[where];
+        mine += n;
+        if (out_cnt) out_cnt[i] = n;
+        if (out_sum) out_sum[i] = sum[where];
+    }
+    mine = gj_wave_sum64(mine);
+    if (lane == 0 && mine) atomicAdd(&s_total, (unsigned long long)mine);
+    __syncthreads();
+    if (tid == 0 && s_total) atomicAdd(a.total, s_total);
+}
+
+}  // namespace
+
+hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, bool sum, u64* out, u64 nb, hipStream_t s) {
+    const u32 grid = a.items ? a.items_cap : a.nparts * a.nsplit;
+    if (!a.err || (!out && (sum || !a.total))) return hipErrorInvalidValue;
+    if (sum && !a.probe.vals) return hipErrorInvalidValue;                        // the probe side carries the values
+    const u32 lds = (u32)sizeof(GjHdr) + GJ_TS * 16u;
+    void (*kern)(FjLdsJoinArgs, u64*, u64) = sum ? fj_group_join_kernel<true> : fj_group_join_kernel<false>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(GJ_NT), lds, s, a, out, nb);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_group(const FjGtArgs& a, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s) {
+    if (!a.total || !cnt || (!out_cnt && !out_sum) || (out_sum && (!sum || !pv))) return hipErrorInvalidValue;
+    if (a.np) {
+        const u64 rounds = (a.np + 1023) / 1024;
+        hipLaunchKernelGGL(fj_gt_group_probe_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
+    }
+    if (a.nb) {
+        const u64 rounds = (a.nb + 1023) / 1024;
+        hipLaunchKernelGGL(fj_gt_group_flush_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, cnt, sum, out_cnt, out_sum);
+    }
+    return hipGetLastError();
+}
+
+namespace fjh {
+
+// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
+// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  Counts are always kept (P is their sum over the build rows)
+static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, hipStream_t s,
+                             fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum) {
+    u64 cap = 64;
+    while (cap < 2 * (u64)nb) cap <<= 1;
+    FjGtArgs a{};
+    void* p;
+    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
+    const size_t acc_words = (d_sum ? 2 : 1) * (cap + 1);
+    if (get_buf(c, W_GT_VALS, acc_words * 8, &p)) return 1;
+    unsigned long long* cnt = (unsigned long long*)p;
+    unsigned long long* sum = d_sum ? cnt + cap + 1 : nullptr;
+    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
+    a.bk = bk; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    HIPCHK(hipMemsetAsync(cnt, 0, acc_words * 8, s));
+    HIPCHK(fj_launch_gt_build_first(a, false, s));
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    HIPCHK(fj_launch_gt_group(a, pv, cnt, sum, d_cnt, d_sum, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    *out_count = c->h_sc->total;
+    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
+    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
+    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
+    t->probe_phase_ms = t->join_ms;
+    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    return 0;
+}
+
+// FJ_ALGO_BUILD_ORDER (fj_join_device has checked the arguments): d_cnt[i] and / or d_sum[i] (nb words each, either may be null) for
+// every build row i; pv: the probe side's value column (np words; read only when d_sum is asked for); *out_count = P, the sum of all
+// counts.  use_radix: the partitioned plan, else the global table.
+int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, int top_bits,
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum) {
+    *out_count = 0;
+    if (nb == 0) return 0;
+    if (np == 0) {                                           // no build row has a partner
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
+        if (d_sum) HIPCHK(hipMemsetAsync(d_sum, 0, nb * 8, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        HIPCHK(hipStreamSynchronize(s));
+        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        return 0;
+    }
+    if (!use_radix) return join_group_global(c, bk, nb, pk, pv, np, s, t, out_count, d_cnt, d_sum);
+
+    const Plan plan = make_plan(nb, top_bits, false);
+    begin_plan(c);
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (clear_plan_scalars(c, s)) return 1;
+    FjLdsJoinArgs ja{};
+    PassIter bit, pit;
+    pass_init(bit, 0, true, nb, plan, top_bits);             // the build rows' positions travel through the passes
+    bit.vals_pos = true;
+    int evc = 0;
+    if (run_passes(c, bit, bk, nullptr, s, &ja.build, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    pass_init(pit, 1, d_sum != nullptr, np, plan, top_bits); // the count form alone: the keys-only pass
+    pit.want_items = true;
+    if (run_passes(c, pit, pk, d_sum ? pv : nullptr, s, &ja.probe, &evc)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
+    if (ja.probe.list) {
+        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
+    } else {                                                 // zero-pass plan: slices of the flat probe side
+        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
+        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
+    }
+    ja.err = &c->d_sc->err;
+    if (d_cnt) {
+        ja.total = &c->d_sc->total;
+        HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
+        HIPCHK(fj_launch_group_join(ja, false, d_cnt, nb, s));
+    }
+    if (d_sum) {
+        ja.total = d_cnt ? nullptr : &c->d_sc->total;        // (the count launch has P)
+        HIPCHK(hipMemsetAsync(d_sum, 0, nb * 8, s));
+        HIPCHK(fj_launch_group_join(ja, true, d_sum, nb, s));
+    }
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    end_plan(c);
+    if (!d_cnt && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
+        // sums alone over duplicated build keys: the hits are not P.  The count form once, without an output, for P
+        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, sizeof(unsigned long long), s));
+        ja.total = &c->d_sc->total;
+        HIPCHK(fj_launch_group_join(ja, false, nullptr, nb, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        if (read_scalars(c, s)) return 1;
+    }
+    plan_timings(c, plan, ja.nparts, evc, t);
+    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
+        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
+        if (join_group_global(c, bk, nb, pk, pv, np, s, &t2, out_count, d_cnt, d_sum)) return 1;
+        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
+        return 0;
+    }
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a build row's position lies beyond the build side");
+    *out_count = c->h_sc->total;
+    return 0;
+}
+
+}  // namespace fjh

@@ -180,6 +180,15 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
+    const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
+    if (bo) {                                                  // build-order aggregate join: *out_keys nb counts, *out_vals nb sums; bv = the PROBE values (np words)
+        if (many_host || left || anti || rid || full || allc || po)
+            return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
+                           many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        if (!materialize) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
+        if (!out_keys && !out_vals) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER needs an output (the counts out_keys, the sums out_vals, or both)");
+        if (np && out_vals && !bv) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER with out_vals needs build_vals (here the probe side's value column, np words)");
+    }
     if (po) {                                                  // probe-order join: *out_vals np words, *out_keys np BYTES (the mask)
         if (many_host || left || anti || full || allc)
             return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
@@ -193,7 +202,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (many_host) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
         if (!left && !full) return set_err("fj_join_host: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo);
     }
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER | FJ_ALGO_BUILD_ORDER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
@@ -227,7 +236,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // internal context, so drop it here
     if (stream_abort(c) || begin_step(c, "fj_join_host")) return 1;
     void *dbk, *dbv, *dpk;
-    if (get_buf(c, W_H_BK, nb * 8, &dbk) || get_buf(c, W_H_BV, nb * 8, &dbv) || get_buf(c, W_H_PK, np * 8, &dpk)) return 1;
+    if (get_buf(c, W_H_BK, nb * 8, &dbk) || get_buf(c, W_H_BV, (bo ? np : nb) * 8, &dbv) || get_buf(c, W_H_PK, np * 8, &dpk)) return 1;
     // pieces: >= 16 MiB (the ring's DMA and memcpy run at full rate), at most 48 of them for the probe side (the streamed
     // join takes <= 64 appends), a multiple of 4 KiB
     size_t piece = std::max<size_t>(16u << 20, (np * 8 + 47) / 48);
@@ -244,7 +253,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // A counting join of the partitioned plan starts on the first piece: the build side is copied and partitioned, then every
     // probe piece gets its first partition pass while the next one crosses PCIe (the join hides under the copy; the bloom
     // precheck is skipped here - it saves device time the copy does not leave on the critical path).
-    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti && !full && !po;
+    const bool streamed = use_radix && !materialize && nb > 0 && np > 0 && !many_host && !left && !anti && !full && !po && !bo;
     hipStream_t js = nullptr;
     auto t0 = std::chrono::steady_clock::now();
     unsigned cursor = 0;
@@ -254,6 +263,10 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (h2d_pipelined(c, dbk, bk, nb * 8, piece, &cursor, nullptr)) return 1;
     if (!streamed) {
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
+        else if (bo) {                                                          // the probe side's value column, read for the sums only
+            if (!out_vals || !np) dbv = nullptr;
+            else if (h2d_pipelined(c, dbv, bv, np * 8, piece, &cursor, nullptr)) return 1;
+        }
         else if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
         if (h2d_pipelined(c, dpk, pk, np * 8, piece, &cursor, nullptr)) return 1;
         HIPCHK(hipStreamSynchronize(c->side));
@@ -349,6 +362,22 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hv;
         joined = true;
     }
+    if (bo) {                                                                  // nb counts and / or nb sums, in build order; no emit step
+        void *dcnt = nullptr, *dsum = nullptr;
+        if ((out_keys && get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dcnt)) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dsum))) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
+                           &count, (u64*)dcnt, (u64*)dsum, nb, &t)) return 1;
+        u64* hc = out_keys ? (u64*)malloc(std::max<size_t>(nb, 1) * 8) : nullptr;
+        u64* hs = out_vals ? (u64*)malloc(std::max<size_t>(nb, 1) * 8) : nullptr;
+        if ((out_keys && !hc) || (out_vals && !hs)) { free(hc); free(hs); return set_err("fj_join_host: out of host memory for %zu rows", nb); }
+        auto t1 = std::chrono::steady_clock::now();
+        if (nb && hc) HIPCHK(hipMemcpy(hc, dcnt, nb * 8, hipMemcpyDeviceToHost));
+        if (nb && hs) HIPCHK(hipMemcpy(hs, dsum, nb * 8, hipMemcpyDeviceToHost));
+        d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (out_keys) *out_keys = hc;
+        if (out_vals) *out_vals = hs;
+        joined = true;
+    }
     if (!joined) {
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
                            &count, nullptr, nullptr, 0, &t)) return 1;
@@ -370,7 +399,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined && !outer_mat && !full && !allc && !po ? 1 : 0;
+    t.host_streamed = joined && !outer_mat && !full && !allc && !po && !bo ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
     if (full && !allc) out_count[1] = full_r;

@@ -331,6 +331,18 @@ hipError_t fj_launch_probe_order_join(const FjLdsJoinArgs& a, bool first, u64 np
 // global table built by fj_launch_gt_build_first (vals = a.out_vals != nullptr): thread i serves probe row i
 hipError_t fj_launch_gt_probe_order(const FjGtArgs& a, unsigned long long* miss_total, unsigned char* mask, hipStream_t s);
 
+// ---- build-order aggregate joins (csrc/fj_group.hip; FJ_ALGO_BUILD_ORDER of include/flashjoin.h) ------------------------------------
+// One output word per build row at the row's own position (the build chunk pool's vals plane; flat arrays: the index).  sum = false:
+// out[pos] += the probe rows of the item's slice that carry the row's key; sum = true: += the sum of their values (a.probe.vals).  out
+// holds nb words and is zeroed before the launch (several items may serve one partition: global atomic adds); out == nullptr (count
+// form only): nothing is flushed.  a.total (may be null) receives P, the sum of all counts - the sum form adds its HITS instead and
+// raises FJ_STAT_DUPS where a partition's build keys repeat (then the hits are not P).  A partition beyond the table: FJ_ERR_LDS_FULL.
+hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, bool sum, u64* out, u64 nb, hipStream_t s);
+// global table built by fj_launch_gt_build_first (vals = false): one thread per probe row adds to cnt[slot] (and sum[slot] += pv[i] when
+// out_sum is asked for), then thread i stores build row i's out_cnt[i] / out_sum[i]; cnt / sum: capacity + 1 zeroed words each (the last
+// one is the empty key's); a.total += the counts of all build rows
+hipError_t fj_launch_gt_group(const FjGtArgs& a, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s);
+
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat
 // arrays: the row index), zeroed before the launch.  Every work item ORs in the rows whose key one of its probe rows hit (mode

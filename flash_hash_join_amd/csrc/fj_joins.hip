@@ -684,8 +684,25 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
+    const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
+    const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
+    if (bo) {
+        // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
+        // d_out_keys = the counts, d_out_vals = the sums, nb words each
+        algo &= ~FJ_ALGO_BUILD_ORDER;
+        if (many || left || anti || rid || full || allc || po)
+            return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
+                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        if (!materialize) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
+        if (nb && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs an output (the counts d_out_keys, the sums d_out_vals, or both)");
+        if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu build rows (FJ_ALGO_BUILD_ORDER writes every build row)", out_capacity, nb);
+        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
+        if (np && d_out_vals && !d_bv) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER with d_out_vals needs d_build_vals (here the probe side's value column, np words)");
+        d_pv = d_bv;
+        if (!d_bv) d_bv = d_bk;                             // the counts read no value (the checks below want a pointer)
+    }
     if (po) {
         // probe-order join (csrc/fj_aligned.hip): every check before any device work, so that it holds for a null context too.
         // d_out_keys is the byte mask here: no alignment asked of it
@@ -772,6 +789,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, c3, rid, full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
         out_count[0] = c3[0]; out_count[1] = c3[1]; out_count[2] = c3[2];
         if (d_out_keys && d_out_vals && emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (bo) {                                               // one row per build row at its own position, never a pending result
+        if (join_group(c, use_radix, d_bk, nb, d_pk, d_pv, np, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals)) return 1;
+        if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;
         return 0;

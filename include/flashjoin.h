@@ -130,6 +130,26 @@ extern "C" {
  * FJ_ALGO_ALL_COPIES; materialize = 0; both outputs NULL; an output capacity below np; a misaligned d_out_vals; d_out_vals with
  * d_build_vals == NULL and no FJ_ALGO_ROW_IDS. */
 #define FJ_ALGO_PROBE_ORDER 0x800
+/* EXTENSION (no reference counterpart; csrc/fj_group.hip): OR this into `algo` together with a base value (ADAPTIVE, SCALAR or RADIX:
+ * the partitioned plan or the global HBM table exactly as for FJ_ALGO_PROBE_ORDER) and nothing else for a BUILD-ORDER aggregate join
+ * (a "group join"): one output word per BUILD row, AT the build row's position - orders per customer, the degree of every vertex, a
+ * histogram over a dictionary - without the pairs in between.  materialize = 1 only; bloom is ignored.  With nb build rows and np
+ * probe rows:
+ *   d_build_vals optional; REUSED AS THE PROBE SIDE'S VALUE COLUMN: np words (not nb), one per probe row, 16-byte aligned like every
+ *                input.  The build side has no value column in this join (its payload is the row's position).  NULL: counts only.
+ *   d_out_keys   optional; 8-byte aligned, nb words: d_out_keys[i] = the number of probe rows whose key equals d_build_keys[i].
+ *   d_out_vals   optional; 8-byte aligned, nb words: d_out_vals[i] = the sum, modulo 2^64, of d_build_vals[j] over those probe rows j,
+ *                0 when there are none.  Needs a non-NULL d_build_vals.
+ * At least one of the two is non-NULL.  Every copy of a duplicated build key receives the aggregate of that key.  *out_count = P, the
+ * sum of all counts: the number of pairs the FJ_ALGO_MANY_TO_MANY inner join counts for the same inputs.  out_capacity >= nb.  Every
+ * one of the nb positions of a requested output is defined after the call (the library zeroes what it accumulates into; the caller
+ * need not clear anything), nothing at or beyond word nb is touched.  np == 0: zeros, P = 0; nb == 0: nothing is written, P = 0.
+ * Never a pending result for fj_emit_pairs (a result that was pending is dropped).  fj_join_host: build_vals is the probe value column
+ * of np words; *out_keys / *out_vals are malloc'ed arrays of nb words, either pointer may be NULL to drop that output.  fj_timings as
+ * for FJ_ALGO_PROBE_ORDER; emit_ms = 0.
+ * Refused up front, before any device work: combined with any other flag (FJ_ALGO_ROW_IDS and FJ_ALGO_PROBE_ORDER included);
+ * materialize = 0; both outputs NULL; an output capacity below nb; a misaligned output; d_out_vals with d_build_vals == NULL. */
+#define FJ_ALGO_BUILD_ORDER 0x1000
 
 typedef struct fj_ctx fj_ctx;
 
