@@ -40,6 +40,9 @@ ALGO_FULL_OUTER = 0x100           # FJ_ALGO_FULL_OUTER: full outer join, np + r 
 ALGO_ALL_COPIES = 0x200           # FJ_ALGO_ALL_COPIES: modifier of LEFT_OUTER / FULL_OUTER - every copy of a duplicated build key; the count is (P, r, u) (extension)
 ALGO_PROBE_ORDER = 0x800          # FJ_ALGO_PROBE_ORDER: one row per probe row at the probe row's position - np values and / or an np-byte mask (extension)
 ALGO_BUILD_ORDER = 0x1000         # FJ_ALGO_BUILD_ORDER: one word per build row at the build row's position - nb counts and / or nb sums of a probe-side column (extension)
+ALGO_AGG_MIN = 0x4000             # FJ_ALGO_AGG_MIN: modifier of ALGO_BUILD_ORDER - the values output holds the minimum instead of the sum (extension)
+ALGO_AGG_MAX = 0x8000             # FJ_ALGO_AGG_MAX: ... the maximum
+ALGO_AGG_SIGNED = 0x10000         # FJ_ALGO_AGG_SIGNED: modifier of AGG_MIN / AGG_MAX - the words compare as two's-complement int64 instead of uint64
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -212,7 +215,8 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
                 hash_top_bits: int = 64, want_values: bool = True, want_mask: bool = False, want_counts: bool = True):
     """Device-resident join on torch ROCm tensors (int64 storage, bit-identical to uint64).
     want_values / want_mask: which outputs a probe-order join (ALGO_PROBE_ORDER) writes; not read otherwise.
-    ALGO_BUILD_ORDER: bv is the PROBE side's value column (len(pk) words, or None); want_counts / want_values: the counts and the sums."""
+    ALGO_BUILD_ORDER: bv is the PROBE side's value column (len(pk) words, or None); want_counts / want_values: the counts and the sums
+    (ALGO_AGG_MIN / ALGO_AGG_MAX in algo: the minima / maxima)."""
     global _last
     import torch
     L = _lib.load()
@@ -650,10 +654,11 @@ def _group_host(algo: int, bk, pk, pv, want_counts: bool):
     return int(cnt.value), float(sec.value), counts, sums
 
 
-def _group(build_keys, probe_keys, probe_values, want_counts: bool):
-    """(P, seconds, counts or None, sums or None): int64 of len(build_keys), where the inputs live"""
+def _group(build_keys, probe_keys, probe_values, want_counts: bool, agg: int = 0):
+    """(P, seconds, counts or None, sums or None): int64 of len(build_keys), where the inputs live.  agg: ALGO_AGG_* flags - the
+    second array then holds the minima / maxima"""
     build_keys, probe_keys, probe_values = (_from_dlpack_if_device(x) if x is not None else None for x in (build_keys, probe_keys, probe_values))
-    algo = ALGO_ADAPTIVE | ALGO_BUILD_ORDER
+    algo = ALGO_ADAPTIVE | ALGO_BUILD_ORDER | agg
     if _is_torch_tensor(build_keys) and build_keys.is_cuda:
         return join_device(algo, 0, 1, build_keys, probe_values, probe_keys, want_counts=want_counts)
     if _is_torch_tensor(build_keys):
@@ -678,6 +683,46 @@ def group_join_sum(build_keys, probe_keys, probe_values, return_counts: bool = F
         raise ValueError("group_join_sum: probe_values is required (group_join_count takes none)")
     P, sec, counts, sums = _group(build_keys, probe_keys, probe_values, bool(return_counts))
     return (P, sec, sums, counts) if return_counts else (P, sec, sums)
+
+
+def _group_minmax(name: str, flag: int, build_keys, probe_keys, probe_values, return_counts: bool, signed):
+    if probe_values is None:
+        raise ValueError(f"{name}: probe_values is required (group_join_count takes none)")
+    if signed is not None and not isinstance(signed, (bool, np.bool_)):
+        raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+    # the sign of the container: a NumPy uint64 column (a torch.uint64 tensor) compares unsigned, everything else signed
+    probe_values = _from_dlpack_if_device(probe_values)      # (a device array of another library: a torch tensor from here on)
+    if _is_torch_tensor(probe_values):
+        unsigned_in = str(probe_values.dtype) == "torch.uint64"
+    else:
+        probe_values = np.asarray(probe_values)
+        unsigned_in = probe_values.dtype == np.uint64
+    signed = (not unsigned_in) if signed is None else bool(signed)
+    P, sec, counts, vals = _group(build_keys, probe_keys, probe_values, bool(return_counts), flag | (ALGO_AGG_SIGNED if signed else 0))
+    if unsigned_in and not signed and isinstance(vals, np.ndarray):
+        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
+    return (P, sec, vals, counts) if return_counts else (P, sec, vals)
+
+
+def group_join_min(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None):
+    """Min form: (P, seconds, values) or, return_counts=True, (P, seconds, values, counts).  values[i] = the minimum of probe_values[j]
+    over the probe rows j whose key equals build_keys[i] ("cheapest offer per product"); every copy of a duplicated build key carries
+    the key's minimum; P = the sum of all counts.  signed=None takes the sign from the container: a NumPy uint64 value column
+    compares unsigned, everything else (NumPy int64, torch int64, DLPack) signed; True / False force it.
+    A build row WITHOUT a partner holds the aggregate's identity: 2^64 - 1 (unsigned) or 2^63 - 1 (signed).  A key whose true minimum
+    equals the identity looks the same: return_counts=True is how to tell them apart (counts[i] == 0: no partner).
+    NumPy in, NumPy out: values has the dtype of probe_values when that is uint64 / int64 and `signed` agrees with it, otherwise it is
+    the int64 storage of the words; counts is int64.  Torch ROCm tensors / DLPack are joined in place, the outputs are torch.int64 on
+    their device.  The probe side moves keys and values once; no pairs are made (csrc/fj_group.hip)."""
+    return _group_minmax("group_join_min", ALGO_AGG_MIN, build_keys, probe_keys, probe_values, return_counts, signed)
+
+
+def group_join_max(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None):
+    """Max form of group_join_min ("latest order date per customer"): values[i] = the maximum of probe_values[j] over the probe rows j
+    whose key equals build_keys[i].  A build row WITHOUT a partner holds the aggregate's identity: 0 (unsigned) or -2^63 (signed); a
+    key whose true maximum equals it looks the same, so ask for return_counts=True to tell them apart (counts[i] == 0: no partner).
+    Arguments, `signed`, containers and dtypes as for group_join_min."""
+    return _group_minmax("group_join_max", ALGO_AGG_MAX, build_keys, probe_keys, probe_values, return_counts, signed)
 
 
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
@@ -767,5 +812,6 @@ REFERENCE_EXPORTS = [
 ]
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
-              "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum"]
+              "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
+              "group_join_min", "group_join_max"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

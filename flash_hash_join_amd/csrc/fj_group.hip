@@ -17,6 +17,12 @@
 // the partition's build keys are distinct, and reports duplicates (FJ_STAT_DUPS) otherwise - the host then runs the count form once
 // without an output, for P alone.
 //
+// Min / max (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX, unsigned or FJ_ALGO_AGG_SIGNED): the same kernel with another aggregate parameter.  The
+// accumulators and the output start at the aggregate's identity (UINT64_MAX, INT64_MAX, 0, INT64_MIN) instead of zero - a memset where
+// that is a byte pattern, a fill kernel where it is not - a hit is one native 64-bit LDS atomic min / max of the value's own signedness,
+// the flush skips a slot that still holds the identity and combines the others into out[position] with the matching global atomic.  No
+// pass over the outputs afterwards.  P and the duplicates are handled as in the sum form.
+//
 // Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole join on the global HBM table (the kernels at
 // the end of this file), timings.fell_back = 1.
 #include "fj_host.h"
@@ -40,15 +46,34 @@ __device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
     return v;
 }
 
-// SUM: the accumulators take the probe rows' values (a.probe.vals), else 1 per row.  out: nb words, zeroed before the launch (nullptr,
-// count form only: nothing is flushed, the launch is for P alone).  a.total (may be null) receives P - count form: what the flush read;
-// sum form: the hits, and FJ_STAT_DUPS tells the host that this is not P.
-template <bool SUM>
+// the aggregate's identity: what an accumulator holds before its first hit and a build row without a partner receives
+template <int AGG> __device__ __forceinline__ constexpr u64 gj_identity() {
+    return AGG == FJ_GJ_MIN_U ? ~0ull : AGG == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : AGG == FJ_GJ_MAX_S ? 0x8000000000000000ull : 0ull;
+}
+
+// one atomic of the aggregate's own type on an accumulator, in LDS or in HBM (count and sum: the add; min / max: the native 64-bit
+// atomic of the value's signedness - no transform of the words, so nothing to undo afterwards)
+template <int AGG> __device__ __forceinline__ void gj_combine(u64* p, u64 v) {
+    if constexpr (AGG == FJ_GJ_MIN_U) atomicMin((unsigned long long*)p, (unsigned long long)v);
+    else if constexpr (AGG == FJ_GJ_MIN_S) atomicMin((long long*)p, (long long)v);
+    else if constexpr (AGG == FJ_GJ_MAX_U) atomicMax((unsigned long long*)p, (unsigned long long)v);
+    else if constexpr (AGG == FJ_GJ_MAX_S) atomicMax((long long*)p, (long long)v);
+    else atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
+
+// AGG (FJ_GJ_*): FJ_GJ_COUNT adds 1 per row; every other form takes the probe rows' values (a.probe.vals) - FJ_GJ_SUM adds them, the
+// four min / max forms combine them with gj_combine.  out: nb words holding the aggregate's identity before the launch (zeroed for
+// count and sum; nullptr, count form only: nothing is flushed, the launch is for P alone).  a.total (may be null) receives P - count
+// form: what the flush read; the forms with values: the hits, and FJ_STAT_DUPS tells the host that this is not P.
+template <int AGG>
 __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a, u64* __restrict__ out, u64 nb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GjHdr* hdr = reinterpret_cast<GjHdr*>(smem);
     u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(GjHdr));
     u64* acc = tkeys + GJ_TS;
+    constexpr bool SUM = AGG != FJ_GJ_COUNT;                 // the probe side carries values; hits are counted instead of counts flushed
+    constexpr bool MINMAX = AGG >= FJ_GJ_MIN_U;
+    constexpr u64 IDENT = gj_identity<AGG>();
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
     u32 p, b0 = 0, nbc, s_lo, s_hi;
@@ -66,8 +91,8 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
     else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
 
-    for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; acc[i] = 0; }
-    if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->hits = 0; hdr->empty_acc = 0; hdr->total = 0; }
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; acc[i] = IDENT; }
+    if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->hits = 0; hdr->empty_acc = IDENT; hdr->total = 0; }
     __syncthreads();
 
     // ---- build: distinct keys; a copy finds its key in place ----
@@ -101,7 +126,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     const bool has_empty = hdr->empty_cnt != 0;
 
     // ---- probe: rounds of GJ_NT * GJ_KPT rows; the next round's loads are requested before this round's lookups.  A hit adds to
-    // its slot's accumulator in LDS: no global traffic ----
+    // its slot's accumulator in LDS (min / max: combines with it): no global traffic ----
     u64 k[GJ_KPT], pv[SUM ? GJ_KPT : 1];
     u32 okm = 0, nh = 0;                                     // nh: wave-uniform count of this wave's hits (SUM)
     auto load_round = [&](u32 pc, u64 (&kk)[GJ_KPT], u64 (&vv)[SUM ? GJ_KPT : 1], u32& ok) {
@@ -132,12 +157,12 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
                 const unsigned long long add = SUM ? (unsigned long long)pv[SUM ? u : 0] : 1ull;
                 if (key == FJ_EMPTY_KEY) {
                     h = has_empty;
-                    if (h) atomicAdd((unsigned long long*)&hdr->empty_acc, add);
+                    if (h) gj_combine<AGG>(&hdr->empty_acc, add);
                 } else {
                     u32 pos = FJ_HW2(key) & (GJ_TS - 1);
                     for (;;) {                               // the build left >= 1/16 of the slots empty: always terminates
                         const u64 t = tkeys[pos];
-                        if (t == key) { h = true; atomicAdd((unsigned long long*)&acc[pos], add); break; }
+                        if (t == key) { h = true; gj_combine<AGG>(&acc[pos], add); break; }
                         if (t == FJ_EMPTY_KEY) break;
                         pos = (pos + 1) & (GJ_TS - 1);
                     }
@@ -169,11 +194,11 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
                 while (tkeys[pos] != key) pos = (pos + 1) & (GJ_TS - 1);      // (the build phase placed it)
                 v = acc[pos];
             }
-            if (v == 0) continue;
-            flushed += v;
+            if (v == IDENT) continue;                        // (count, sum: 0 adds nothing; min / max: out[] holds the identity already)
+            if (!MINMAX) flushed += v;
             if (!out) continue;
             const u64 o = a.build.vals ? a.build.vals[src] : src;             // (zero-pass plan: the flat index IS the position)
-            if (o < nb) atomicAdd((unsigned long long*)&out[o], (unsigned long long)v);   // (always: positions are 0 .. nb - 1)
+            if (o < nb) gj_combine<AGG>(&out[o], v);                          // (always: positions are 0 .. nb - 1)
             else atomicOr(a.err, FJ_ERR_OUTCAP);
         }
     }
@@ -204,7 +229,9 @@ __device__ __forceinline__ bool gj_gt_find(const u64* __restrict__ tkeys, u64 ca
     return false;
 }
 
-// thread per probe row: a hit adds 1 to cnt[slot] and (sum != nullptr) the row's value to sum[slot]
+// thread per probe row: a hit adds 1 to cnt[slot] and (sum != nullptr) combines the row's value into sum[slot]: AGG = FJ_GJ_SUM adds
+// it, the min / max forms take the typed global atomic (sum[] then starts at the aggregate's identity, not at zero)
+template <int AGG>
 __global__ __launch_bounds__(1024) void fj_gt_group_probe_kernel(FjGtArgs a, const u64* __restrict__ pv, unsigned long long* cnt, unsigned long long* sum) {
     const bool has_empty = a.flags[0] != 0;
     const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -213,11 +240,12 @@ __global__ __launch_bounds__(1024) void fj_gt_group_probe_kernel(FjGtArgs a, con
         u64 where = a.cap_mask + 1;
         if (key == FJ_EMPTY_KEY ? !has_empty : !gj_gt_find(a.tkeys, a.cap_mask, key, where)) continue;
         atomicAdd(&cnt[where], 1ull);
-        if (sum) atomicAdd(&sum[where], (unsigned long long)pv[i]);
+        if (sum) gj_combine<AGG>((u64*)&sum[where], pv[i]);
     }
 }
 
-// thread i per build row i: out_cnt[i] / out_sum[i] = the slot's accumulators (coalesced stores, every row); a.total += the counts
+// thread i per build row i: out_cnt[i] / out_sum[i] = the slot's accumulators (coalesced stores, every row: a row without a partner
+// reads what sum[] was filled with, the aggregate's identity); a.total += the counts
 __global__ __launch_bounds__(1024) void fj_gt_group_flush_kernel(FjGtArgs a, const unsigned long long* cnt, const unsigned long long* sum,
                                                                  u64* __restrict__ out_cnt, u64* __restrict__ out_sum) {
     __shared__ unsigned long long s_total;
@@ -241,25 +269,54 @@ __global__ __launch_bounds__(1024) void fj_gt_group_flush_kernel(FjGtArgs a, con
     if (tid == 0 && s_total) atomicAdd(a.total, s_total);
 }
 
+// out[i] = v for i < n: the identities that are no byte pattern (INT64_MAX, INT64_MIN)
+__global__ __launch_bounds__(256) void fj_fill64_kernel(u64* __restrict__ out, u64 v, u64 n) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = v;
+}
+
 }  // namespace
 
-hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, bool sum, u64* out, u64 nb, hipStream_t s) {
+u64 fj_group_identity(int agg) {
+    return agg == FJ_GJ_MIN_U ? ~0ull : agg == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : agg == FJ_GJ_MAX_S ? 0x8000000000000000ull : 0ull;
+}
+
+hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const u64 v = fj_group_identity(agg);
+    if (v == 0 || v == ~0ull) return hipMemsetAsync(out, v ? 0xFF : 0, n * 8, s);
+    const u64 blocks = (n + 256 * 8 - 1) / (256 * 8);                             // ~8 words per thread, at most 4096 workgroups
+    hipLaunchKernelGGL(fj_fill64_kernel, dim3((u32)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, out, v, n);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 nb, hipStream_t s) {
     const u32 grid = a.items ? a.items_cap : a.nparts * a.nsplit;
-    if (!a.err || (!out && (sum || !a.total))) return hipErrorInvalidValue;
-    if (sum && !a.probe.vals) return hipErrorInvalidValue;                        // the probe side carries the values
+    const bool vals = agg != FJ_GJ_COUNT;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S) return hipErrorInvalidValue;
+    if (!a.err || (!out && (vals || !a.total))) return hipErrorInvalidValue;
+    if (vals && !a.probe.vals) return hipErrorInvalidValue;                       // the probe side carries the values
     const u32 lds = (u32)sizeof(GjHdr) + GJ_TS * 16u;
-    void (*kern)(FjLdsJoinArgs, u64*, u64) = sum ? fj_group_join_kernel<true> : fj_group_join_kernel<false>;
+    void (*kern)(FjLdsJoinArgs, u64*, u64) =
+        agg == FJ_GJ_COUNT ? fj_group_join_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_group_join_kernel<FJ_GJ_SUM> :
+        agg == FJ_GJ_MIN_U ? fj_group_join_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_group_join_kernel<FJ_GJ_MIN_S> :
+        agg == FJ_GJ_MAX_U ? fj_group_join_kernel<FJ_GJ_MAX_U> : fj_group_join_kernel<FJ_GJ_MAX_S>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(GJ_NT), lds, s, a, out, nb);
     return hipGetLastError();
 }
 
-hipError_t fj_launch_gt_group(const FjGtArgs& a, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s) {
+hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s) {
     if (!a.total || !cnt || (!out_cnt && !out_sum) || (out_sum && (!sum || !pv))) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || (out_sum && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     if (a.np) {
         const u64 rounds = (a.np + 1023) / 1024;
-        hipLaunchKernelGGL(fj_gt_group_probe_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
+        void (*probe)(FjGtArgs, const u64*, unsigned long long*, unsigned long long*) =
+            agg == FJ_GJ_MIN_U ? fj_gt_group_probe_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_probe_kernel<FJ_GJ_MIN_S> :
+            agg == FJ_GJ_MAX_U ? fj_gt_group_probe_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_probe_kernel<FJ_GJ_MAX_S> :
+            fj_gt_group_probe_kernel<FJ_GJ_SUM>;                                  // (the count form: sum == nullptr)
+        hipLaunchKernelGGL(probe, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
     }
     if (a.nb) {
         const u64 rounds = (a.nb + 1023) / 1024;
@@ -272,8 +329,9 @@ namespace fjh {
 
 // the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
 // "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  Counts are always kept (P is their sum over the build rows)
+// agg: what d_sum receives (FJ_GJ_SUM or a min / max form); its accumulators start at the aggregate's identity, the empty key's too
 static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, hipStream_t s,
-                             fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum) {
+                             fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum, int agg) {
     u64 cap = 64;
     while (cap < 2 * (u64)nb) cap <<= 1;
     FjGtArgs a{};
@@ -288,11 +346,13 @@ static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk,
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
     HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
-    HIPCHK(hipMemsetAsync(cnt, 0, acc_words * 8, s));
+    const bool own_fill = sum && fj_group_identity(agg) != 0;                    // (sum, unsigned max: one memset serves both arrays)
+    HIPCHK(hipMemsetAsync(cnt, 0, (own_fill ? cap + 1 : acc_words) * 8, s));
+    if (own_fill) HIPCHK(fj_launch_group_fill((u64*)sum, cap + 1, agg, s));
     HIPCHK(fj_launch_gt_build_first(a, false, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    HIPCHK(fj_launch_gt_group(a, pv, cnt, sum, d_cnt, d_sum, s));
+    HIPCHK(fj_launch_gt_group(a, d_sum ? agg : FJ_GJ_COUNT, pv, cnt, sum, d_cnt, d_sum, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     *out_count = c->h_sc->total;
@@ -305,22 +365,24 @@ static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk,
 }
 
 // FJ_ALGO_BUILD_ORDER (fj_join_device has checked the arguments): d_cnt[i] and / or d_sum[i] (nb words each, either may be null) for
-// every build row i; pv: the probe side's value column (np words; read only when d_sum is asked for); *out_count = P, the sum of all
-// counts.  use_radix: the partitioned plan, else the global table.
+// every build row i; pv: the probe side's value column (np words; read only when d_sum is asked for); agg: the aggregate d_sum holds
+// (FJ_GJ_SUM, or a min / max form: FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX); *out_count = P, the sum of all counts.  use_radix: the
+// partitioned plan, else the global table.  d_sum is filled with the aggregate's identity on the stream before the kernel combines into
+// it, so every word below nb is defined by the call and a row without a partner reads the identity.
 int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, int top_bits,
-               hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum) {
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum, int agg) {
     *out_count = 0;
     if (nb == 0) return 0;
     if (np == 0) {                                           // no build row has a partner
         HIPCHK(hipEventRecord(c->ev[E_START], s));
         if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
-        if (d_sum) HIPCHK(hipMemsetAsync(d_sum, 0, nb * 8, s));
+        if (d_sum) HIPCHK(fj_launch_group_fill(d_sum, nb, agg, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         HIPCHK(hipStreamSynchronize(s));
         t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
         return 0;
     }
-    if (!use_radix) return join_group_global(c, bk, nb, pk, pv, np, s, t, out_count, d_cnt, d_sum);
+    if (!use_radix) return join_group_global(c, bk, nb, pk, pv, np, s, t, out_count, d_cnt, d_sum, agg);
 
     const Plan plan = make_plan(nb, top_bits, false);
     begin_plan(c);
@@ -348,29 +410,29 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
     if (d_cnt) {
         ja.total = &c->d_sc->total;
         HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
-        HIPCHK(fj_launch_group_join(ja, false, d_cnt, nb, s));
+        HIPCHK(fj_launch_group_join(ja, FJ_GJ_COUNT, d_cnt, nb, s));
     }
     if (d_sum) {
         ja.total = d_cnt ? nullptr : &c->d_sc->total;        // (the count launch has P)
-        HIPCHK(hipMemsetAsync(d_sum, 0, nb * 8, s));
-        HIPCHK(fj_launch_group_join(ja, true, d_sum, nb, s));
+        HIPCHK(fj_launch_group_fill(d_sum, nb, agg, s));
+        HIPCHK(fj_launch_group_join(ja, agg, d_sum, nb, s));
     }
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
     end_plan(c);
     if (!d_cnt && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
-        // sums alone over duplicated build keys: the hits are not P.  The count form once, without an output, for P
+        // sums (minima, maxima) alone over duplicated build keys: the hits are not P.  The count form once, without an output, for P
         HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, sizeof(unsigned long long), s));
         ja.total = &c->d_sc->total;
-        HIPCHK(fj_launch_group_join(ja, false, nullptr, nb, s));
+        HIPCHK(fj_launch_group_join(ja, FJ_GJ_COUNT, nullptr, nb, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
     }
     plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
         fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_group_global(c, bk, nb, pk, pv, np, s, &t2, out_count, d_cnt, d_sum)) return 1;
+        if (join_group_global(c, bk, nb, pk, pv, np, s, &t2, out_count, d_cnt, d_sum, agg)) return 1;
         t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
         return 0;
     }

@@ -316,9 +316,10 @@ int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, si
                      hipStream_t s, fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid);
 
 // ---- build-order aggregate joins (fj_group.hip): FJ_ALGO_BUILD_ORDER; d_cnt[i] and / or d_sum[i] (nb words each) for every build row i,
-// either may be null; pv: the probe side's value column (np words, read for d_sum only); *out_count = P, the sum of all counts ----
+// either may be null; pv: the probe side's value column (np words, read for d_sum only); agg: the aggregate d_sum receives, FJ_GJ_SUM or
+// one of the four min / max forms (csrc/fj_internal.h); *out_count = P, the sum of all counts ----
 int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, int top_bits,
-               hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum);
+               hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum, int agg);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

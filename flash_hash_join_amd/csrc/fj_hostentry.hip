@@ -181,12 +181,17 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
-    if (bo) {                                                  // build-order aggregate join: *out_keys nb counts, *out_vals nb sums; bv = the PROBE values (np words)
+    const int agg_flags = bo ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0;     // modifiers of FJ_ALGO_BUILD_ORDER: unknown without it
+    if (bo) {                                                  // build-order aggregate join: *out_keys nb counts, *out_vals nb sums (minima, maxima); bv = the PROBE values (np words)
+        const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (many_host || left || anti || rid || full || allc || po)
             return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
+        if (asigned && !amin && !amax) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if (!materialize) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
         if (!out_keys && !out_vals) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER needs an output (the counts out_keys, the sums out_vals, or both)");
+        if ((amin || amax) && !out_vals) return set_err("fj_join_host: FJ_ALGO_AGG_%s needs out_vals (the counts alone are the plain count form of FJ_ALGO_BUILD_ORDER)", amin ? "MIN" : "MAX");
         if (np && out_vals && !bv) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER with out_vals needs build_vals (here the probe side's value column, np words)");
     }
     if (po) {                                                  // probe-order join: *out_vals np words, *out_keys np BYTES (the mask)
@@ -202,7 +207,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (many_host) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
         if (!left && !full) return set_err("fj_join_host: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo);
     }
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER | FJ_ALGO_BUILD_ORDER)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER | FJ_ALGO_BUILD_ORDER | agg_flags)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
@@ -362,7 +367,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hv;
         joined = true;
     }
-    if (bo) {                                                                  // nb counts and / or nb sums, in build order; no emit step
+    if (bo) {                                                                  // nb counts and / or nb sums (minima, maxima), in build order; no emit step
         void *dcnt = nullptr, *dsum = nullptr;
         if ((out_keys && get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dcnt)) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dsum))) return 1;
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,

@@ -337,11 +337,18 @@ hipError_t fj_launch_gt_probe_order(const FjGtArgs& a, unsigned long long* miss_
 // holds nb words and is zeroed before the launch (several items may serve one partition: global atomic adds); out == nullptr (count
 // form only): nothing is flushed.  a.total (may be null) receives P, the sum of all counts - the sum form adds its HITS instead and
 // raises FJ_STAT_DUPS where a partition's build keys repeat (then the hits are not P).  A partition beyond the table: FJ_ERR_LDS_FULL.
-hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, bool sum, u64* out, u64 nb, hipStream_t s);
+// agg: FJ_GJ_COUNT / FJ_GJ_SUM as above; the four min / max forms combine the values with the native 64-bit atomic min / max of their
+// signedness instead of adding them - out then holds the aggregate's identity (fj_group_identity) before the launch, not zeros - and
+// report P like the sum form.
+enum { FJ_GJ_COUNT = 0, FJ_GJ_SUM = 1, FJ_GJ_MIN_U = 2, FJ_GJ_MIN_S = 3, FJ_GJ_MAX_U = 4, FJ_GJ_MAX_S = 5 };
+u64 fj_group_identity(int agg);                                         // 0, 0, UINT64_MAX, INT64_MAX, 0, INT64_MIN
+hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s);      // out[0 .. n) = the identity: a memset where it is a byte pattern, else a fill kernel
+hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 nb, hipStream_t s);
 // global table built by fj_launch_gt_build_first (vals = false): one thread per probe row adds to cnt[slot] (and sum[slot] += pv[i] when
 // out_sum is asked for), then thread i stores build row i's out_cnt[i] / out_sum[i]; cnt / sum: capacity + 1 zeroed words each (the last
-// one is the empty key's); a.total += the counts of all build rows
-hipError_t fj_launch_gt_group(const FjGtArgs& a, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s);
+// one is the empty key's); a.total += the counts of all build rows.  agg (used with out_sum): FJ_GJ_SUM, or a min / max form - sum[]
+// then holds the aggregate's identity in all capacity + 1 words before the launch
+hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

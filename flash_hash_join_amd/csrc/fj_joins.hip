@@ -685,21 +685,29 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
+    const bool amin = bo && (algo & FJ_ALGO_AGG_MIN) != 0, amax = bo && (algo & FJ_ALGO_AGG_MAX) != 0, asigned = bo && (algo & FJ_ALGO_AGG_SIGNED) != 0;
+    int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER: what d_out_vals receives
     const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
     if (bo) {
         // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
-        // d_out_keys = the counts, d_out_vals = the sums, nb words each
-        algo &= ~FJ_ALGO_BUILD_ORDER;
+        // d_out_keys = the counts, d_out_vals = the sums (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX: the minima / maxima), nb words each.
+        // The three aggregate flags are modifiers of this one: without it they are an unknown algo below
+        algo &= ~(FJ_ALGO_BUILD_ORDER | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED);
         if (many || left || anti || rid || full || allc || po)
             return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
+        if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if (!materialize) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
         if (nb && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs an output (the counts d_out_keys, the sums d_out_vals, or both)");
+        if (nb && (amin || amax) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_%s needs d_out_vals (the counts alone are the plain count form of FJ_ALGO_BUILD_ORDER)", amin ? "MIN" : "MAX");
         if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu build rows (FJ_ALGO_BUILD_ORDER writes every build row)", out_capacity, nb);
         if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
         if (np && d_out_vals && !d_bv) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER with d_out_vals needs d_build_vals (here the probe side's value column, np words)");
+        if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
+        if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
         d_pv = d_bv;
         if (!d_bv) d_bv = d_bk;                             // the counts read no value (the checks below want a pointer)
     }
@@ -794,7 +802,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         return 0;
     }
     if (bo) {                                               // one row per build row at its own position, never a pending result
-        if (join_group(c, use_radix, d_bk, nb, d_pk, d_pv, np, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals)) return 1;
+        if (join_group(c, use_radix, d_bk, nb, d_pk, d_pv, np, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, agg)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

@@ -150,6 +150,23 @@ extern "C" {
  * Refused up front, before any device work: combined with any other flag (FJ_ALGO_ROW_IDS and FJ_ALGO_PROBE_ORDER included);
  * materialize = 0; both outputs NULL; an output capacity below nb; a misaligned output; d_out_vals with d_build_vals == NULL. */
 #define FJ_ALGO_BUILD_ORDER 0x1000
+/* EXTENSION: modifiers of FJ_ALGO_BUILD_ORDER (and of nothing else: without it each of them is an unknown algo).  FJ_ALGO_AGG_MIN /
+ * FJ_ALGO_AGG_MAX: d_out_vals[i] = the MINIMUM / MAXIMUM, instead of the sum, of d_build_vals[j] over the probe rows j whose key equals
+ * d_build_keys[i] ("latest order per customer", "cheapest offer per product").  The words are compared as uint64, or as
+ * two's-complement int64 with FJ_ALGO_AGG_SIGNED.  A build row without a partner receives the aggregate's identity:
+ *   unsigned min UINT64_MAX | signed min INT64_MAX | unsigned max 0 | signed max INT64_MIN
+ * A key whose true aggregate EQUALS the identity cannot be told from "no partner" in d_out_vals alone: ask for the counts (d_out_keys)
+ * in the same call - a row has a partner exactly when its count is non-zero.  Everything else is as for the sum: d_out_keys optional
+ * and unchanged (nb counts), every copy of a duplicated build key receives the key's aggregate, *out_count = P, every requested word
+ * below nb is defined by the call alone whatever the buffer held (the library fills what it combines into; no pass over the outputs
+ * afterwards), nothing at or beyond word nb is touched, never a pending result.  np == 0: the identity in every row of d_out_vals,
+ * zero counts, P = 0; nb == 0: nothing is written.  fj_join_host: *out_vals is the malloc'ed array of nb aggregates.
+ * Refused up front, before any device work, in addition to what FJ_ALGO_BUILD_ORDER refuses: FJ_ALGO_AGG_MIN together with
+ * FJ_ALGO_AGG_MAX (one aggregate per call: call twice); FJ_ALGO_AGG_SIGNED without either (the sum is taken modulo 2^64 and has no
+ * sign); FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX with d_out_vals == NULL (the counts alone are the plain count form). */
+#define FJ_ALGO_AGG_MIN    0x4000
+#define FJ_ALGO_AGG_MAX    0x8000
+#define FJ_ALGO_AGG_SIGNED 0x10000
 
 typedef struct fj_ctx fj_ctx;
 

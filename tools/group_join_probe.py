@@ -1,16 +1,19 @@
-"""Build-order aggregate joins (group_join_count / group_join_sum, FJ_ALGO_BUILD_ORDER) on device tensors next to what a user had to
-compose before them, and next to the counting join as the floor of the shared partition passes.  One JSON line per form:
+"""Build-order aggregate joins (group_join_count / group_join_sum / group_join_min / group_join_max, FJ_ALGO_BUILD_ORDER) on device
+tensors next to what a user had to compose before them, and next to the counting join as the floor of the shared partition passes.
+One JSON line per form:
 
   (a) group_join_count, group_join_sum, group_join_sum(return_counts=True)
-  (b) the composition: join_indices(how="inner", many_to_many=True), then torch.bincount(build_idx, minlength=nb) (counts) or
-      zeros(nb).index_add_(0, build_idx, pv[probe_idx]) (sums) - the wall time of the steps between two device synchronisations,
-      and the join's own device time beside it
+  (m) group_join_min and group_join_max, signed and unsigned, and group_join_min(return_counts=True); their yardstick is the sum form
+      of (a) in the same run (identical bytes moved)
+  (b) the composition: join_indices(how="inner", many_to_many=True), then torch.bincount(build_idx, minlength=nb) (counts),
+      zeros(nb).index_add_(0, build_idx, pv[probe_idx]) (sums) or full(nb, INT64_MAX).scatter_reduce_(0, build_idx, pv[probe_idx],
+      "amin") (minima) - the wall time of the steps between two device synchronisations, and the join's own device time beside it
   (c) hash_join_count_radix: the counting join of the same sizes
-  (d) the hot-key shape: one key owns 10 % of the probe rows (workload "hot": 1M x 1B), forms (a) only
+  (d) the hot-key shape: one key owns 10 % of the probe rows (workload "hot": 1M x 1B), forms (a) and (m) only
 
-    python tools/group_join_probe.py [--workloads c3,c2,hot] [--forms a,b,c] [--steps 8] [--warmup 2]
+    python tools/group_join_probe.py [--workloads c3,c2,hot] [--forms a,m,b,c] [--steps 8] [--warmup 2]
 
-(b) and (c) call nothing this extension added, so they can be timed on a build of the parent commit through FJ_LIB_VARIANT=<name>
+(b) and (c) call nothing these extensions added, so they can be timed on a build of the parent commit through FJ_LIB_VARIANT=<name>
 (--forms b,c).  Times of (a) and (c) are device times (core_duration_sec, HIP events); (b) has torch kernels in it, so its figure is
 wall time around a synchronised region, and (a) is reported that way too ("wall_median_ms") so that the two compare like with like."""
 import argparse
@@ -48,7 +51,7 @@ def _timed(fn, want, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="c3,c2")
-    ap.add_argument("--forms", default="a,b,c")
+    ap.add_argument("--forms", default="a,m,b,c")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     args = ap.parse_args()
@@ -76,13 +79,24 @@ def main():
             n, sec, pi, bi = flash_join.join_indices(bk, pk, how="inner", many_to_many=True)
             return n, sec, torch.zeros(nb, dtype=torch.int64, device=bk.device).index_add_(0, bi, pv[pi])
 
+        def composed_min():
+            n, sec, pi, bi = flash_join.join_indices(bk, pk, how="inner", many_to_many=True)
+            return n, sec, torch.full((nb,), 2**63 - 1, dtype=torch.int64, device=bk.device).scatter_reduce_(0, bi, pv[pi], "amin")
+
         runs = []
         if "a" in forms:
             runs += [("a", "group_join_count", lambda: flash_join.group_join_count(bk, pk)),
                      ("a", "group_join_sum", lambda: flash_join.group_join_sum(bk, pk, pv)),
                      ("a", "group_join_sum_counts", lambda: flash_join.group_join_sum(bk, pk, pv, return_counts=True))]
+        if "m" in forms:
+            runs += [("m", "group_join_min", lambda: flash_join.group_join_min(bk, pk, pv)),
+                     ("m", "group_join_min_unsigned", lambda: flash_join.group_join_min(bk, pk, pv, signed=False)),
+                     ("m", "group_join_max", lambda: flash_join.group_join_max(bk, pk, pv)),
+                     ("m", "group_join_max_unsigned", lambda: flash_join.group_join_max(bk, pk, pv, signed=False)),
+                     ("m", "group_join_min_counts", lambda: flash_join.group_join_min(bk, pk, pv, return_counts=True))]
         if "b" in forms and wl != "hot":
-            runs += [("b", "join_indices_m2m+bincount", composed_count), ("b", "join_indices_m2m+index_add", composed_sum)]
+            runs += [("b", "join_indices_m2m+bincount", composed_count), ("b", "join_indices_m2m+index_add", composed_sum),
+                     ("b", "join_indices_m2m+scatter_reduce_amin", composed_min)]
         if "c" in forms:
             runs += [("c", "hash_join_count_radix", lambda: flash_join.hash_join_count_radix(bk, bv, pk))]
         for form, name, fn in runs:
