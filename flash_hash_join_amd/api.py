@@ -43,6 +43,7 @@ ALGO_BUILD_ORDER = 0x1000         # FJ_ALGO_BUILD_ORDER: one word per build row 
 ALGO_AGG_MIN = 0x4000             # FJ_ALGO_AGG_MIN: modifier of ALGO_BUILD_ORDER - the values output holds the minimum instead of the sum (extension)
 ALGO_AGG_MAX = 0x8000             # FJ_ALGO_AGG_MAX: ... the maximum
 ALGO_AGG_SIGNED = 0x10000         # FJ_ALGO_AGG_SIGNED: modifier of AGG_MIN / AGG_MAX - the words compare as two's-complement int64 instead of uint64
+ALGO_GROUP_BY = 0x40000           # FJ_ALGO_GROUP_BY: group-by on ONE relation (the build side) - its g distinct keys and one aggregate per key; AGG_* and ROW_IDS modify it (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -725,6 +726,149 @@ def group_join_max(build_keys, probe_keys, probe_values, return_counts: bool = F
     return _group_minmax("group_join_max", ALGO_AGG_MAX, build_keys, probe_keys, probe_values, return_counts, signed)
 
 
+# ---- extension: group-by on one relation (the distinct keys and one aggregate per key; csrc/fj_groupby.hip) ----------------------------
+def _trim(buf, g: int):
+    """the first g rows of an n-row device buffer: an exact-size copy unless they fill most of it (the 3/4 rule of join_device)"""
+    if buf is None:
+        return None
+    return buf[:g].clone() if g * 4 < buf.shape[0] * 3 else buf[:g]
+
+
+def _group_by(keys, values, flags: int, materialize: bool = True, want_vals: bool = True):
+    """(g, seconds, group_keys or None, aggregates or None), where the inputs live: NumPy uint64 keys and int64 words (the storage of
+    the uint64 aggregates), or torch.int64 tensors on the inputs' device.  values=None: the count form (or ALGO_ROW_IDS in flags)."""
+    global _last
+    keys, values = (_from_dlpack_if_device(x) if x is not None else None for x in (keys, values))
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | flags
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    if _is_torch_tensor(keys) and keys.is_cuda:
+        import torch
+        k = _dev_tensor(keys, "keys")
+        v = _dev_tensor(values, "values") if values is not None else None
+        if v is not None and v.numel() != k.numel():
+            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
+        n = k.numel()
+        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(n, dtype=torch.int64, device=k.device) if materialize else None
+        ov = torch.empty(n, dtype=torch.int64, device=k.device) if materialize and want_vals else None
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, 0, int(materialize), k.data_ptr(), v.data_ptr() if v is not None else None, n, None, 0, stream, 64,
+                                   ctypes.byref(cnt), ok.data_ptr() if ok is not None else None, ov.data_ptr() if ov is not None else None,
+                                   n if materialize else 0, ctypes.byref(t)))
+        _last = t
+        g = int(cnt.value)
+        return g, t.total_ms * 1e-3, _trim(ok, g), _trim(ov, g)
+    if _is_torch_tensor(keys):
+        keys, values = (x.numpy() if x is not None else None for x in (keys, values))
+    k = _as_u64_host(keys, "keys")
+    v = _as_u64_host(values, "values") if values is not None else None
+    if v is not None and v.size != k.size:
+        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, int(materialize), k.ctypes.data, v.ctypes.data if v is not None else None, k.size, None, 0,
+                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok) if materialize else None,
+                         ctypes.byref(ov) if materialize and want_vals else None))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(g,)).copy() if g else np.empty(0, np.uint64))
+        gk = take(ok) if materialize else None
+        gv = take(ov).view(np.int64) if materialize and want_vals else None
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    return g, float(sec.value), gk, gv
+
+
+def _align_by_key(keys_a, keys_b, vals_b):
+    """vals_b, given in the order of keys_b, in the order of keys_a (the same set of distinct keys)"""
+    if _is_torch_tensor(keys_a):
+        import torch
+        out = torch.empty_like(vals_b)
+        out[torch.argsort(keys_a)] = vals_b[torch.argsort(keys_b)]
+        return out
+    out = np.empty_like(vals_b)
+    out[np.argsort(keys_a, kind="stable")] = vals_b[np.argsort(keys_b, kind="stable")]
+    return out
+
+
+def unique(keys, return_index: bool = False, return_counts: bool = False):
+    """The distinct keys of one relation (DISTINCT; torch.unique / np.unique without the sort): (g, seconds, unique_keys) followed by
+    first_index if return_index (the 0-based position of every key's FIRST occurrence, int64) and by counts if return_counts (int64).
+    The order of the keys is unspecified; the extras are aligned with unique_keys.  Either extra alone is one call; asking for BOTH
+    makes two calls (one aggregate per call) and aligns the second by key with two argsorts of g keys - `seconds` is the sum of both.
+    NumPy in: unique_keys is uint64; torch ROCm tensors / DLPack are grouped in place, every output is torch.int64 on their device."""
+    if return_index:
+        g, sec, gk, idx = _group_by(keys, None, ALGO_ROW_IDS)
+        if not return_counts:
+            return g, sec, gk, idx
+        g2, sec2, gk2, counts = _group_by(keys, None, 0)
+        return g, sec + sec2, gk, idx, _align_by_key(gk, gk2, counts)
+    if return_counts:
+        return _group_by(keys, None, 0)
+    return _group_by(keys, None, 0, want_vals=False)[:3]
+
+
+def distinct_count(keys):
+    """COUNT(DISTINCT keys): (g, seconds).  A keys-only pass; nothing is written."""
+    return _group_by(keys, None, 0, materialize=False)[:2]
+
+
+def group_by_count(keys):
+    """GROUP BY keys, COUNT(*): (g, seconds, group_keys, counts) - the g distinct keys in unspecified order and the number of rows of
+    each, int64, aligned with group_keys.  The list of groups the group_join_* functions ask for, made inside the library."""
+    return _group_by(keys, None, 0)
+
+
+def group_by_sum(keys, values):
+    """GROUP BY keys, SUM(values): (g, seconds, group_keys, sums), sums[i] = the sum modulo 2^64 of values[j] over the rows j whose
+    key is group_keys[i] (int64 storage of the uint64 words).  values has one word per row."""
+    if values is None:
+        raise ValueError("group_by_sum: values is required (group_by_count takes none)")
+    return _group_by(keys, values, 0)
+
+
+def _group_by_minmax(name: str, flag: int, keys, values, signed):
+    if values is None:
+        raise ValueError(f"{name}: values is required")
+    if signed is not None and not isinstance(signed, (bool, np.bool_)):
+        raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+    values = _from_dlpack_if_device(values)
+    if _is_torch_tensor(values):
+        if values.dtype.is_floating_point:
+            raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers)")
+        unsigned_in = str(values.dtype) == "torch.uint64"
+    else:
+        values = np.asarray(values)
+        if values.dtype.kind not in "iub":
+            raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers)")
+        unsigned_in = values.dtype == np.uint64
+    signed = (not unsigned_in) if signed is None else bool(signed)
+    g, sec, gk, vals = _group_by(keys, values, flag | (ALGO_AGG_SIGNED if signed else 0))
+    if unsigned_in and not signed and isinstance(vals, np.ndarray):
+        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
+    return g, sec, gk, vals
+
+
+def group_by_min(keys, values, signed=None):
+    """GROUP BY keys, MIN(values): (g, seconds, group_keys, values).  signed=None takes the sign from the container, as group_join_min
+    does: a NumPy uint64 column compares unsigned, everything else signed; True / False force it.  Every group has a row, so no
+    identity appears.  NumPy in: the minima have the dtype of `values` when that is uint64 / int64 and `signed` agrees, else int64."""
+    return _group_by_minmax("group_by_min", ALGO_AGG_MIN, keys, values, signed)
+
+
+def group_by_max(keys, values, signed=None):
+    """GROUP BY keys, MAX(values): the max form of group_by_min."""
+    return _group_by_minmax("group_by_max", ALGO_AGG_MAX, keys, values, signed)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
@@ -813,5 +957,5 @@ REFERENCE_EXPORTS = [
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
-              "group_join_min", "group_join_max"]
+              "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

@@ -26,40 +26,11 @@
 // Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole join on the global HBM table (the kernels at
 // the end of this file), timings.fell_back = 1.
 #include "fj_host.h"
+#include "fj_group_dev.h"
 
 namespace {
 
-constexpr u32 GJ_NT = 1024, GJ_KPT = 8, GJ_ROUND_CHUNKS = GJ_NT * GJ_KPT / FJ_CHUNK;
-constexpr u32 GJ_TS = 8192, GJ_LIMIT = GJ_TS - GJ_TS / 16;
 struct GjHdr { u32 full, dups, empty_cnt, nkeys, hits, pad0; u64 empty_acc, total; };
-
-__device__ __forceinline__ u32 gj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
-
-__device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (u64)__shfl_xor((unsigned long long)v, d, 64);
-    return v;
-}
-
-// the aggregate's identity: what an accumulator holds before its first hit and a build row without a partner receives
-template <int AGG> __device__ __forceinline__ constexpr u64 gj_identity() {
-    return AGG == FJ_GJ_MIN_U ? ~0ull : AGG == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : AGG == FJ_GJ_MAX_S ? 0x8000000000000000ull : 0ull;
-}
-
-// one atomic of the aggregate's own type on an accumulator, in LDS or in HBM (count and sum: the add; min / max: the native 64-bit
-// atomic of the value's signedness - no transform of the words, so nothing to undo afterwards)
-template <int AGG> __device__ __forceinline__ void gj_combine(u64* p, u64 v) {
-    if constexpr (AGG == FJ_GJ_MIN_U) atomicMin((unsigned long long*)p, (unsigned long long)v);
-    else if constexpr (AGG == FJ_GJ_MIN_S) atomicMin((long long*)p, (long long)v);
-    else if constexpr (AGG == FJ_GJ_MAX_U) atomicMax((unsigned long long*)p, (unsigned long long)v);
-    else if constexpr (AGG == FJ_GJ_MAX_S) atomicMax((long long*)p, (long long)v);
-    else atomicAdd((unsigned long long*)p, (unsigned long long)v);
-}
 
 // AGG (FJ_GJ_*): FJ_GJ_COUNT adds 1 per row; every other form takes the probe rows' values (a.probe.vals) - FJ_GJ_SUM adds them, the
 // four min / max forms combine them with gj_combine.  out: nb words holding the aggregate's identity before the launch (zeroed for
@@ -216,19 +187,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     }
 }
 
-// ---- the global-table form.  The table is fj_gt_build_first_kernel's, keys only (csrc/fj_join.hip: group-aligned home slot, linear
-// probing, the raw empty key out of band); the accumulators are arrays of capacity + 1 words, the last one the empty key's ----
-__device__ __forceinline__ bool gj_gt_find(const u64* __restrict__ tkeys, u64 cap_mask, u64 key, u64& where) {
-    u64 pos = (fj_hash64(key) & cap_mask) & ~(u64)(FJ_GT_GROUP - 1);
-    for (u64 step = 0; step <= cap_mask; ++step) {
-        const u64 t = tkeys[pos];
-        if (t == key) { where = pos; return true; }
-        if (t == FJ_EMPTY_KEY) return false;
-        pos = (pos + 1) & cap_mask;
-    }
-    return false;
-}
-
+// ---- the global-table form (gj_gt_find: csrc/fj_group_dev.h) ----
 // thread per probe row: a hit adds 1 to cnt[slot] and (sum != nullptr) combines the row's value into sum[slot]: AGG = FJ_GJ_SUM adds
 // it, the min / max forms take the typed global atomic (sum[] then starts at the aggregate's identity, not at zero)
 template <int AGG>

@@ -1,0 +1,312 @@
+// fj_groupby.hip -- group-by on ONE relation (an EXTENSION: FJ_ALGO_GROUP_BY, include/flashjoin.h): the distinct keys of a relation,
+// densely packed, and optionally one aggregate per key - its row count, the sum / minimum / maximum of a value column, or the position
+// of its first occurrence (FJ_ALGO_ROW_IDS: an unsigned minimum over the positions the first pass makes).  DISTINCT, COUNT(DISTINCT)
+// and GROUP BY with one aggregate; the reference's first step, "deduplicate the build keys" (hash_join.cpp:125), handed out.
+//
+// The relation goes through the build side's partition passes (keys only for the distinct and count forms, with the value column or
+// the rows' positions otherwise).  One work item is one WHOLE final partition - two slices of a partition would each emit the same
+// key - and the kernel builds its table from the stream it aggregates: every row inserts or finds its key in the 8192-slot LDS table
+// (CAS, linear probing) and combines into the slot's 8-byte accumulator with one LDS atomic (gj_combine, csrc/fj_group_dev.h).  Then
+// the workgroup reserves its g_p output rows on the call's cursor with ONE global atomic and sweeps the table: occupied slots take
+// ranks inside the range by wave ballot + popcount on an LDS cursor.  The emit is the only phase that writes to HBM; the order of
+// the groups is whatever the cursor and the slots make it.
+//
+// Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition, and its LDS atomics hit
+// one address; fewer than ~256 distinct keys leave CUs idle.  Correct at any distribution (DESIGN.md "Group-by on one relation").
+//
+// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than GJ_LIMIT distinct keys) -> the
+// whole call on the global HBM table (the kernels at the end of this file) from cursor 0, timings.fell_back = 1.
+#include "fj_host.h"
+#include "fj_group_dev.h"
+
+namespace {
+
+struct GbHdr { u32 full, has_empty, nkeys, cursor; u64 empty_acc, base; };      // 32 B: the key slots behind it stay 16-byte aligned
+
+// AGG (FJ_GJ_*): FJ_GJ_COUNT adds 1 per row; every other form combines the row's value - a.rel.vals, or the row's flat index where the
+// zero-pass plan carries positions (FJ_ALGO_ROW_IDS: FJ_GJ_MIN_U over them).  EMIT = false: only g is added to a.cursor (COUNT(DISTINCT):
+// no accumulator is touched, no output pointer read).  a.out_vals == nullptr: the keys alone.
+template <int AGG, bool EMIT>
+__global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_kernel(FjGroupByArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    GbHdr* hdr = reinterpret_cast<GbHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(GbHdr));
+    u64* acc = tkeys + GJ_TS;
+    constexpr bool VALS = AGG != FJ_GJ_COUNT;
+    constexpr u64 IDENT = gj_identity<AGG>();
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 p = blockIdx.x;
+    u32 b0 = 0, nbc;
+    if (a.rel.list) { b0 = a.rel.boff[p]; nbc = a.rel.boff[p + 1] - b0; }
+    else nbc = (u32)((a.rel.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    if (nbc == 0) return;
+
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; if (EMIT) acc[i] = IDENT; }
+    if (tid == 0) { hdr->full = 0; hdr->has_empty = 0; hdr->nkeys = 0; hdr->cursor = 0; hdr->empty_acc = IDENT; hdr->base = 0; }
+    __syncthreads();
+
+    // ---- stream: rounds of GJ_NT * GJ_KPT rows; the next round's loads are requested before this round's inserts.  No global
+    // store, no barrier inside the loop ----
+    u64 k[GJ_KPT], pv[VALS ? GJ_KPT : 1];
+    u32 okm = 0;
+    auto load_round = [&](u32 c0, u64 (&kk)[GJ_KPT], u64 (&vv)[VALS ? GJ_KPT : 1], u32& ok) {
+        ok = 0;
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) {
+            const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            kk[u] = 0; if (VALS) vv[VALS ? u : 0] = 0;
+            if (c >= nbc) continue;
+            const u32 e = gj_entry(a.rel, b0 + c);
+            if (off >= FJ_LIST_CNT(e)) continue;
+            const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            kk[u] = a.rel.keys[src];
+            if (VALS) vv[VALS ? u : 0] = a.rel.vals ? a.rel.vals[src] : src;      // (zero-pass plan, positions: the flat index IS the position)
+            ok |= 1u << u;
+        }
+    };
+    load_round(0, k, pv, okm);
+    for (u32 c0 = 0; c0 < nbc; c0 += GJ_ROUND_CHUNKS) {
+        u64 kn[GJ_KPT], pvn[VALS ? GJ_KPT : 1];
+        u32 okn = 0;
+        if (c0 + GJ_ROUND_CHUNKS < nbc) load_round(c0 + GJ_ROUND_CHUNKS, kn, pvn, okn);
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) {
+            if (!((okm >> u) & 1u)) continue;
+            const u64 key = a.rel.list ? k[u] : fj_key_mix(k[u]);                 // chunk pools hold mixed keys, flat arrays raw ones
+            const u64 v = VALS ? pv[VALS ? u : 0] : 1ull;
+            if (key == FJ_EMPTY_KEY) {                       // the empty marker is never stored in the table
+                hdr->has_empty = 1;
+                if (EMIT) gj_combine<AGG>(&hdr->empty_acc, v);
+                continue;
+            }
+            if (*(volatile u32*)&hdr->full) continue;        // the item is lost already: the rest of its rows do no table work
+            u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+            bool placed = false;
+            for (u32 step = 0; step < GJ_TS; ++step) {
+                u64 t = tkeys[pos];                          // (a slot never changes once it holds a key: a stale read costs a CAS at most)
+                if (t == FJ_EMPTY_KEY) {
+                    t = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+                    if (t == FJ_EMPTY_KEY) {
+                        if (atomicAdd(&hdr->nkeys, 1u) >= GJ_LIMIT) hdr->full = 1;
+                        t = key;
+                    }
+                }
+                if (t == key) { placed = true; break; }
+                pos = (pos + 1) & (GJ_TS - 1);
+            }
+            if (!placed) hdr->full = 1;
+            else if (EMIT) gj_combine<AGG>(&acc[pos], v);
+        }
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) { k[u] = kn[u]; if (VALS) pv[VALS ? u : 0] = pvn[VALS ? u : 0]; }
+        okm = okn;
+    }
+    __syncthreads();
+    if (hdr->full) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }     // nothing written: the host re-runs the call on the HBM table
+
+    // ---- emit: one global atomic reserves [o, o + g_p); the table's occupied slots take ranks inside it, the marker key the last ----
+    const u32 nk = hdr->nkeys;
+    const bool has_empty = hdr->has_empty != 0;
+    if (tid == 0) hdr->base = (u64)atomicAdd(a.cursor, (unsigned long long)(nk + (has_empty ? 1u : 0u)));
+    if (!EMIT) return;
+    __syncthreads();
+    const u64 o = hdr->base;
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) {               // (GJ_TS is a multiple of GJ_NT: whole waves every round)
+        const u64 key = tkeys[i];
+        const bool occ = key != FJ_EMPTY_KEY;
+        const unsigned long long m = __ballot(occ);
+        u32 wbase = 0;
+        if (lane == 0 && m) wbase = atomicAdd(&hdr->cursor, (u32)__popcll(m));
+        wbase = __shfl(wbase, 0, 64);
+        if (!occ) continue;
+        const u64 row = o + wbase + (u32)__popcll(m & ((1ull << lane) - 1ull));
+        if (row < a.out_capacity) {
+            a.out_keys[row] = fj_key_unmix(key);
+            if (a.out_vals) a.out_vals[row] = acc[i];
+        } else atomicOr(a.err, FJ_ERR_OUTCAP);
+    }
+    if (tid == 0 && has_empty) {
+        const u64 row = o + nk;
+        if (row < a.out_capacity) {
+            a.out_keys[row] = fj_key_unmix(FJ_EMPTY_KEY);
+            if (a.out_vals) a.out_vals[row] = hdr->empty_acc;
+        } else atomicOr(a.err, FJ_ERR_OUTCAP);
+    }
+}
+
+// ---- the global-table form.  The table is fj_gt_build_first_kernel's (csrc/fj_join.hip: raw keys, the raw empty key out of band);
+// the accumulators are capacity + 1 words holding the aggregate's identity, the last one the empty key's ----
+// thread per row of the relation: one typed global atomic on the slot of the row's key (the build placed every key)
+template <int AGG>
+__global__ __launch_bounds__(1024) void fj_gt_group_by_combine_kernel(FjGtArgs a, const u64* __restrict__ vals, u64* acc) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < a.nb; i += stride) {
+        const u64 key = a.bk[i];
+        u64 where = a.cap_mask + 1;
+        if (key != FJ_EMPTY_KEY && !gj_gt_find(a.tkeys, a.cap_mask, key, where)) continue;
+        gj_combine<AGG>(&acc[where], AGG == FJ_GJ_COUNT ? 1ull : vals[i]);
+    }
+}
+
+// the capacity + 1 slots, compacted: an occupied slot's (key, accumulator) goes to the row a wave-aggregated cursor hands out (one
+// global atomic per wave that holds a key).  out_keys == nullptr: the cursor alone (COUNT(DISTINCT)); acc == nullptr: the keys alone
+__global__ __launch_bounds__(1024) void fj_gt_group_by_sweep_kernel(FjGtArgs a, const u64* __restrict__ acc, u64* __restrict__ out_keys,
+                                                                    u64* __restrict__ out_vals, u64 out_capacity, unsigned long long* cursor, u32* err) {
+    const u64 cap = a.cap_mask + 1;
+    const bool has_empty = a.flags[0] != 0;
+    const u32 lane = threadIdx.x & 63;
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 w0 = (u64)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); w0 <= cap; w0 += stride) {     // (uniform per wave)
+        const u64 i = w0 + lane;
+        const u64 key = i < cap ? a.tkeys[i] : FJ_EMPTY_KEY;
+        const bool occ = i < cap ? key != FJ_EMPTY_KEY : (i == cap && has_empty);
+        const unsigned long long m = __ballot(occ);
+        if (!m) continue;
+        unsigned long long wbase = 0;
+        if (lane == 0) wbase = atomicAdd(cursor, (unsigned long long)__popcll(m));
+        wbase = __shfl(wbase, 0, 64);
+        if (!occ || !out_keys) continue;
+        const u64 row = wbase + (u32)__popcll(m & ((1ull << lane) - 1ull));
+        if (row < out_capacity) {
+            out_keys[row] = key;
+            if (out_vals) out_vals[row] = acc[i];
+        } else atomicOr(err, FJ_ERR_OUTCAP);
+    }
+}
+
+template <bool EMIT> hipError_t launch_lds(const FjGroupByArgs& a, int agg, hipStream_t s) {
+    const u32 lds = (u32)sizeof(GbHdr) + GJ_TS * 16u;
+    void (*kern)(FjGroupByArgs);
+    if constexpr (EMIT)
+        kern = agg == FJ_GJ_COUNT ? fj_group_by_kernel<FJ_GJ_COUNT, true> : agg == FJ_GJ_SUM ? fj_group_by_kernel<FJ_GJ_SUM, true> :
+               agg == FJ_GJ_MIN_U ? fj_group_by_kernel<FJ_GJ_MIN_U, true> : agg == FJ_GJ_MIN_S ? fj_group_by_kernel<FJ_GJ_MIN_S, true> :
+               agg == FJ_GJ_MAX_U ? fj_group_by_kernel<FJ_GJ_MAX_U, true> : fj_group_by_kernel<FJ_GJ_MAX_S, true>;
+    else kern = fj_group_by_kernel<FJ_GJ_COUNT, false>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(a.nparts), dim3(GJ_NT), lds, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t fj_launch_group_by(const FjGroupByArgs& a, int agg, bool emit, hipStream_t s) {
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || !a.cursor || !a.err || !a.nparts) return hipErrorInvalidValue;
+    if (emit && !a.out_keys) return hipErrorInvalidValue;
+    if (!emit && agg != FJ_GJ_COUNT) return hipErrorInvalidValue;                 // (the total needs no aggregate)
+    return emit ? launch_lds<true>(a, agg, s) : launch_lds<false>(a, agg, s);
+}
+
+hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s) {
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
+    if (!a.nb) return hipSuccess;
+    const u64 rounds = (a.nb + 1023) / 1024;
+    void (*kern)(FjGtArgs, const u64*, u64*) =
+        agg == FJ_GJ_COUNT ? fj_gt_group_by_combine_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM> :
+        agg == FJ_GJ_MIN_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_S> :
+        agg == FJ_GJ_MAX_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_U> : fj_gt_group_by_combine_kernel<FJ_GJ_MAX_S>;
+    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, vals, acc);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
+                                       unsigned long long* cursor, u32* err, hipStream_t s) {
+    if (!cursor || !err || (out_vals && (!acc || !out_keys))) return hipErrorInvalidValue;
+    const u64 rounds = (a.cap_mask + 2 + 1023) / 1024;
+    hipLaunchKernelGGL(fj_gt_group_by_sweep_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, acc, out_keys, out_vals,
+                       out_capacity, cursor, err);
+    return hipGetLastError();
+}
+
+namespace fjh {
+
+// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
+// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts at 0: whatever an
+// abandoned partitioned attempt wrote is overwritten.  rid: the table build itself keeps every key's first row index
+// (fj_gt_build_first_kernel with values), so the accumulators are its value plane and no combine pass runs.
+static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
+                           u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid) {
+    u64 cap = 64;
+    while (cap < 2 * (u64)nb) cap <<= 1;
+    FjGtArgs a{};
+    void* p;
+    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
+    u64* acc = nullptr;
+    if (d_ov) { if (get_buf(c, W_GT_VALS, (cap + 1) * 8, &p)) return 1; acc = (u64*)p; }
+    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
+    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    if (acc && rid) {                                        // (row index minimum: all ones at rest; the empty key's word is the table's last)
+        a.tvals = acc; a.empty_val = acc + cap;
+        HIPCHK(hipMemsetAsync(acc, 0xFF, (cap + 1) * 8, s));
+        HIPCHK(fj_launch_gt_build_first(a, true, s));
+    } else {
+        HIPCHK(fj_launch_gt_build_first(a, false, s));
+        if (acc) {
+            HIPCHK(fj_launch_group_fill(acc, cap + 1, agg, s));
+            HIPCHK(fj_launch_gt_group_by_combine(a, agg, bv, acc, s));
+        }
+    }
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    HIPCHK(fj_launch_gt_group_by_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
+    *out_count = c->h_sc->total;
+    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
+    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
+    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
+    t->probe_phase_ms = t->join_ms;
+    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    return 0;
+}
+
+// FJ_ALGO_GROUP_BY (fj_join_device has checked the arguments): the g distinct keys of bk[0 .. nb) in d_ok and their aggregates in d_ov
+// (null: the keys alone), g <= nb <= cap_out rows; d_ok == nullptr: *out_count = g alone (COUNT(DISTINCT), a keys-only pass).  agg:
+// FJ_GJ_COUNT (bv is not read), FJ_GJ_SUM or a min / max form over bv; rid: the first occurrence's position instead (bv is not read).
+// use_radix: the partitioned plan, else the global table.
+int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+             u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid) {
+    *out_count = 0;
+    if (nb == 0) return 0;
+    if (!d_ok) d_ov = nullptr;
+    if (!d_ov) { agg = FJ_GJ_COUNT; rid = false; }           // no aggregate leaves the call: nothing travels beside the keys
+    if (rid) agg = FJ_GJ_MIN_U;
+    if (!use_radix) return group_by_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, agg, rid);
+
+    const Plan plan = make_plan(nb, top_bits, false);
+    begin_plan(c);
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (clear_plan_scalars(c, s)) return 1;
+    FjGroupByArgs ga{};
+    PassIter it;
+    pass_init(it, 0, agg != FJ_GJ_COUNT, nb, plan, top_bits);
+    it.vals_pos = rid;                                       // the rows' positions travel through the passes
+    if (run_passes(c, it, bk, (agg != FJ_GJ_COUNT && !rid) ? bv : nullptr, s, &ga.rel, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
+    ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
+    HIPCHK(fj_launch_group_by(ga, agg, d_ok != nullptr, s));
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    end_plan(c);
+    plan_timings(c, plan, ga.nparts, 0, t);
+    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
+    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
+        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
+        if (group_by_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, agg, rid)) return 1;
+        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
+        return 0;
+    }
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
+    *out_count = c->h_sc->total;
+    return 0;
+}
+
+}  // namespace fjh

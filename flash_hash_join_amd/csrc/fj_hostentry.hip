@@ -181,7 +181,20 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
-    const int agg_flags = bo ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0;     // modifiers of FJ_ALGO_BUILD_ORDER: unknown without it
+    const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
+    const int agg_flags = (bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0;     // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
+    if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
+        const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
+        if (many_host || left || anti || full || allc || po || bo)
+            return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
+                           many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+        if (pk || np) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
+        if (asigned && !amin && !amax) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
+        if ((amin || amax) && nb && !bv) return set_err("fj_join_host: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
+        if (rid && (amin || amax)) return set_err("fj_join_host: FJ_ALGO_ROW_IDS cannot be combined with FJ_ALGO_AGG_%s under FJ_ALGO_GROUP_BY (the first occurrence's position IS the aggregate)", amin ? "MIN" : "MAX");
+        if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS with FJ_ALGO_GROUP_BY needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+    }
     if (bo) {                                                  // build-order aggregate join: *out_keys nb counts, *out_vals nb sums (minima, maxima); bv = the PROBE values (np words)
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (many_host || left || anti || rid || full || allc || po)
@@ -207,7 +220,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (many_host) return set_err("fj_join_host: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
         if (!left && !full) return set_err("fj_join_host: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo);
     }
-    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER | FJ_ALGO_BUILD_ORDER | agg_flags)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
+    if (algo < 0 || (algo & ~(FJ_ALGO_MANY_TO_MANY | FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI | FJ_ALGO_ROW_IDS | FJ_ALGO_FULL_OUTER | FJ_ALGO_ALL_COPIES | FJ_ALGO_PROBE_ORDER | FJ_ALGO_BUILD_ORDER | FJ_ALGO_GROUP_BY | agg_flags)) > 2) return set_err("fj_join_host: unknown algo %d", algo);
     if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
     if (left && anti) return set_err("fj_join_host: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
     if ((left || anti) && many_host) return set_err("fj_join_host: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
@@ -268,6 +281,10 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (h2d_pipelined(c, dbk, bk, nb * 8, piece, &cursor, nullptr)) return 1;
     if (!streamed) {
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
+        else if (gb) {                                                          // the relation's value column: only the sum / min / max forms that return it read it
+            if (!bv) dbv = nullptr;
+            else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
+        }
         else if (bo) {                                                          // the probe side's value column, read for the sums only
             if (!out_vals || !np) dbv = nullptr;
             else if (h2d_pipelined(c, dbv, bv, np * 8, piece, &cursor, nullptr)) return 1;
@@ -383,6 +400,25 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hs;
         joined = true;
     }
+    if (gb) {                                                                  // g <= nb keys and aggregates; exactly g rows go back
+        void *dok = nullptr, *dov = nullptr;
+        if (materialize && (get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dok) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dov)))) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
+                           &count, (u64*)dok, (u64*)dov, nb, &t)) return 1;
+        if (materialize) {
+            const size_t g = (size_t)count;
+            u64* hk = out_keys ? (u64*)malloc(std::max<size_t>(g, 1) * 8) : nullptr;
+            u64* hv = out_vals ? (u64*)malloc(std::max<size_t>(g, 1) * 8) : nullptr;
+            if ((out_keys && !hk) || (out_vals && !hv)) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", g); }
+            auto t1 = std::chrono::steady_clock::now();
+            if (g && hk) HIPCHK(hipMemcpy(hk, dok, g * 8, hipMemcpyDeviceToHost));
+            if (g && hv) HIPCHK(hipMemcpy(hv, dov, g * 8, hipMemcpyDeviceToHost));
+            d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+            if (out_keys) *out_keys = hk;
+            if (out_vals) *out_vals = hv;
+        }
+        joined = true;
+    }
     if (!joined) {
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, (const u64*)dpk, np, js, 64,
                            &count, nullptr, nullptr, 0, &t)) return 1;
@@ -404,7 +440,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // h2d_ms: wall time from the first byte copied to the last piece enqueued + joined when the join was streamed under the
     // copy (then total_ms, the device-resident time, lies INSIDE it), else the copies alone
     t.h2d_ms = h2d; t.d2h_ms = d2h;
-    t.host_streamed = joined && !outer_mat && !full && !allc && !po && !bo ? 1 : 0;
+    t.host_streamed = joined && !outer_mat && !full && !allc && !po && !bo && !gb ? 1 : 0;
     last_timings() = t;
     if (out_count) *out_count = count;
     if (full && !allc) out_count[1] = full_r;

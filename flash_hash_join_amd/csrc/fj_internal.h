@@ -350,6 +350,30 @@ hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 n
 // then holds the aggregate's identity in all capacity + 1 words before the launch
 hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s);
 
+// ---- group-by on one relation (csrc/fj_groupby.hip; FJ_ALGO_GROUP_BY of include/flashjoin.h) ------------------------------------------
+// One workgroup per final partition of `rel` (chunk lists with boff per partition; flat arrays: one partition): the partition's distinct
+// keys go to out_keys, un-mixed, and - out_vals != nullptr - their aggregates beside them, in the rows [o, o + g_p) that ONE atomic on
+// `cursor` reserves; the cursor ends as g.  agg: FJ_GJ_COUNT (1 per row), or FJ_GJ_SUM / a min / max form over rel.vals (flat arrays
+// with rel.vals == nullptr: over the rows' indices - the first occurrence's position is FJ_GJ_MIN_U of them).  emit = false
+// (FJ_GJ_COUNT only): the cursor alone.  A partition of more distinct keys than the table takes writes nothing and raises
+// FJ_ERR_LDS_FULL; a row at or beyond out_capacity is not written (FJ_ERR_OUTCAP).
+struct FjGroupByArgs {
+    FjChunkSet rel;
+    u32 nparts;
+    u64* out_keys; u64* out_vals;
+    u64 out_capacity;
+    unsigned long long* cursor;  // device scalar, zeroed before the launch
+    u32* err;
+};
+hipError_t fj_launch_group_by(const FjGroupByArgs& a, int agg, bool emit, hipStream_t s);
+// global table built by fj_launch_gt_build_first (vals = false) over a.bk: one thread per row combines into acc[slot] (capacity + 1 words
+// holding the aggregate's identity, the last one the empty key's) - 1 per row (FJ_GJ_COUNT) or vals[i]
+hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s);
+// ... and its capacity + 1 slots compacted into out rows [0, *cursor): (key, acc[slot]); out_vals == nullptr: the keys alone; out_keys
+// == nullptr: the cursor alone.  Rows at or beyond out_capacity are not written (FJ_ERR_OUTCAP)
+hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
+                                       unsigned long long* cursor, u32* err, hipStream_t s);
+
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat
 // arrays: the row index), zeroed before the launch.  Every work item ORs in the rows whose key one of its probe rows hit (mode

@@ -685,11 +685,39 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
-    const bool amin = bo && (algo & FJ_ALGO_AGG_MIN) != 0, amax = bo && (algo & FJ_ALGO_AGG_MAX) != 0, asigned = bo && (algo & FJ_ALGO_AGG_SIGNED) != 0;
-    int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER: what d_out_vals receives
+    const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
+    const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
+               asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0;
+    int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
     const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
+    const uint64_t* d_gv = nullptr;                         // FJ_ALGO_GROUP_BY: d_build_vals is the relation's value column (null: the count form)
+    if (gb) {
+        // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
+        // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
+        // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_ROW_IDS);
+        if (many || left || anti || full || allc || po || bo)
+            return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
+                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+        if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
+        if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
+        if ((amin || amax) && nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs d_build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
+        if (rid && (amin || amax)) return set_err("fj_join_device: FJ_ALGO_ROW_IDS cannot be combined with FJ_ALGO_AGG_%s under FJ_ALGO_GROUP_BY (the first occurrence's position IS the aggregate)", amin ? "MIN" : "MAX");
+        if (rid && !materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS with FJ_ALGO_GROUP_BY needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+        if (materialize) {
+            if (nb && !d_out_keys) return set_err("fj_join_device: FJ_ALGO_GROUP_BY with materialize = 1 needs d_out_keys (d_out_vals is optional; materialize = 0 returns the number of distinct keys alone)");
+            if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu rows (FJ_ALGO_GROUP_BY: every row may be a group of its own)", out_capacity, nb);
+            if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
+        }
+        if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
+        if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+        if (!amin && !amax && !d_bv) agg = FJ_GJ_COUNT;
+        d_gv = rid ? nullptr : d_bv;
+        if (!d_bv || rid) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
+    }
     if (bo) {
         // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
         // d_out_keys = the counts, d_out_vals = the sums (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX: the minima / maxima), nb words each.
@@ -725,7 +753,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (nb && d_out_vals && !rid && !d_bv) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER with d_out_vals needs d_build_vals (only FJ_ALGO_ROW_IDS and the mask alone read no build value)");
         if (!d_bv) d_bv = d_bk;                             // the mask alone reads no value (the checks below want a pointer)
     }
-    if (rid) {
+    if (rid && !gb) {
         // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
         algo &= ~FJ_ALGO_ROW_IDS;
         if (!materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
@@ -797,6 +825,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, c3, rid, full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
         out_count[0] = c3[0]; out_count[1] = c3[1]; out_count[2] = c3[2];
         if (d_out_keys && d_out_vals && emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (gb) {                                               // one row per distinct key, never a pending result
+        if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,
+                     materialize ? (u64*)d_out_vals : nullptr, out_capacity, agg, rid)) return 1;
+        if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;
         return 0;

@@ -150,7 +150,7 @@ extern "C" {
  * Refused up front, before any device work: combined with any other flag (FJ_ALGO_ROW_IDS and FJ_ALGO_PROBE_ORDER included);
  * materialize = 0; both outputs NULL; an output capacity below nb; a misaligned output; d_out_vals with d_build_vals == NULL. */
 #define FJ_ALGO_BUILD_ORDER 0x1000
-/* EXTENSION: modifiers of FJ_ALGO_BUILD_ORDER (and of nothing else: without it each of them is an unknown algo).  FJ_ALGO_AGG_MIN /
+/* EXTENSION: modifiers of FJ_ALGO_BUILD_ORDER (and of FJ_ALGO_GROUP_BY below; without either each of them is an unknown algo).  FJ_ALGO_AGG_MIN /
  * FJ_ALGO_AGG_MAX: d_out_vals[i] = the MINIMUM / MAXIMUM, instead of the sum, of d_build_vals[j] over the probe rows j whose key equals
  * d_build_keys[i] ("latest order per customer", "cheapest offer per product").  The words are compared as uint64, or as
  * two's-complement int64 with FJ_ALGO_AGG_SIGNED.  A build row without a partner receives the aggregate's identity:
@@ -167,6 +167,36 @@ extern "C" {
 #define FJ_ALGO_AGG_MIN    0x4000
 #define FJ_ALGO_AGG_MAX    0x8000
 #define FJ_ALGO_AGG_SIGNED 0x10000
+/* EXTENSION (no reference counterpart; csrc/fj_groupby.hip): OR this into `algo` together with a base value (ADAPTIVE, SCALAR or RADIX:
+ * the partitioned plan or the global HBM table exactly as for FJ_ALGO_BUILD_ORDER) for a GROUP BY / DISTINCT on ONE relation: the
+ * list of groups that FJ_ALGO_BUILD_ORDER asks its caller for, and one aggregate per group.  The relation is passed as the build side:
+ *   d_build_keys  nb keys.
+ *   d_build_vals  optional; nb words, the value column.
+ *   d_probe_keys  must be NULL and np 0: there is no second relation.
+ * *out_count = g, the number of distinct keys.  The result has one row per group, g rows, in an unspecified order that both arrays of
+ * one call share:
+ *   d_out_keys[i] the raw key of group i.
+ *   d_out_vals[i] optional (NULL: the keys alone); the group's aggregate -
+ *                   no modifier, d_build_vals == NULL:   the group's row count
+ *                   no modifier, d_build_vals != NULL:   the sum of the values modulo 2^64
+ *                   FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX:   the minimum / maximum, compared as uint64, or as int64 with FJ_ALGO_AGG_SIGNED
+ *                                                        (needs d_build_vals; every group has a row, so the identity never appears)
+ *                   FJ_ALGO_ROW_IDS:                     the 0-based position of the key's FIRST occurrence in d_build_keys
+ *                                                        (d_build_vals is never read)
+ * materialize = 1 needs 8-byte aligned outputs and out_capacity >= nb, room for any result; the caller trims to g.  Rows [g, nb) may
+ * hold anything afterwards, nothing at or beyond word out_capacity is touched.  materialize = 0 is COUNT(DISTINCT): g alone from a
+ * keys-only pass; no output pointer is read and no capacity needed.  nb == 0: g = 0, nothing is written.  bloom is ignored.  Never a
+ * pending result for fj_emit_pairs (a result that was pending is dropped).  fj_timings: the relation's passes in build_phase_ms, the
+ * kernel in join_ms = probe_phase_ms, emit_ms = 0, fell_back = 1 when a final partition held more distinct keys than the LDS table
+ * takes and the call ran again on the HBM table.  fj_join_host: probe_keys NULL, np 0; *out_keys / *out_vals are malloc'ed arrays of
+ * exactly g rows, either pointer may be NULL to drop that output.
+ * A key that owns a large share of the rows is aggregated by ONE workgroup (a final partition is one work item); the result is exact
+ * at any distribution, the time is not flat.
+ * Refused up front, before any device work: combined with FJ_ALGO_MANY_TO_MANY, FJ_ALGO_LEFT_OUTER, FJ_ALGO_ANTI, FJ_ALGO_FULL_OUTER,
+ * FJ_ALGO_ALL_COPIES, FJ_ALGO_PROBE_ORDER or FJ_ALGO_BUILD_ORDER; a probe side; FJ_ALGO_AGG_MIN with FJ_ALGO_AGG_MAX; FJ_ALGO_AGG_SIGNED
+ * without either; FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX with d_build_vals == NULL (and nb > 0); FJ_ALGO_ROW_IDS with either of them or with
+ * materialize = 0; materialize = 1 with d_out_keys == NULL (and nb > 0), an output capacity below nb or a misaligned output. */
+#define FJ_ALGO_GROUP_BY   0x40000
 
 typedef struct fj_ctx fj_ctx;
 

@@ -1,0 +1,115 @@
+"""Group-by on one relation (unique / distinct_count / group_by_count / group_by_sum / group_by_min / group_by_max, FJ_ALGO_GROUP_BY)
+on device tensors next to the composition a user runs without it.  One JSON line per form, appended to --out:
+
+  (a) unique, unique(return_index=True), distinct_count, group_by_count, group_by_sum, group_by_min, group_by_max
+  (b) the composition: torch.unique(keys, return_counts=True) (counts), or torch.unique(keys, return_inverse=True) followed by
+      zeros(g).index_add_(0, inverse, values) (sums) / full(g, INT64_MAX).scatter_reduce_(0, inverse, values, "amin") (minima) - the
+      wall time of the steps between two device synchronisations
+
+    python tools/group_by_probe.py [--workloads u1m,distinct,hot,b1g] [--forms a,b] [--steps 8] [--warmup 2] [--out profiles/group_by_probe.jsonl]
+
+Workloads: u1m = 100M rows over 1M distinct keys, uniform; distinct = 100M rows, all distinct; b1g = 1B rows over 100M distinct keys;
+hot = 100M rows over 1M keys of which one owns every tenth row.  Times of (a) are device times (core_duration_sec, HIP events); (b) is
+torch kernels, so its figure is wall time around a synchronised region, and (a) is reported that way too ("wall_median_ms") so that
+the two compare like with like.  "timings" of (a) carry the split: build_phase_ms = the relation's passes, join_ms = the kernel - for
+the hot workload the kernel's time is the one long work item's (the hot key's partition)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WORKLOADS = {"u1m": (100_000_000, 1_000_000), "distinct": (100_000_000, 100_000_000), "b1g": (1_000_000_000, 100_000_000), "hot": (100_000_000, 1_000_000)}
+KEEP = ("total_ms", "build_phase_ms", "probe_phase_ms", "join_ms", "emit_ms", "path", "passes", "radix_bits", "fell_back")
+SPREAD = 0x9E3779B97F4A7C15 - 2**64          # an odd multiplier: i -> i * SPREAD is one-to-one modulo 2^64 (int64 storage)
+
+
+def _timed(fn, want, steps, warmup):
+    """medians of the device time fn reports (r[1]; None: a torch composition) and of the wall time of the synchronised call"""
+    import torch
+    dev, wall = [], []
+    for i in range(warmup + steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        assert r[0] == want, (r[0], want)
+        if i >= warmup:
+            if r[1] is not None:
+                dev.append(r[1] * 1e3)
+            wall.append((t1 - t0) * 1e3)
+        del r
+    return (statistics.median(dev) if dev else None), (min(dev) if dev else None), statistics.median(wall)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="u1m,distinct,hot")
+    ap.add_argument("--forms", default="a,b")
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "group_by_probe.jsonl"))
+    args = ap.parse_args()
+    import torch
+    import flash_join
+    flash_join.initialize()
+    forms = args.forms.split(",")
+    out = open(args.out, "a")
+    for wl in args.workloads.split(","):
+        n, g = WORKLOADS[wl]
+        if g == n:
+            keys = torch.arange(n, dtype=torch.int64, device="cuda:0")[torch.randperm(n, device="cuda:0")] * SPREAD
+        else:
+            keys = torch.randint(0, g, (n,), dtype=torch.int64, device="cuda:0")
+            keys[:g] = torch.arange(g, dtype=torch.int64, device="cuda:0")        # every key occurs
+            keys *= SPREAD
+        if wl == "hot":
+            keys[::10] = keys[12345].clone()                                      # (key 12345 sits at row 12345)
+        vals = torch.randint(-2**63, 2**63 - 1, (n,), dtype=torch.int64, device="cuda:0")
+
+        def composed_count():
+            uk, cnt = torch.unique(keys, return_counts=True)
+            return uk.numel(), None, uk, cnt
+
+        def composed_sum():
+            uk, inv = torch.unique(keys, return_inverse=True)
+            return uk.numel(), None, uk, torch.zeros(uk.numel(), dtype=torch.int64, device=keys.device).index_add_(0, inv, vals)
+
+        def composed_min():
+            uk, inv = torch.unique(keys, return_inverse=True)
+            return uk.numel(), None, uk, torch.full((uk.numel(),), 2**63 - 1, dtype=torch.int64, device=keys.device).scatter_reduce_(0, inv, vals, "amin")
+
+        runs = []
+        if "a" in forms:
+            runs += [("a", "unique", lambda: flash_join.unique(keys)),
+                     ("a", "unique_return_index", lambda: flash_join.unique(keys, return_index=True)),
+                     ("a", "distinct_count", lambda: flash_join.distinct_count(keys)),
+                     ("a", "group_by_count", lambda: flash_join.group_by_count(keys)),
+                     ("a", "group_by_sum", lambda: flash_join.group_by_sum(keys, vals)),
+                     ("a", "group_by_min", lambda: flash_join.group_by_min(keys, vals)),
+                     ("a", "group_by_max", lambda: flash_join.group_by_max(keys, vals))]
+        if "b" in forms:
+            runs += [("b", "torch.unique(return_counts)", composed_count), ("b", "torch.unique(return_inverse)+index_add", composed_sum),
+                     ("b", "torch.unique(return_inverse)+scatter_reduce_amin", composed_min)]
+        for form, name, fn in runs:
+            d_med, d_min, w_med = _timed(fn, g, args.steps, args.warmup)
+            lt = flash_join.last_timings() if form == "a" else None
+            line = json.dumps({"workload": wl, "rows": n, "distinct": g, "form": form, "name": name,
+                               "device_median_ms": None if d_med is None else round(d_med, 3),
+                               "device_min_ms": None if d_min is None else round(d_min, 3), "wall_median_ms": round(w_med, 3),
+                               "timings": {k: lt[k] for k in KEEP} if lt else None})
+            print(line, flush=True)
+            out.write(line + "\n")
+            out.flush()
+            torch.cuda.empty_cache()
+        del keys, vals
+        torch.cuda.empty_cache()
+    out.close()
+
+
+if __name__ == "__main__":
+    main()
