@@ -44,6 +44,7 @@ ALGO_AGG_MIN = 0x4000             # FJ_ALGO_AGG_MIN: modifier of ALGO_BUILD_ORDE
 ALGO_AGG_MAX = 0x8000             # FJ_ALGO_AGG_MAX: ... the maximum
 ALGO_AGG_SIGNED = 0x10000         # FJ_ALGO_AGG_SIGNED: modifier of AGG_MIN / AGG_MAX - the words compare as two's-complement int64 instead of uint64
 ALGO_GROUP_BY = 0x40000           # FJ_ALGO_GROUP_BY: group-by on ONE relation (the build side) - its g distinct keys and one aggregate per key; AGG_* and ROW_IDS modify it (extension)
+ALGO_INVERSE = 0x100000           # FJ_ALGO_INVERSE: modifier of ALGO_GROUP_BY - the values output holds the group id of EVERY row, at the row's position (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -736,10 +737,14 @@ def _trim(buf, g: int):
 
 def _group_by(keys, values, flags: int, materialize: bool = True, want_vals: bool = True):
     """(g, seconds, group_keys or None, aggregates or None), where the inputs live: NumPy uint64 keys and int64 words (the storage of
-    the uint64 aggregates), or torch.int64 tensors on the inputs' device.  values=None: the count form (or ALGO_ROW_IDS in flags)."""
+    the uint64 aggregates), or torch.int64 tensors on the inputs' device.  values=None: the count form (or ALGO_ROW_IDS in flags).
+    ALGO_INVERSE in flags: the fourth item is the group id of every row instead - len(keys) int64 in [0, g), never trimmed to g."""
     global _last
     keys, values = (_from_dlpack_if_device(x) if x is not None else None for x in (keys, values))
     algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | flags
+    inverse = bool(flags & ALGO_INVERSE)
+    if inverse and not (materialize and want_vals):
+        raise ValueError("ALGO_INVERSE: the group ids are the values output (materialize and want_vals)")
     L = _lib.load()
     cnt = ctypes.c_uint64(0)
     if _is_torch_tensor(keys) and keys.is_cuda:
@@ -761,7 +766,7 @@ def _group_by(keys, values, flags: int, materialize: bool = True, want_vals: boo
                                    n if materialize else 0, ctypes.byref(t)))
         _last = t
         g = int(cnt.value)
-        return g, t.total_ms * 1e-3, _trim(ok, g), _trim(ov, g)
+        return g, t.total_ms * 1e-3, _trim(ok, g), ov if inverse else _trim(ov, g)
     if _is_torch_tensor(keys):
         keys, values = (x.numpy() if x is not None else None for x in (keys, values))
     k = _as_u64_host(keys, "keys")
@@ -778,9 +783,9 @@ def _group_by(keys, values, flags: int, materialize: bool = True, want_vals: boo
     _last = t
     g = int(cnt.value)
     try:
-        take = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(g,)).copy() if g else np.empty(0, np.uint64))
-        gk = take(ok) if materialize else None
-        gv = take(ov).view(np.int64) if materialize and want_vals else None
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        gk = take(ok, g) if materialize else None
+        gv = take(ov, k.size if inverse else g).view(np.int64) if materialize and want_vals else None
     finally:
         L.fj_free_host(ok)
         L.fj_free_host(ov)
@@ -799,12 +804,52 @@ def _align_by_key(keys_a, keys_b, vals_b):
     return out
 
 
-def unique(keys, return_index: bool = False, return_counts: bool = False):
+def _bincount(ids, g: int):
+    """rows per id in [0, g), int64, where the ids live"""
+    if _is_torch_tensor(ids):
+        import torch
+        return torch.bincount(ids, minlength=g)
+    return np.bincount(ids, minlength=g).astype(np.int64, copy=False)
+
+
+def _ids_by_key(keys_a, keys_b, ids_b):
+    """ids_b, indices into keys_b, as indices into keys_a (the same set of distinct keys in another order)"""
+    if _is_torch_tensor(keys_a):
+        import torch
+        perm = torch.empty_like(keys_a)
+        perm[torch.argsort(keys_b)] = torch.argsort(keys_a)
+        return perm[ids_b]
+    perm = np.empty(keys_a.shape[0], np.int64)
+    perm[np.argsort(keys_b, kind="stable")] = np.argsort(keys_a, kind="stable")
+    return perm[ids_b]
+
+
+def factorize(keys):
+    """The dense group id of every row (pandas.factorize; the dictionary encoding of a key column): (g, seconds, codes, uniques) -
+    uniques the g distinct keys in unspecified order (neither sorted nor by first occurrence), codes one int64 in [0, g) per row of
+    keys with uniques[codes] == keys.  One library call: the relation is grouped once, and every further aggregate is an
+    index_add_ / scatter_reduce_ / np.bincount of the caller's over codes.  NumPy in: uniques is uint64, codes int64; torch ROCm
+    tensors / DLPack are grouped in place, both outputs are torch.int64 on their device."""
+    g, sec, uniques, codes = _group_by(keys, None, ALGO_INVERSE)
+    return g, sec, codes, uniques
+
+
+def unique(keys, return_index: bool = False, return_counts: bool = False, return_inverse: bool = False):
     """The distinct keys of one relation (DISTINCT; torch.unique / np.unique without the sort): (g, seconds, unique_keys) followed by
-    first_index if return_index (the 0-based position of every key's FIRST occurrence, int64) and by counts if return_counts (int64).
-    The order of the keys is unspecified; the extras are aligned with unique_keys.  Either extra alone is one call; asking for BOTH
-    makes two calls (one aggregate per call) and aligns the second by key with two argsorts of g keys - `seconds` is the sum of both.
+    first_index if return_index (the 0-based position of every key's FIRST occurrence, int64), by inverse if return_inverse (int64,
+    one per row of keys: unique_keys[inverse] == keys) and by counts if return_counts (int64) - NumPy's order.
+    The order of the keys is unspecified; the extras are aligned with unique_keys.  Any one extra is one call; so is return_inverse
+    with return_counts (the counts are the bincount of the inverse, where the data lives).  return_index with either of the others
+    makes two calls (one per-call output) and aligns the second by key with two argsorts of g keys - `seconds` is the sum of both.
     NumPy in: unique_keys is uint64; torch ROCm tensors / DLPack are grouped in place, every output is torch.int64 on their device."""
+    if return_inverse:
+        if not return_index:
+            g, sec, gk, inv = _group_by(keys, None, ALGO_INVERSE)
+            return (g, sec, gk, inv, _bincount(inv, g)) if return_counts else (g, sec, gk, inv)
+        g, sec, gk, idx = _group_by(keys, None, ALGO_ROW_IDS)
+        g2, sec2, gk2, inv2 = _group_by(keys, None, ALGO_INVERSE)
+        inv = _ids_by_key(gk, gk2, inv2)
+        return (g, sec + sec2, gk, idx, inv, _bincount(inv, g)) if return_counts else (g, sec + sec2, gk, idx, inv)
     if return_index:
         g, sec, gk, idx = _group_by(keys, None, ALGO_ROW_IDS)
         if not return_counts:
@@ -957,5 +1002,6 @@ REFERENCE_EXPORTS = [
 ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_radix_bloom", "adaptive_bloom"]
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
-              "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max"]
+              "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
+              "factorize"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]

@@ -11,6 +11,10 @@
 // ranks inside the range by wave ballot + popcount on an LDS cursor.  The emit is the only phase that writes to HBM; the order of
 // the groups is whatever the cursor and the slots make it.
 //
+// FJ_ALGO_INVERSE is the inverse of that: beside the distinct keys, the result row of its key - a dense group id - for EVERY row of the
+// relation, at the row's own position (fj_group_by_inverse_kernel: the table from the keys, the ranks, then a second sweep over the
+// partition's rows).  np.unique(return_inverse=True) / pandas.factorize without the sort.
+//
 // Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition, and its LDS atomics hit
 // one address; fewer than ~256 distinct keys leave CUs idle.  Correct at any distribution (DESIGN.md "Group-by on one relation").
 //
@@ -134,6 +138,145 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_kernel(FjGroupByArgs a) 
     }
 }
 
+// ---- the inverse form (FJ_ALGO_INVERSE): the distinct keys as above and, for EVERY row, the result row of its key - the group id - at
+// the row's own position (a.rel.vals: the positions the first pass made; flat arrays: the index).  Three phases over one partition:
+//   stream 1  the rows' keys build the table (no accumulator work; the plane behind the key slots stays free),
+//   rank      the emit above: one global atomic reserves [o, o + g_p), an occupied slot takes rank r by wave ballot, out_keys[o + r] is
+//             written and the id o + r is stored in the word behind the slot (the marker key's id, o + nkeys, in the header),
+//   stream 2  the same chunks again, keys and positions (L2 / MALL hits: a partition is ~64 KiB): a read-only probe of the finished
+//             table - no CAS, no atomic - and out_vals[position] = id, one 8-byte scattered store per row.
+// A partition beyond the table skips the last two phases (all threads alike: hdr->full is read behind a barrier) and the host runs the
+// call again on the HBM table, which overwrites every id the other partitions wrote from the abandoned cursor.
+template <bool POS>
+__device__ __forceinline__ void gb_load_round(const FjChunkSet& rel, u32 b0, u32 nbc, u32 c0, u32 tid, u64 (&kk)[GJ_KPT],
+                                              u64 (&vv)[POS ? GJ_KPT : 1], u32& ok) {
+    ok = 0;
+#pragma unroll
+    for (u32 u = 0; u < GJ_KPT; ++u) {
+        const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        kk[u] = 0; if (POS) vv[POS ? u : 0] = 0;
+        if (c >= nbc) continue;
+        const u32 e = gj_entry(rel, b0 + c);
+        if (off >= FJ_LIST_CNT(e)) continue;
+        const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+        kk[u] = rel.keys[src];
+        if (POS) vv[POS ? u : 0] = rel.vals ? rel.vals[src] : src;                // (zero-pass plan: the flat index IS the position)
+        ok |= 1u << u;
+    }
+}
+
+__global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_inverse_kernel(FjGroupByArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    GbHdr* hdr = reinterpret_cast<GbHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(GbHdr));
+    u64* ids = tkeys + GJ_TS;                                // written for every occupied slot before stream 2 reads it: no fill
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 p = blockIdx.x;
+    u32 b0 = 0, nbc;
+    if (a.rel.list) { b0 = a.rel.boff[p]; nbc = a.rel.boff[p + 1] - b0; }
+    else nbc = (u32)((a.rel.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    if (nbc == 0) return;
+
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) tkeys[i] = FJ_EMPTY_KEY;
+    if (tid == 0) { hdr->full = 0; hdr->has_empty = 0; hdr->nkeys = 0; hdr->cursor = 0; hdr->empty_acc = 0; hdr->base = 0; }
+    __syncthreads();
+
+    // ---- stream 1: the keys alone, the shape of fj_group_by_kernel's stream ----
+    {
+        u64 k[GJ_KPT], none[1];
+        u32 okm = 0;
+        gb_load_round<false>(a.rel, b0, nbc, 0, tid, k, none, okm);
+        for (u32 c0 = 0; c0 < nbc; c0 += GJ_ROUND_CHUNKS) {
+            u64 kn[GJ_KPT];
+            u32 okn = 0;
+            if (c0 + GJ_ROUND_CHUNKS < nbc) gb_load_round<false>(a.rel, b0, nbc, c0 + GJ_ROUND_CHUNKS, tid, kn, none, okn);
+#pragma unroll
+            for (u32 u = 0; u < GJ_KPT; ++u) {
+                if (!((okm >> u) & 1u)) continue;
+                const u64 key = a.rel.list ? k[u] : fj_key_mix(k[u]);
+                if (key == FJ_EMPTY_KEY) { hdr->has_empty = 1; continue; }        // the empty marker is never stored in the table
+                if (*(volatile u32*)&hdr->full) continue;
+                u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+                bool placed = false;
+                for (u32 step = 0; step < GJ_TS; ++step) {
+                    u64 t = tkeys[pos];
+                    if (t == FJ_EMPTY_KEY) {
+                        t = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+                        if (t == FJ_EMPTY_KEY) {
+                            if (atomicAdd(&hdr->nkeys, 1u) >= GJ_LIMIT) hdr->full = 1;
+                            t = key;
+                        }
+                    }
+                    if (t == key) { placed = true; break; }
+                    pos = (pos + 1) & (GJ_TS - 1);
+                }
+                if (!placed) hdr->full = 1;
+            }
+#pragma unroll
+            for (u32 u = 0; u < GJ_KPT; ++u) k[u] = kn[u];
+            okm = okn;
+        }
+    }
+    __syncthreads();
+    if (hdr->full) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }     // (uniform: every thread reads the word behind the barrier)
+
+    // ---- reserve and rank: the emit of fj_group_by_kernel; the slot's result row stays behind it in LDS ----
+    const u32 nk = hdr->nkeys;
+    const bool has_empty = hdr->has_empty != 0;
+    if (tid == 0) {
+        const u64 o0 = (u64)atomicAdd(a.cursor, (unsigned long long)(nk + (has_empty ? 1u : 0u)));
+        hdr->base = o0; hdr->empty_acc = o0 + nk;
+    }
+    __syncthreads();
+    const u64 o = hdr->base;
+    for (u32 i = tid; i < GJ_TS; i += GJ_NT) {               // (GJ_TS is a multiple of GJ_NT: whole waves every round)
+        const u64 key = tkeys[i];
+        const bool occ = key != FJ_EMPTY_KEY;
+        const unsigned long long m = __ballot(occ);
+        u32 wbase = 0;
+        if (lane == 0 && m) wbase = atomicAdd(&hdr->cursor, (u32)__popcll(m));
+        wbase = __shfl(wbase, 0, 64);
+        if (!occ) continue;
+        const u64 row = o + wbase + (u32)__popcll(m & ((1ull << lane) - 1ull));
+        ids[i] = row;
+        if (row < a.out_capacity) a.out_keys[row] = fj_key_unmix(key);
+        else atomicOr(a.err, FJ_ERR_OUTCAP);
+    }
+    if (tid == 0 && has_empty) {
+        const u64 row = o + nk;
+        if (row < a.out_capacity) a.out_keys[row] = fj_key_unmix(FJ_EMPTY_KEY);
+        else atomicOr(a.err, FJ_ERR_OUTCAP);
+    }
+    __syncthreads();
+
+    // ---- stream 2: every row finds its key's slot in the finished table and stores the slot's id at the row's position ----
+    const u64 empty_id = hdr->empty_acc;
+    u64 k[GJ_KPT], pv[GJ_KPT];
+    u32 okm = 0;
+    gb_load_round<true>(a.rel, b0, nbc, 0, tid, k, pv, okm);
+    for (u32 c0 = 0; c0 < nbc; c0 += GJ_ROUND_CHUNKS) {
+        u64 kn[GJ_KPT], pvn[GJ_KPT];
+        u32 okn = 0;
+        if (c0 + GJ_ROUND_CHUNKS < nbc) gb_load_round<true>(a.rel, b0, nbc, c0 + GJ_ROUND_CHUNKS, tid, kn, pvn, okn);
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) {
+            if (!((okm >> u) & 1u)) continue;
+            const u64 key = a.rel.list ? k[u] : fj_key_mix(k[u]);
+            u64 id = empty_id;
+            if (key != FJ_EMPTY_KEY) {
+                u32 pos = FJ_HW2(key) & (GJ_TS - 1);
+                for (u32 step = 0; step < GJ_TS && tkeys[pos] != key; ++step) pos = (pos + 1) & (GJ_TS - 1);      // (stream 1 placed every key)
+                id = ids[pos];
+            }
+            if (pv[u] < a.out_capacity) a.out_vals[pv[u]] = id;
+            else atomicOr(a.err, FJ_ERR_OUTCAP);
+        }
+#pragma unroll
+        for (u32 u = 0; u < GJ_KPT; ++u) { k[u] = kn[u]; pv[u] = pvn[u]; }
+        okm = okn;
+    }
+}
+
 // ---- the global-table form.  The table is fj_gt_build_first_kernel's (csrc/fj_join.hip: raw keys, the raw empty key out of band);
 // the accumulators are capacity + 1 words holding the aggregate's identity, the last one the empty key's ----
 // thread per row of the relation: one typed global atomic on the slot of the row's key (the build placed every key)
@@ -149,9 +292,12 @@ __global__ __launch_bounds__(1024) void fj_gt_group_by_combine_kernel(FjGtArgs a
 }
 
 // the capacity + 1 slots, compacted: an occupied slot's (key, accumulator) goes to the row a wave-aggregated cursor hands out (one
-// global atomic per wave that holds a key).  out_keys == nullptr: the cursor alone (COUNT(DISTINCT)); acc == nullptr: the keys alone
+// global atomic per wave that holds a key).  out_keys == nullptr: the cursor alone (COUNT(DISTINCT)); acc == nullptr: the keys alone.
+// IDS (the inverse form; out_vals is not written here): the row a slot receives is also stored in ids[slot], capacity + 1 words
+template <bool IDS>
 __global__ __launch_bounds__(1024) void fj_gt_group_by_sweep_kernel(FjGtArgs a, const u64* __restrict__ acc, u64* __restrict__ out_keys,
-                                                                    u64* __restrict__ out_vals, u64 out_capacity, unsigned long long* cursor, u32* err) {
+                                                                    u64* __restrict__ out_vals, u64 out_capacity, unsigned long long* cursor, u32* err,
+                                                                    u64* __restrict__ ids) {
     const u64 cap = a.cap_mask + 1;
     const bool has_empty = a.flags[0] != 0;
     const u32 lane = threadIdx.x & 63;
@@ -167,10 +313,25 @@ __global__ __launch_bounds__(1024) void fj_gt_group_by_sweep_kernel(FjGtArgs a, 
         wbase = __shfl(wbase, 0, 64);
         if (!occ || !out_keys) continue;
         const u64 row = wbase + (u32)__popcll(m & ((1ull << lane) - 1ull));
+        if (IDS) ids[i] = row;
         if (row < out_capacity) {
             out_keys[row] = key;
-            if (out_vals) out_vals[row] = acc[i];
+            if (!IDS && out_vals) out_vals[row] = acc[i];
         } else atomicOr(err, FJ_ERR_OUTCAP);
+    }
+}
+
+// the inverse form's last step, behind the sweep on the same stream: thread per row of the relation, out_vals[i] = the row the sweep
+// handed to the slot of row i's key (the build placed every key; the empty key's id is the plane's last word)
+__global__ __launch_bounds__(1024) void fj_gt_group_by_inverse_kernel(FjGtArgs a, const u64* __restrict__ ids, u64* __restrict__ out_vals,
+                                                                      u64 out_capacity) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    const u64 n = a.nb < out_capacity ? a.nb : out_capacity;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const u64 key = a.bk[i];
+        u64 where = a.cap_mask + 1;
+        if (key != FJ_EMPTY_KEY && !gj_gt_find(a.tkeys, a.cap_mask, key, where)) continue;
+        out_vals[i] = ids[where];
     }
 }
 
@@ -197,6 +358,15 @@ hipError_t fj_launch_group_by(const FjGroupByArgs& a, int agg, bool emit, hipStr
     return emit ? launch_lds<true>(a, agg, s) : launch_lds<false>(a, agg, s);
 }
 
+hipError_t fj_launch_group_by_inverse(const FjGroupByArgs& a, hipStream_t s) {
+    if (!a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals) return hipErrorInvalidValue;
+    const u32 lds = (u32)sizeof(GbHdr) + GJ_TS * 16u;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(fj_group_by_inverse_kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fj_group_by_inverse_kernel, dim3(a.nparts), dim3(GJ_NT), lds, s, a);
+    return hipGetLastError();
+}
+
 hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s) {
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
@@ -210,11 +380,19 @@ hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* 
 }
 
 hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
-                                       unsigned long long* cursor, u32* err, hipStream_t s) {
-    if (!cursor || !err || (out_vals && (!acc || !out_keys))) return hipErrorInvalidValue;
+                                       unsigned long long* cursor, u32* err, hipStream_t s, u64* ids) {
+    if (!cursor || !err || (out_vals && (!acc || !out_keys)) || (ids && (!out_keys || out_vals))) return hipErrorInvalidValue;
     const u64 rounds = (a.cap_mask + 2 + 1023) / 1024;
-    hipLaunchKernelGGL(fj_gt_group_by_sweep_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, acc, out_keys, out_vals,
-                       out_capacity, cursor, err);
+    hipLaunchKernelGGL(ids ? fj_gt_group_by_sweep_kernel<true> : fj_gt_group_by_sweep_kernel<false>, dim3((u32)(rounds < 4096 ? rounds : 4096)),
+                       dim3(1024), 0, s, a, acc, out_keys, out_vals, out_capacity, cursor, err, ids);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_gt_group_by_inverse(const FjGtArgs& a, const u64* ids, u64* out_vals, u64 out_capacity, hipStream_t s) {
+    if (!ids || !out_vals) return hipErrorInvalidValue;
+    if (!a.nb) return hipSuccess;
+    const u64 rounds = (a.nb + 1023) / 1024;
+    hipLaunchKernelGGL(fj_gt_group_by_inverse_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, ids, out_vals, out_capacity);
     return hipGetLastError();
 }
 
@@ -223,9 +401,11 @@ namespace fjh {
 // the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
 // "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts at 0: whatever an
 // abandoned partitioned attempt wrote is overwritten.  rid: the table build itself keeps every key's first row index
-// (fj_gt_build_first_kernel with values), so the accumulators are its value plane and no combine pass runs.
+// (fj_gt_build_first_kernel with values), so the accumulators are its value plane and no combine pass runs.  inv: the value plane
+// receives the row the sweep hands to every slot instead, and one more kernel, behind the sweep on the same stream, stores every row's
+// id at the row's position: all nb words of d_ov, whatever an abandoned partitioned attempt left there.
 static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
-                           u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid) {
+                           u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid, bool inv) {
     u64 cap = 64;
     while (cap < 2 * (u64)nb) cap <<= 1;
     FjGtArgs a{};
@@ -238,7 +418,8 @@ static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, h
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
     HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
-    if (acc && rid) {                                        // (row index minimum: all ones at rest; the empty key's word is the table's last)
+    if (inv) HIPCHK(fj_launch_gt_build_first(a, false, s));  // (the id plane needs no fill: the sweep writes every word that is read)
+    else if (acc && rid) {                                   // (row index minimum: all ones at rest; the empty key's word is the table's last)
         a.tvals = acc; a.empty_val = acc + cap;
         HIPCHK(hipMemsetAsync(acc, 0xFF, (cap + 1) * 8, s));
         HIPCHK(fj_launch_gt_build_first(a, true, s));
@@ -251,7 +432,10 @@ static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, h
     }
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    HIPCHK(fj_launch_gt_group_by_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
+    if (inv) {
+        HIPCHK(fj_launch_gt_group_by_sweep(a, nullptr, d_ok, nullptr, cap_out, &c->d_sc->total, &c->d_sc->err, s, acc));
+        HIPCHK(fj_launch_gt_group_by_inverse(a, acc, d_ov, cap_out, s));
+    } else HIPCHK(fj_launch_gt_group_by_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
@@ -267,15 +451,17 @@ static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, h
 // FJ_ALGO_GROUP_BY (fj_join_device has checked the arguments): the g distinct keys of bk[0 .. nb) in d_ok and their aggregates in d_ov
 // (null: the keys alone), g <= nb <= cap_out rows; d_ok == nullptr: *out_count = g alone (COUNT(DISTINCT), a keys-only pass).  agg:
 // FJ_GJ_COUNT (bv is not read), FJ_GJ_SUM or a min / max form over bv; rid: the first occurrence's position instead (bv is not read).
-// use_radix: the partitioned plan, else the global table.
+// use_radix: the partitioned plan, else the global table.  inv (FJ_ALGO_INVERSE; d_ok and d_ov given, no aggregate): d_ov receives
+// nb words instead, the group id of every row at the row's position (bv is not read).
 int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
-             u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid) {
+             u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid, bool inv) {
     *out_count = 0;
     if (nb == 0) return 0;
     if (!d_ok) d_ov = nullptr;
-    if (!d_ov) { agg = FJ_GJ_COUNT; rid = false; }           // no aggregate leaves the call: nothing travels beside the keys
+    if (!d_ov) { agg = FJ_GJ_COUNT; rid = false; inv = false; }      // no aggregate leaves the call: nothing travels beside the keys
+    if (inv) rid = false;
     if (rid) agg = FJ_GJ_MIN_U;
-    if (!use_radix) return group_by_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, agg, rid);
+    if (!use_radix) return group_by_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, agg, rid, inv);
 
     const Plan plan = make_plan(nb, top_bits, false);
     begin_plan(c);
@@ -283,15 +469,16 @@ int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb,
     if (clear_plan_scalars(c, s)) return 1;
     FjGroupByArgs ga{};
     PassIter it;
-    pass_init(it, 0, agg != FJ_GJ_COUNT, nb, plan, top_bits);
-    it.vals_pos = rid;                                       // the rows' positions travel through the passes
-    if (run_passes(c, it, bk, (agg != FJ_GJ_COUNT && !rid) ? bv : nullptr, s, &ga.rel, nullptr)) return 1;
+    pass_init(it, 0, agg != FJ_GJ_COUNT || inv, nb, plan, top_bits);
+    it.vals_pos = rid || inv;                                // the rows' positions travel through the passes
+    if (run_passes(c, it, bk, (agg != FJ_GJ_COUNT && !rid && !inv) ? bv : nullptr, s, &ga.rel, nullptr)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
-    HIPCHK(fj_launch_group_by(ga, agg, d_ok != nullptr, s));
+    if (inv) HIPCHK(fj_launch_group_by_inverse(ga, s));
+    else HIPCHK(fj_launch_group_by(ga, agg, d_ok != nullptr, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
@@ -300,7 +487,7 @@ int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb,
     t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
     if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
         fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (group_by_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, agg, rid)) return 1;
+        if (group_by_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, agg, rid, inv)) return 1;
         t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
         return 0;
     }

@@ -323,9 +323,10 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
 
 // ---- group-by on one relation (fj_groupby.hip): FJ_ALGO_GROUP_BY; the g distinct keys of bk in d_ok and one aggregate per key in d_ov
 // (null: the keys alone), cap_out >= nb rows each; d_ok == nullptr: g alone; agg: FJ_GJ_COUNT, FJ_GJ_SUM or a min / max form over bv;
-// rid: the position of the key's first occurrence instead; *out_count = g ----
+// rid: the position of the key's first occurrence instead; inv (FJ_ALGO_INVERSE): d_ov receives nb words instead, every row's group id
+// (its key's row in d_ok) at the row's position; *out_count = g ----
 int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
-             u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid);
+             u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid, bool inv = false);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

@@ -182,13 +182,22 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
-    const int agg_flags = (bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0;     // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
+    const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
+    const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
+                          (gb ? FJ_ALGO_INVERSE : 0);                                                     // a modifier of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (many_host || left || anti || full || allc || po || bo)
             return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (pk || np) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (inv) {                                             // the group id of every row: *out_vals nb words, no aggregate beside it
+            if (amin || amax || asigned)
+                return set_err("fj_join_host: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_AGG_%s (the ids group the rows once: every aggregate is a pass of the caller's over them)",
+                               amin ? "MIN" : amax ? "MAX" : "SIGNED");
+            if (rid) return set_err("fj_join_host: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_ROW_IDS (out_vals is taken: one per-call output)");
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+        }
         if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if ((amin || amax) && nb && !bv) return set_err("fj_join_host: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
@@ -282,7 +291,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (!streamed) {
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
         else if (gb) {                                                          // the relation's value column: only the sum / min / max forms that return it read it
-            if (!bv) dbv = nullptr;
+            if (!bv || inv) dbv = nullptr;
             else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
         }
         else if (bo) {                                                          // the probe side's value column, read for the sums only
@@ -400,19 +409,22 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hs;
         joined = true;
     }
-    if (gb) {                                                                  // g <= nb keys and aggregates; exactly g rows go back
+    if (gb) {                                                                  // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
         void *dok = nullptr, *dov = nullptr;
+        const bool ids = inv && out_vals;                                       // (nobody takes the ids: the plain distinct form)
+        if (inv && !ids) algo &= ~FJ_ALGO_INVERSE;
         if (materialize && (get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dok) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dov)))) return 1;
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
                            &count, (u64*)dok, (u64*)dov, nb, &t)) return 1;
         if (materialize) {
             const size_t g = (size_t)count;
             u64* hk = out_keys ? (u64*)malloc(std::max<size_t>(g, 1) * 8) : nullptr;
-            u64* hv = out_vals ? (u64*)malloc(std::max<size_t>(g, 1) * 8) : nullptr;
-            if ((out_keys && !hk) || (out_vals && !hv)) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", g); }
+            const size_t gv = ids ? nb : g;
+            u64* hv = out_vals ? (u64*)malloc(std::max<size_t>(gv, 1) * 8) : nullptr;
+            if ((out_keys && !hk) || (out_vals && !hv)) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", std::max(g, gv)); }
             auto t1 = std::chrono::steady_clock::now();
             if (g && hk) HIPCHK(hipMemcpy(hk, dok, g * 8, hipMemcpyDeviceToHost));
-            if (g && hv) HIPCHK(hipMemcpy(hv, dov, g * 8, hipMemcpyDeviceToHost));
+            if (gv && hv) HIPCHK(hipMemcpy(hv, dov, gv * 8, hipMemcpyDeviceToHost));
             d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
             if (out_keys) *out_keys = hk;
             if (out_vals) *out_vals = hv;

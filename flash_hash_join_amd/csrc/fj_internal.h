@@ -366,13 +366,21 @@ struct FjGroupByArgs {
     u32* err;
 };
 hipError_t fj_launch_group_by(const FjGroupByArgs& a, int agg, bool emit, hipStream_t s);
+// the inverse form (FJ_ALGO_INVERSE): the distinct keys as above (out_keys) and, in out_vals, the result row of its key - the group id -
+// for EVERY row of `rel` at the row's own position (rel.vals: the positions the first pass made; flat arrays: the index).  A position at
+// or beyond out_capacity is not written (FJ_ERR_OUTCAP); a partition beyond the table writes nothing and raises FJ_ERR_LDS_FULL, while
+// other partitions have written ids of the cursor the caller then abandons: the re-run must define every id again.
+hipError_t fj_launch_group_by_inverse(const FjGroupByArgs& a, hipStream_t s);
 // global table built by fj_launch_gt_build_first (vals = false) over a.bk: one thread per row combines into acc[slot] (capacity + 1 words
 // holding the aggregate's identity, the last one the empty key's) - 1 per row (FJ_GJ_COUNT) or vals[i]
 hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s);
 // ... and its capacity + 1 slots compacted into out rows [0, *cursor): (key, acc[slot]); out_vals == nullptr: the keys alone; out_keys
-// == nullptr: the cursor alone.  Rows at or beyond out_capacity are not written (FJ_ERR_OUTCAP)
+// == nullptr: the cursor alone.  Rows at or beyond out_capacity are not written (FJ_ERR_OUTCAP).  ids != nullptr (capacity + 1 words,
+// the last one the empty key's; out_vals must be null): every occupied slot's row is stored there too
 hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
-                                       unsigned long long* cursor, u32* err, hipStream_t s);
+                                       unsigned long long* cursor, u32* err, hipStream_t s, u64* ids = nullptr);
+// ... and, behind that sweep on the same stream, out_vals[i] = ids[slot of a.bk[i]] for the rows i < min(a.nb, out_capacity)
+hipError_t fj_launch_gt_group_by_inverse(const FjGtArgs& a, const u64* ids, u64* out_vals, u64 out_capacity, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

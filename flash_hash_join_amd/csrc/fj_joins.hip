@@ -686,6 +686,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
+    const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
                asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0;
     int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
@@ -697,11 +698,19 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_ROW_IDS);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE);
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (inv) {                                          // the group id of every row (d_out_vals: nb words), no aggregate beside it
+            if (amin || amax || asigned)
+                return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_AGG_%s (the ids group the rows once: every aggregate is a pass of the caller's over them)",
+                               amin ? "MIN" : amax ? "MAX" : "SIGNED");
+            if (rid) return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_ROW_IDS (d_out_vals is taken: one per-call output)");
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_INVERSE needs d_out_keys and d_out_vals (the g distinct keys and the nb group ids that index them)");
+        }
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if ((amin || amax) && nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs d_build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
@@ -715,8 +724,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
         if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
         if (!amin && !amax && !d_bv) agg = FJ_GJ_COUNT;
-        d_gv = rid ? nullptr : d_bv;
-        if (!d_bv || rid) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
+        d_gv = (rid || inv) ? nullptr : d_bv;
+        if (!d_bv || rid || inv) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
     }
     if (bo) {
         // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
@@ -831,7 +840,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     }
     if (gb) {                                               // one row per distinct key, never a pending result
         if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,
-                     materialize ? (u64*)d_out_vals : nullptr, out_capacity, agg, rid)) return 1;
+                     materialize ? (u64*)d_out_vals : nullptr, out_capacity, agg, rid, inv)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

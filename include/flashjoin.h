@@ -197,6 +197,25 @@ extern "C" {
  * without either; FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX with d_build_vals == NULL (and nb > 0); FJ_ALGO_ROW_IDS with either of them or with
  * materialize = 0; materialize = 1 with d_out_keys == NULL (and nb > 0), an output capacity below nb or a misaligned output. */
 #define FJ_ALGO_GROUP_BY   0x40000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY (without it an unknown algo; csrc/fj_groupby.hip): the INVERSE of the group-by, what
+ * np.unique(return_inverse=True), torch.unique(return_inverse=True) and pandas.factorize return - the group of EVERY row.  OR it into
+ * `algo` together with FJ_ALGO_GROUP_BY and a base value (ADAPTIVE, SCALAR or RADIX), materialize = 1:
+ *   d_out_keys[0 .. g) the distinct raw keys in an unspecified order, exactly as without the flag; rows [g, nb) may hold anything.
+ *   d_out_vals[i]      for every i < nb: the group id of build row i, AT row i's position - a uint64 in [0, g) with
+ *                      d_out_keys[d_out_vals[i]] == d_build_keys[i].
+ * *out_count = g.  out_capacity >= nb covers both arrays; both are required (nb > 0) and 8-byte aligned.  All nb words of d_out_vals are
+ * defined by the call alone, whatever the buffer held before; nothing at or beyond word out_capacity of either array is touched.
+ * d_build_vals is never read and may be NULL.  nb == 0: g = 0, nothing is written.  bloom is ignored.  Never a pending result for
+ * fj_emit_pairs.  The ids are the dictionary encoding of the key column: with them the relation is grouped ONCE, and every further
+ * aggregate (an average, a variance, several value columns) is a scatter of the caller's over ids in [0, g).  The order of the groups
+ * is the cursor's: neither sorted nor by first occurrence.  fj_timings as for FJ_ALGO_GROUP_BY: the pass over the rows that writes the
+ * ids counts into join_ms = probe_phase_ms, emit_ms = 0, fell_back as there (the re-run on the HBM table writes all nb ids again).
+ * fj_join_host: *out_keys is a malloc'ed array of exactly g rows, *out_vals one of exactly nb rows; either pointer may be NULL to drop
+ * that output (out_vals == NULL runs the plain distinct form).
+ * Refused up front, before any device work, in addition to what FJ_ALGO_GROUP_BY refuses: combined with FJ_ALGO_AGG_MIN,
+ * FJ_ALGO_AGG_MAX or FJ_ALGO_AGG_SIGNED (no aggregate in the same call) or with FJ_ALGO_ROW_IDS (d_out_vals is taken: one per-call
+ * output); materialize = 0; fj_join_device with d_out_keys == NULL or d_out_vals == NULL (and nb > 0). */
+#define FJ_ALGO_INVERSE    0x100000
 
 typedef struct fj_ctx fj_ctx;
 

@@ -1,12 +1,15 @@
 """Group-by on one relation (unique / distinct_count / group_by_count / group_by_sum / group_by_min / group_by_max, FJ_ALGO_GROUP_BY)
-on device tensors next to the composition a user runs without it.  One JSON line per form, appended to --out:
+and its inverse (factorize, FJ_ALGO_INVERSE) on device tensors next to the composition a user runs without them.  One JSON line per
+form, appended to --out:
 
-  (a) unique, unique(return_index=True), distinct_count, group_by_count, group_by_sum, group_by_min, group_by_max
-  (b) the composition: torch.unique(keys, return_counts=True) (counts), or torch.unique(keys, return_inverse=True) followed by
-      zeros(g).index_add_(0, inverse, values) (sums) / full(g, INT64_MAX).scatter_reduce_(0, inverse, values, "amin") (minima) - the
-      wall time of the steps between two device synchronisations
+  (a) unique, unique(return_index=True), distinct_count, group_by_count, group_by_sum, group_by_min, group_by_max, factorize,
+      factorize followed by zeros(g).index_add_(0, codes, values) (the sums from the ids: one grouping, then any aggregate)
+  (b) the composition: torch.unique(keys, return_counts=True) (counts), torch.unique(keys, return_inverse=True) alone (the ids), or
+      followed by zeros(g).index_add_(0, inverse, values) (sums) / full(g, INT64_MAX).scatter_reduce_(0, inverse, values, "amin")
+      (minima) - the wall time of the steps between two device synchronisations
 
-    python tools/group_by_probe.py [--workloads u1m,distinct,hot,b1g] [--forms a,b] [--steps 8] [--warmup 2] [--out profiles/group_by_probe.jsonl]
+    python tools/group_by_probe.py [--workloads u1m,distinct,hot,b1g] [--forms a,b] [--names factorize,...] [--steps 8] [--warmup 2]
+                                   [--out profiles/group_by_probe.jsonl]
 
 Workloads: u1m = 100M rows over 1M distinct keys, uniform; distinct = 100M rows, all distinct; b1g = 1B rows over 100M distinct keys;
 hot = 100M rows over 1M keys of which one owns every tenth row.  Times of (a) are device times (core_duration_sec, HIP events); (b) is
@@ -50,6 +53,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="u1m,distinct,hot")
     ap.add_argument("--forms", default="a,b")
+    ap.add_argument("--names", default="", help="comma-separated names of the lines to run (default: every line of the chosen forms)")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "group_by_probe.jsonl"))
@@ -83,6 +87,14 @@ def main():
             uk, inv = torch.unique(keys, return_inverse=True)
             return uk.numel(), None, uk, torch.full((uk.numel(),), 2**63 - 1, dtype=torch.int64, device=keys.device).scatter_reduce_(0, inv, vals, "amin")
 
+        def composed_inverse():
+            uk, inv = torch.unique(keys, return_inverse=True)
+            return uk.numel(), None, uk, inv
+
+        def factorize_sum():
+            n_g, sec, codes, uk = flash_join.factorize(keys)
+            return n_g, sec, uk, torch.zeros(n_g, dtype=torch.int64, device=keys.device).index_add_(0, codes, vals)
+
         runs = []
         if "a" in forms:
             runs += [("a", "unique", lambda: flash_join.unique(keys)),
@@ -91,10 +103,15 @@ def main():
                      ("a", "group_by_count", lambda: flash_join.group_by_count(keys)),
                      ("a", "group_by_sum", lambda: flash_join.group_by_sum(keys, vals)),
                      ("a", "group_by_min", lambda: flash_join.group_by_min(keys, vals)),
-                     ("a", "group_by_max", lambda: flash_join.group_by_max(keys, vals))]
+                     ("a", "group_by_max", lambda: flash_join.group_by_max(keys, vals)),
+                     ("a", "factorize", lambda: flash_join.factorize(keys)),
+                     ("a", "factorize+index_add", factorize_sum)]
         if "b" in forms:
-            runs += [("b", "torch.unique(return_counts)", composed_count), ("b", "torch.unique(return_inverse)+index_add", composed_sum),
+            runs += [("b", "torch.unique(return_counts)", composed_count), ("b", "torch.unique(return_inverse)", composed_inverse),
+                     ("b", "torch.unique(return_inverse)+index_add", composed_sum),
                      ("b", "torch.unique(return_inverse)+scatter_reduce_amin", composed_min)]
+        if args.names:
+            runs = [r for r in runs if r[1] in args.names.split(",")]
         for form, name, fn in runs:
             d_med, d_min, w_med = _timed(fn, g, args.steps, args.warmup)
             lt = flash_join.last_timings() if form == "a" else None
