@@ -45,6 +45,8 @@ ALGO_AGG_MAX = 0x8000             # FJ_ALGO_AGG_MAX: ... the maximum
 ALGO_AGG_SIGNED = 0x10000         # FJ_ALGO_AGG_SIGNED: modifier of AGG_MIN / AGG_MAX - the words compare as two's-complement int64 instead of uint64
 ALGO_GROUP_BY = 0x40000           # FJ_ALGO_GROUP_BY: group-by on ONE relation (the build side) - its g distinct keys and one aggregate per key; AGG_* and ROW_IDS modify it (extension)
 ALGO_INVERSE = 0x100000           # FJ_ALGO_INVERSE: modifier of ALGO_GROUP_BY - the values output holds the group id of EVERY row, at the row's position (extension)
+ALGO_RETAIN_BUILD = 0x400000      # FJ_ALGO_RETAIN_BUILD: modifier of ALGO_PROBE_ORDER - the call also leaves its build side prepared on the context (extension)
+ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_ORDER - no build side in the call: the context's prepared one is probed (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -592,27 +594,36 @@ def _probe_order(algo: int, build_keys, build_values, probe_keys, want_values: b
     return m, sec, (vals.view(np.int64) if vals is not None else None), mask
 
 
-def lookup(build_keys, build_values, probe_keys, fill_value: int = 0, return_mask: bool = False):
-    """Dictionary / foreign-key lookup in probe order: values[i] is the build value of probe_keys[i] (a duplicated build key: its
-    FIRST occurrence's), `fill_value` where the key is not among the build keys.  Returns (m, seconds, values) or, return_mask=True,
-    (m, seconds, values, mask): m = probe rows with a partner (what the counting joins return), values int64 of len(probe_keys) (the
-    storage of the uint64 words), mask uint8 1 / 0 per probe row.  One pass over the probe side: no counting pass, no compaction.
-    NumPy arrays in, NumPy arrays out; torch ROCm tensors / DLPack are joined in place and the outputs live on their device."""
+def _fill_word(fill_value) -> int:
     if isinstance(fill_value, bool) or not isinstance(fill_value, (int, np.integer)):
         raise TypeError(f"lookup: fill_value must be an integer, got {type(fill_value).__name__}")
     fill_value = int(fill_value)
     if not -(1 << 63) <= fill_value < (1 << 64):
         raise ValueError("lookup: fill_value does not fit 64 bits")
-    if build_values is None:
-        raise ValueError("lookup: build_values is required (isin / lookup_indices take none)")
-    need_mask = return_mask or fill_value != 0
-    m, sec, vals, mask = _probe_order(ALGO_ADAPTIVE, build_keys, build_values, probe_keys, True, need_mask)
+    return fill_value
+
+
+def _apply_fill(vals, mask, m: int, fill_value: int) -> None:
     if fill_value != 0 and m < vals.shape[0]:                # applied through the mask, as _fill does for left_join's ranges
         word = int(np.array(fill_value % (1 << 64), dtype=np.uint64).view(np.int64))     # int64 storage of the uint64 word
         if _is_torch_tensor(vals):
             vals.masked_fill_(mask == 0, word)
         else:
             vals[mask == 0] = word
+
+
+def lookup(build_keys, build_values, probe_keys, fill_value: int = 0, return_mask: bool = False):
+    """Dictionary / foreign-key lookup in probe order: values[i] is the build value of probe_keys[i] (a duplicated build key: its
+    FIRST occurrence's), `fill_value` where the key is not among the build keys.  Returns (m, seconds, values) or, return_mask=True,
+    (m, seconds, values, mask): m = probe rows with a partner (what the counting joins return), values int64 of len(probe_keys) (the
+    storage of the uint64 words), mask uint8 1 / 0 per probe row.  One pass over the probe side: no counting pass, no compaction.
+    NumPy arrays in, NumPy arrays out; torch ROCm tensors / DLPack are joined in place and the outputs live on their device."""
+    fill_value = _fill_word(fill_value)
+    if build_values is None:
+        raise ValueError("lookup: build_values is required (isin / lookup_indices take none)")
+    need_mask = return_mask or fill_value != 0
+    m, sec, vals, mask = _probe_order(ALGO_ADAPTIVE, build_keys, build_values, probe_keys, True, need_mask)
+    _apply_fill(vals, mask, m, fill_value)
     return (m, sec, vals, mask) if return_mask else (m, sec, vals)
 
 
@@ -628,6 +639,201 @@ def lookup_indices(build_keys, probe_keys):
     the build keys, -1 where there is none; int64 of len(probe_keys).  join_indices(how="left") without the compaction."""
     m, sec, idx, _ = _probe_order(ALGO_ADAPTIVE | ALGO_ROW_IDS, build_keys, None, probe_keys, True, False)
     return m, sec, idx
+
+
+# ---- extension: a prepared build side - build once, probe many times (csrc/fj_prepared.hip) ------------------------------------------
+def _device_scope(dev: int):
+    """hipMalloc and hipMemcpy of the NumPy staging act on the calling thread's current device"""
+    import contextlib
+    try:
+        import torch
+    except ImportError:
+        if dev != 0:
+            raise RuntimeError("build_index: staging NumPy arrays on a device other than 0 needs torch (it selects the device)")
+        return contextlib.nullcontext()
+    return torch.cuda.device(dev)
+
+
+class _Staged:
+    """device buffers of a NumPy call (fj_device_malloc), freed on exit"""
+    def __init__(self):
+        self.L, self.ptrs = _lib.load(), []
+
+    def alloc(self, nbytes: int) -> int:
+        p = ctypes.c_void_p()
+        check(self.L.fj_device_malloc(ctypes.byref(p), nbytes))
+        self.ptrs.append(p)
+        return p.value
+
+    def upload(self, arr: np.ndarray) -> int:
+        d = self.alloc(arr.nbytes)
+        check(self.L.fj_memcpy_h2d(d, arr.ctypes.data, arr.nbytes))
+        return d
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.ptrs:
+            self.L.fj_device_free(p)
+        self.ptrs = []
+        return False
+
+
+class Index:
+    """A build side prepared once (build_index) and probed any number of times: `lookup`, `isin` and `lookup_indices` return what the
+    module functions of the same name return for (build_keys, build_values, probe_keys), without the build side's partition passes
+    and first-occurrence logic in every call.  The index owns a native context of its own - the prepared side lives in device memory
+    of that context, beside the workspace of the probe side's passes - and a lock: calls on one index are serialised, two indexes
+    are independent.  A context manager; `close()` frees the device memory, after which every call raises.
+
+    num_keys: distinct build keys (g); num_rows: build rows (nb); has_values: built with build_values; device: the ROCm device index."""
+
+    def __init__(self, ctx: int, device: int, num_rows: int, num_keys: int, has_values: bool):
+        self._ctx, self._lock = ctx, threading.RLock()
+        self.device, self.num_rows, self.num_keys, self.has_values = device, num_rows, num_keys, has_values
+
+    def close(self) -> None:
+        with self._lock:
+            ctx, self._ctx = self._ctx, None
+            if ctx:
+                _lib.load().fj_ctx_destroy(ctx)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                          # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def _probe(self, probe_keys, flags: int, want_values: bool, want_mask: bool):
+        """(m, seconds, values or None, mask or None) as _probe_order returns them, against the prepared side"""
+        global _last
+        L = _lib.load()
+        algo = ALGO_PROBE_ORDER | ALGO_REUSE_BUILD | flags
+        cnt, t = ctypes.c_uint64(0), FjTimings()
+        pk = _from_dlpack_if_device(probe_keys)
+        if _is_torch_tensor(pk) and pk.is_cuda:
+            import torch
+            pk = _dev_tensor(pk, "probe_keys")
+            dev = pk.device.index if pk.device.index is not None else torch.cuda.current_device()
+            if dev != self.device:
+                raise ValueError(f"probe_keys live on device {dev}, the index on device {self.device}")
+            n_p = pk.numel()
+            ov = torch.empty(n_p, dtype=torch.int64, device=pk.device) if want_values else None
+            om = torch.empty(n_p, dtype=torch.uint8, device=pk.device) if want_mask else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            with self._lock:
+                if not self._ctx:
+                    raise RuntimeError("this Index is closed")
+                check(L.fj_join_device(self._ctx, algo, 0, 1, None, None, 0, pk.data_ptr(), n_p, stream, 64, ctypes.byref(cnt),
+                                       om.data_ptr() if want_mask else None, ov.data_ptr() if want_values else None, n_p, ctypes.byref(t)))
+            _last = t
+            return int(cnt.value), t.total_ms * 1e-3, ov, om
+        if _is_torch_tensor(pk):
+            pk = pk.numpy()
+        pk = _as_u64_host(pk, "probe_keys")
+        n_p = pk.size
+        vals = np.empty(n_p, np.int64) if want_values else None
+        mask = np.empty(n_p, np.uint8) if want_mask else None
+        with self._lock:
+            if not self._ctx:
+                raise RuntimeError("this Index is closed")
+            with _device_scope(self.device), _Staged() as st:
+                d_pk = st.upload(pk)
+                d_ov = st.alloc(n_p * 8) if want_values else None
+                d_om = st.alloc(n_p) if want_mask else None
+                check(L.fj_join_device(self._ctx, algo, 0, 1, None, None, 0, d_pk, n_p, None, 64, ctypes.byref(cnt), d_om, d_ov, n_p, ctypes.byref(t)))
+                if want_values:
+                    check(L.fj_memcpy_d2h(vals.ctypes.data, d_ov, n_p * 8))
+                if want_mask:
+                    check(L.fj_memcpy_d2h(mask.ctypes.data, d_om, n_p))
+        _last = t
+        return int(cnt.value), t.total_ms * 1e-3, vals, mask
+
+    def lookup(self, probe_keys, fill_value: int = 0, return_mask: bool = False):
+        """lookup(build_keys, build_values, probe_keys, fill_value, return_mask) of this module against the prepared side"""
+        fill_value = _fill_word(fill_value)
+        if not self.has_values:
+            raise ValueError("Index.lookup: this index was built without build_values (isin and lookup_indices need none)")
+        need_mask = return_mask or fill_value != 0
+        m, sec, vals, mask = self._probe(probe_keys, 0, True, need_mask)
+        _apply_fill(vals, mask, m, fill_value)
+        return (m, sec, vals, mask) if return_mask else (m, sec, vals)
+
+    def isin(self, probe_keys):
+        """isin(probe_keys, build_keys) of this module against the prepared side"""
+        m, sec, _, mask = self._probe(probe_keys, 0, False, True)
+        return m, sec, mask
+
+    def lookup_indices(self, probe_keys):
+        """lookup_indices(build_keys, probe_keys) of this module against the prepared side"""
+        m, sec, idx, _ = self._probe(probe_keys, ALGO_ROW_IDS, True, False)
+        return m, sec, idx
+
+
+def build_index(build_keys, build_values=None, device: Optional[int] = None) -> Index:
+    """Prepare a build side once for many probes: returns an Index whose lookup / isin / lookup_indices answer as the module functions
+    do for these build_keys (and build_values; None: a keys-only index, lookup then raises).  The keys, the values and every key's
+    first-occurrence position are copied into device memory the index owns (16 bytes per build row, 24 with values): the caller's
+    arrays may be overwritten or freed as soon as this returns.  Torch ROCm tensors / DLPack are read in place, on their device and the
+    current stream, and the outputs of later probes with device tensors live on the device.  NumPy arrays are staged through
+    fj_device_malloc / fj_memcpy_*, here and in every probe with NumPy keys: synchronous and unpipelined copies - a host-side caller
+    who wants the copy hidden under the join uses the one-shot functions - and their outputs are NumPy.  `device`: where a NumPy-built
+    index lives (default 0); for device tensors it must be their device.  An index built from NumPy arrays may be probed with device
+    tensors of its device and the reverse.  The plan is chosen now, from the build side's size and the options in force."""
+    global _last
+    L = _lib.load()
+    bk, bv = (_from_dlpack_if_device(x) if x is not None else None for x in (build_keys, build_values))
+    cnt, t = ctypes.c_uint64(0), FjTimings()
+    algo = ALGO_ADAPTIVE | ALGO_PROBE_ORDER | ALGO_RETAIN_BUILD
+    on_device = _is_torch_tensor(bk) and bk.is_cuda
+    if on_device:
+        import torch
+        bk = _dev_tensor(bk, "build_keys")
+        bv = _dev_tensor(bv, "build_values") if bv is not None else None
+        n_b, n_v = bk.numel(), (bv.numel() if bv is not None else 0)
+        dev = bk.device.index if bk.device.index is not None else torch.cuda.current_device()
+        if bv is not None and (not bv.is_cuda or bv.device != bk.device):
+            raise ValueError("build_values must live on the device of build_keys")
+    else:
+        if _is_torch_tensor(bk):
+            bk = bk.numpy()
+        if _is_torch_tensor(bv):
+            bv = bv.cpu().numpy()
+        bk = _as_u64_host(bk, "build_keys")
+        bv = _as_u64_host(bv, "build_values") if bv is not None else None
+        n_b, n_v = bk.size, (bv.size if bv is not None else 0)
+        dev = 0 if device is None else int(device)
+    if bv is not None and n_v < n_b:
+        raise ValueError(f"build_values has {n_v} elements, build_keys has {n_b}")
+    if device is not None and int(device) != dev:
+        raise ValueError(f"device={device}, but build_keys live on device {dev}")
+    ctx = L.fj_ctx_create(dev)
+    if not ctx:
+        raise RuntimeError(_lib.last_error())
+    try:
+        if on_device:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(L.fj_join_device(ctx, algo, 0, 1, bk.data_ptr(), bv.data_ptr() if bv is not None else None, n_b, None, 0, stream, 64,
+                                   ctypes.byref(cnt), None, None, 0, ctypes.byref(t)))
+        else:
+            with _device_scope(dev), _Staged() as st:
+                d_bk = st.upload(bk)
+                d_bv = st.upload(bv[:n_b]) if bv is not None else None
+                check(L.fj_join_device(ctx, algo, 0, 1, d_bk, d_bv, n_b, None, 0, None, 64, ctypes.byref(cnt), None, None, 0, ctypes.byref(t)))
+        check(L.fj_ctx_trim(ctx))       # the build side's passes are over: their workspace goes back, the prepared side is no workspace
+    except BaseException:
+        L.fj_ctx_destroy(ctx)
+        raise
+    _last = t
+    return Index(ctx, dev, n_b, int(cnt.value), bv is not None)
 
 
 # ---- extension: build-order aggregate joins (one word per build row, at the build row's position; csrc/fj_group.hip) -----------------
@@ -1003,5 +1209,5 @@ ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_rad
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
               "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
-              "factorize"]
-__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace"]
+              "factorize", "build_index"]
+__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

@@ -1,6 +1,7 @@
 // fj_host.h -- host-side state shared by the translation units behind the C ABI (include/flashjoin.h):
 //   fj_plan.hip   workspace, plans, the partition-pass state machine, contexts, options, diagnostics
 //   fj_joins.hip  one-shot joins (the reference's drivers, hash_join.cpp:315-594), emit, owner split, bloom export / prefilter
+//   fj_prepared.hip  a build side prepared once and probed many times (FJ_ALGO_RETAIN_BUILD / FJ_ALGO_REUSE_BUILD)
 //   fj_stream.hip joins whose relations arrive in pieces, the owner shuffle's pack / append side
 //   fj_hostentry.hip  the NumPy (host-buffer) entry
 // (one file, fj_api.hip, until round 4).
@@ -141,6 +142,25 @@ struct SingleOut { u64* keys = nullptr; u64* vals = nullptr; size_t cap = 0; boo
 // against per-bucket Bloom filters of the build side's level L before pass L+1 (csrc/fj_bloom.hip)
 struct Plan { int bits = 0, npass = 0; int fan_log[4] = {0, 0, 0, 0}; int bloom_level = 0; };
 
+// The build side that FJ_ALGO_RETAIN_BUILD left on the context for FJ_ALGO_REUSE_BUILD (csrc/fj_prepared.hip): at most one, in device
+// memory of its own (hipMalloc, not a workspace slot: fj_ctx_trim and fj_ctx_workspace_bytes do not see it), freed when it is replaced
+// and by fj_ctx_destroy.  Not the pending result: begin_step leaves it alone
+struct Prepared {
+    enum Form { EMPTY, LDS, HBM };       // no build rows / runs per final partition for the LDS table / the global table
+    bool valid = false;
+    Form form = EMPTY;
+    bool has_vals = false;               // prepared with d_build_vals (or empty): the value form may be asked for
+    int top_bits = 64, path = 0;         // hash_top_bits of the plan; fj_timings::path of a probe against it
+    Plan plan; u32 nparts = 0;           // LDS: the stored plan and its final partitions
+    size_t nb = 0; u64 g = 0;            // build rows, distinct keys
+    // LDS: g mixed keys, first positions and values (nb rows allocated each), aux = nparts FjPrepRun records
+    // HBM: the table's key and first-position planes (cap_mask + 1 slots each), vals = a copy of the nb values, aux = the table's
+    //      flag word and, 8 bytes in, the empty key's first position
+    u64* keys = nullptr; u64* rows = nullptr; u64* vals = nullptr; void* aux = nullptr;
+    u64 cap_mask = 0;
+    size_t bytes = 0;                    // device memory held
+};
+
 // iteration state over the plan's passes for one relation (see pass_prepare / pass_launch / pass_complete)
 struct PassIter {
     int side = 0; bool has_vals = false; size_t n = 0; Plan plan; int used = 64; u32 parents = 1; u64 lbound = 0;
@@ -215,6 +235,7 @@ struct fj_ctx {
     fjh::Scalars* d_sc = nullptr;
     fjh::Scalars* h_sc = nullptr;
     fjh::Pending pend;
+    fjh::Prepared prep;                // the prepared build side (FJ_ALGO_RETAIN_BUILD), if any
     StreamState st;
     PackState pk;
     BcastState bc;
@@ -314,6 +335,13 @@ int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb
 // either may be null; *out_count = probe rows with a partner; rid: d_ov holds first-occurrence build positions (~0: none) ----
 int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
                      hipStream_t s, fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid);
+
+// ---- prepared build side (fj_prepared.hip): FJ_ALGO_RETAIN_BUILD prepares bk / bv (null: keys only) under the plan the one-shot call
+// would take now and leaves it on the context - on failure the caller calls prepared_free; prepared_probe is FJ_ALGO_REUSE_BUILD's
+// probe side against it, outputs and count as join_probe_order's ----
+void prepared_free(fj_ctx* c);
+int prepared_retain(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t);
+int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid);
 
 // ---- build-order aggregate joins (fj_group.hip): FJ_ALGO_BUILD_ORDER; d_cnt[i] and / or d_sum[i] (nb words each) for every build row i,
 // either may be null; pv: the probe side's value column (np words, read for d_sum only); agg: the aggregate d_sum receives, FJ_GJ_SUM or

@@ -217,6 +217,9 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (np && out_vals && !bv) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER with out_vals needs build_vals (here the probe side's value column, np words)");
     }
     if (po) {                                                  // probe-order join: *out_vals np words, *out_keys np BYTES (the mask)
+        if (algo & (FJ_ALGO_RETAIN_BUILD | FJ_ALGO_REUSE_BUILD))   // (without FJ_ALGO_PROBE_ORDER: unknown algos below)
+            return set_err("fj_join_host: FJ_ALGO_%s_BUILD is not served here (the internal context is shared by every host-buffer call of the process): call fj_join_device on a context of your own",
+                           (algo & FJ_ALGO_RETAIN_BUILD) ? "RETAIN" : "REUSE");
         if (many_host || left || anti || full || allc)
             return set_err("fj_join_host: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : "ALL_COPIES");

@@ -331,6 +331,42 @@ hipError_t fj_launch_probe_order_join(const FjLdsJoinArgs& a, bool first, u64 np
 // global table built by fj_launch_gt_build_first (vals = a.out_vals != nullptr): thread i serves probe row i
 hipError_t fj_launch_gt_probe_order(const FjGtArgs& a, unsigned long long* miss_total, unsigned char* mask, hipStream_t s);
 
+// ---- prepared build side (csrc/fj_prepared.hip; FJ_ALGO_RETAIN_BUILD / FJ_ALGO_REUSE_BUILD of include/flashjoin.h) -------------------
+// Three dense planes of one row per DISTINCT build key - the mixed key, the position of its first occurrence, that row's value - in
+// which final partition p owns the run [runs[p].off, runs[p].off + runs[p].n); the mixed empty marker is an ordinary row of its run.
+struct FjPrepRun { u64 off, n; };
+// One workgroup per final partition of `rel` (chunk lists whose vals plane holds the rows' positions; flat arrays: one partition, the
+// index is the position): the partition's distinct keys, first positions and - orig_vals != nullptr - orig_vals[first position] go to
+// the run that ONE atomic on `cursor` reserves; the cursor ends as g.  runs[] is zeroed before the launch (an empty partition writes
+// no record).  A partition of more distinct keys than the probe kernel's table takes writes nothing and raises FJ_ERR_LDS_FULL; a row
+// at or beyond out_capacity or a position at or beyond nrows is not stored (FJ_ERR_OUTCAP).
+struct FjPrepBuildArgs {
+    FjChunkSet rel;
+    u32 nparts;
+    const u64* orig_vals; u64 nrows;                         // the caller's build_values (nullptr: a keys-only side) / build rows
+    u64* out_keys; u64* out_rows; u64* out_vals;
+    u64 out_capacity;
+    FjPrepRun* runs;
+    unsigned long long* cursor;                              // device scalar, zeroed before the launch
+    u32* err;
+};
+hipError_t fj_launch_prep_build(const FjPrepBuildArgs& a, hipStream_t s);
+// The probe-order join's probe phase against those runs; the work items are the one-shot join's (items: tiles of the probe chunk lists;
+// nullptr: nsplit equal slices of a flat probe side).  out_vals[pos] = plane[row of the key] (plane: the values or the positions), or
+// miss_word; out_vals == nullptr: the mask form, a keys-only table.  total counts the hits, miss_total the misses; positions >= np are
+// not written (FJ_ERR_OUTCAP); a run that is not one of fj_launch_prep_build's (beyond the table, beyond nkeys rows): FJ_ERR_LDS_FULL.
+struct FjPrepProbeArgs {
+    FjChunkSet probe;
+    u32 nparts, nsplit;
+    const uint4* items; const u32* nitems_dev; u32 items_cap;
+    const u64* keys; const u64* plane; const FjPrepRun* runs; u64 nkeys;
+    u64 miss_word;
+    u64* out_vals; unsigned char* mask; u64 np;
+    unsigned long long* total; unsigned long long* miss_total;
+    u32* err;
+};
+hipError_t fj_launch_prep_probe(const FjPrepProbeArgs& a, hipStream_t s);
+
 // ---- build-order aggregate joins (csrc/fj_group.hip; FJ_ALGO_BUILD_ORDER of include/flashjoin.h) ------------------------------------
 // One output word per build row at the row's own position (the build chunk pool's vals plane; flat arrays: the index).  sum = false:
 // out[pos] += the probe rows of the item's slice that carry the row's key; sum = true: += the sum of their values (a.probe.vals).  out

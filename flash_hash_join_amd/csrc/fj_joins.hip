@@ -687,6 +687,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
+    const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
+    const uint64_t* d_rv = nullptr;                         // FJ_ALGO_RETAIN_BUILD: the caller's d_build_vals as given (null: a keys-only side)
     const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
                asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0;
     int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
@@ -751,7 +753,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     if (po) {
         // probe-order join (csrc/fj_aligned.hip): every check before any device work, so that it holds for a null context too.
         // d_out_keys is the byte mask here: no alignment asked of it
-        algo &= ~FJ_ALGO_PROBE_ORDER;
+        algo &= ~(FJ_ALGO_PROBE_ORDER | FJ_ALGO_RETAIN_BUILD | FJ_ALGO_REUSE_BUILD);
         if (many || left || anti || full || allc)
             return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : "ALL_COPIES");
@@ -759,7 +761,11 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (np && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER needs an output (d_out_vals, the byte mask d_out_keys, or both)");
         if (out_capacity < np) return set_err("fj_join_device: output capacity %zu < %zu probe rows (FJ_ALGO_PROBE_ORDER writes every probe row)", out_capacity, np);
         if ((uintptr_t)d_out_vals & 7) return set_err("fj_join_device: d_out_vals must be 8-byte aligned");
+        // the prepared build side (csrc/fj_prepared.hip): one call prepares OR reuses, and a reuse brings no build side of its own
+        if (retain && reuse) return set_err("fj_join_device: FJ_ALGO_RETAIN_BUILD cannot be combined with FJ_ALGO_REUSE_BUILD (a call prepares a build side or probes the prepared one)");
+        if (reuse && (d_bk || d_bv || nb)) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD takes no build side (d_build_keys and d_build_vals must be NULL and nb 0: the context's prepared side is probed)");
         if (nb && d_out_vals && !rid && !d_bv) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER with d_out_vals needs d_build_vals (only FJ_ALGO_ROW_IDS and the mask alone read no build value)");
+        d_rv = d_bv;
         if (!d_bv) d_bv = d_bk;                             // the mask alone reads no value (the checks below want a pointer)
     }
     if (rid && !gb) {
@@ -848,6 +854,27 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     }
     if (bo) {                                               // one row per build row at its own position, never a pending result
         if (join_group(c, use_radix, d_bk, nb, d_pk, d_pv, np, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, agg)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (po && (retain || reuse)) {                          // ... against a build side the context keeps prepared (csrc/fj_prepared.hip)
+        if (retain) {
+            if (prepared_retain(c, use_radix, d_bk, d_rv, nb, hash_top_bits, s, &t)) { prepared_free(c); return 1; }   // (a failed call leaves none)
+            count = c->prep.g;                              // np == 0: the call only prepares, *out_count = the distinct build keys
+        } else {
+            if (!c->prep.valid) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD without a prepared build side on this context (FJ_ALGO_RETAIN_BUILD makes one)");
+            if (hash_top_bits != c->prep.top_bits) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with hash_top_bits %d, the build side was prepared with %d", hash_top_bits, c->prep.top_bits);
+            if (np && d_out_vals && !rid && !c->prep.has_vals)
+                return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with d_out_vals needs a build side prepared with d_build_vals (this one has keys only: the mask and FJ_ALGO_ROW_IDS work)");
+        }
+        if (np || reuse) {
+            fj_timings tp; memset(&tp, 0, sizeof tp); tp.sampled_hit_bp = -1;
+            if (prepared_probe(c, d_pk, np, s, &tp, &count, (unsigned char*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
+            if (retain) { tp.build_phase_ms = t.build_phase_ms; tp.total_ms += t.total_ms; tp.fell_back = t.fell_back; }
+            t = tp;
+        }
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

@@ -509,6 +509,7 @@ fj_ctx* fj_ctx_create(int device) {
 void fj_ctx_destroy(fj_ctx* c) {
     if (!c) return;
     DeviceGuard guard(c->device);
+    prepared_free(c);
     for (auto& b : c->bufs) if (b.p) (void)hipFree(b.p);
     for (int i = 0; i < E_NEV; ++i) (void)hipEventDestroy(c->ev[i]);
     if (c->side) (void)hipStreamDestroy(c->side);

@@ -216,6 +216,40 @@ extern "C" {
  * FJ_ALGO_AGG_MAX or FJ_ALGO_AGG_SIGNED (no aggregate in the same call) or with FJ_ALGO_ROW_IDS (d_out_vals is taken: one per-call
  * output); materialize = 0; fj_join_device with d_out_keys == NULL or d_out_vals == NULL (and nb > 0). */
 #define FJ_ALGO_INVERSE    0x100000
+/* EXTENSION: modifiers of FJ_ALGO_PROBE_ORDER (without it each of them is an unknown algo; csrc/fj_prepared.hip) for a PREPARED build
+ * side: one dictionary or dimension table probed by many batches - a foreign-key column arriving in morsels, id remapping per training
+ * step, an IN list applied to every partition of a fact table - pays its partition passes and its first-occurrence logic once.
+ *
+ * FJ_ALGO_RETAIN_BUILD: the call does what the same call does without the flag - same outputs, *out_count = m - and in addition leaves
+ * the build side prepared on the context: deduplicated to the first occurrence of every key, grouped by the final partitions of the
+ * plan, in device memory the context owns OUTSIDE its workspace.  The build keys are copied, the values when d_build_vals is non-NULL,
+ * the first-occurrence positions always: the caller may overwrite or free its build arrays as soon as the call returns.  np == 0: the
+ * call only prepares - both outputs may be NULL, *out_count = g, the number of distinct build keys.  The base value (ADAPTIVE, SCALAR
+ * or RADIX) and the options "plan_target_keys", "radix_threshold" and "scalar_hbm_table" are read NOW and choose between the partitioned
+ * form and the HBM-table form exactly as for the one-shot call; the plan and hash_top_bits are stored with the side.  A partition of
+ * more distinct keys than the LDS table takes prepares the HBM-table form instead (fj_timings: fell_back = 1 in this call).  nb == 0
+ * prepares an empty side, on which every lookup misses, and frees what was held.  fj_timings: the preparation in build_phase_ms.
+ * A context holds ONE prepared side: the next FJ_ALGO_RETAIN_BUILD call replaces it (one that fails after its argument checks leaves
+ * none) and fj_ctx_destroy frees it.  Nothing else touches it - not another join of any kind on the context, not fj_emit_pairs, not
+ * fj_ctx_trim - fj_ctx_workspace_bytes does not count it, and it is not the context's pending result.  Memory: 16 bytes per build row,
+ * 24 with values, and 16 bytes per final partition; the HBM-table form 16 bytes per table slot (2 to 4 slots per row) and 8 bytes per
+ * row with values.
+ *
+ * FJ_ALGO_REUSE_BUILD: d_build_keys and d_build_vals must be NULL and nb 0; the probe side runs against the context's prepared side.
+ * The outputs are exactly those of FJ_ALGO_PROBE_ORDER on the build side that was prepared: d_out_vals[i] the first occurrence's build
+ * value, 0 on a miss (FJ_ALGO_ROW_IDS: its position, UINT64_MAX on a miss), the byte mask in d_out_keys, either or both, *out_count = m;
+ * every one of the np positions is written exactly once, nothing at or beyond np is touched, np == 0 does nothing.  The base value
+ * must be 0..2 and is otherwise ignored: the stored plan decides.  The context's workspace serves the probe side's passes only.
+ * fj_timings: build_phase_ms = 0; passes, radix_bits, partitions and path are those of the prepared side.
+ *
+ * Refused up front, before any device work: either flag without FJ_ALGO_PROBE_ORDER (unknown algo) or with anything it refuses; both
+ * flags together; FJ_ALGO_REUSE_BUILD with a build side (a non-NULL d_build_keys or d_build_vals, nb != 0).  Refused on the context,
+ * which stays usable: FJ_ALGO_REUSE_BUILD with no prepared side, with another hash_top_bits than the prepared side's, or asking for
+ * values (d_out_vals without FJ_ALGO_ROW_IDS) from a side prepared without d_build_vals - the mask and the row-id form always work.
+ * fj_join_host refuses both flags (its internal context is shared by every host-buffer call of the process): use fj_join_device on a
+ * context of your own. */
+#define FJ_ALGO_RETAIN_BUILD 0x400000
+#define FJ_ALGO_REUSE_BUILD  0x800000
 
 typedef struct fj_ctx fj_ctx;
 
