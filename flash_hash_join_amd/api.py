@@ -47,6 +47,7 @@ ALGO_GROUP_BY = 0x40000           # FJ_ALGO_GROUP_BY: group-by on ONE relation (
 ALGO_INVERSE = 0x100000           # FJ_ALGO_INVERSE: modifier of ALGO_GROUP_BY - the values output holds the group id of EVERY row, at the row's position (extension)
 ALGO_RETAIN_BUILD = 0x400000      # FJ_ALGO_RETAIN_BUILD: modifier of ALGO_PROBE_ORDER - the call also leaves its build side prepared on the context (extension)
 ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_ORDER - no build side in the call: the context's prepared one is probed (extension)
+ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_ORDER | ALGO_REUSE_BUILD - the outputs are combined into as they are instead of filled first (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -776,6 +777,162 @@ class Index:
         """lookup_indices(build_keys, probe_keys) of this module against the prepared side"""
         m, sec, idx, _ = self._probe(probe_keys, ALGO_ROW_IDS, True, False)
         return m, sec, idx
+
+    # ---- build-order aggregates onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD [| FJ_ALGO_ACCUMULATE]) ----
+    def _check_out(self, name: str, what: str, buf, on_device: bool):
+        """a caller's accumulator: of the kind of probe_keys, int64 storage, num_rows elements, contiguous (before any native call)"""
+        if on_device:
+            if not _is_torch_tensor(buf):
+                raise TypeError(f"{name}: {what} must be a torch tensor on the index's device, like probe_keys (got {type(buf).__name__})")
+            import torch
+            if buf.dtype != torch.int64:
+                raise TypeError(f"{name}: {what} must be int64, got {buf.dtype}")
+            if not buf.is_cuda or (buf.device.index if buf.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError(f"{name}: {what} lives on {buf.device}, the index on device {self.device}")
+            if buf.dim() != 1 or buf.numel() != self.num_rows:
+                raise ValueError(f"{name}: {what} has shape {tuple(buf.shape)}, the index has {self.num_rows} rows")
+            if not buf.is_contiguous():
+                raise ValueError(f"{name}: {what} must be contiguous (it is combined into in place)")
+        else:
+            if not isinstance(buf, np.ndarray):
+                raise TypeError(f"{name}: {what} must be a NumPy array, like probe_keys (got {type(buf).__name__})")
+            if buf.dtype not in (np.int64, np.uint64):
+                raise TypeError(f"{name}: {what} must be int64 or uint64, got {buf.dtype}")
+            if buf.ndim != 1 or buf.size != self.num_rows:
+                raise ValueError(f"{name}: {what} has shape {buf.shape}, the index has {self.num_rows} rows")
+            if not buf.flags.c_contiguous or not buf.flags.writeable:
+                raise ValueError(f"{name}: {what} must be a writable C-contiguous array (it is combined into in place)")
+
+    def _group(self, name: str, probe_keys, probe_values, agg: int, out, counts_out, want_counts: bool):
+        """(m, seconds, values or None, counts or None): num_rows int64 words each, where probe_keys live.  probe_values None: the
+        count form (`out` is then the counts).  out / counts_out given: ALGO_ACCUMULATE, combined into in place and returned"""
+        global _last
+        L = _lib.load()
+        want_vals = probe_values is not None
+        if not want_vals:
+            counts_out, out, want_counts = out, None, True
+        want_counts = bool(want_counts) or counts_out is not None
+        pk, pv = (_from_dlpack_if_device(x) if x is not None else None for x in (probe_keys, probe_values))
+        on_device = _is_torch_tensor(pk) and pk.is_cuda
+        if want_vals and want_counts and (out is None) != (counts_out is None):
+            raise ValueError(f"{name}: out and counts_out are given together or not at all (one call either fills its outputs or combines into them)")
+        accumulate = out is not None or counts_out is not None
+        for what, buf in (("out" if want_vals else "out (the counts)", out if want_vals else counts_out), ("counts_out", counts_out if want_vals else None)):
+            if buf is not None:
+                self._check_out(name, what, buf, on_device)
+        algo = ALGO_BUILD_ORDER | ALGO_REUSE_BUILD | agg | (ALGO_ACCUMULATE if accumulate else 0)
+        n_b = self.num_rows
+        cnt, t = ctypes.c_uint64(0), FjTimings()
+        if on_device:
+            import torch
+            pk = _dev_tensor(pk, "probe_keys")
+            dev = pk.device.index if pk.device.index is not None else torch.cuda.current_device()
+            if dev != self.device:
+                raise ValueError(f"probe_keys live on device {dev}, the index on device {self.device}")
+            n_p = pk.numel()
+            if want_vals:
+                if not (_is_torch_tensor(pv) and pv.is_cuda and pv.device == pk.device):
+                    raise ValueError(f"{name}: probe_values must live on the device of probe_keys")
+                pv = _dev_tensor(pv, "probe_values")
+                if pv.numel() < n_p:
+                    raise ValueError(f"{name}: probe_values has {pv.numel()} elements, probe_keys has {n_p}")
+            ov = (out if out is not None else torch.empty(n_b, dtype=torch.int64, device=pk.device)) if want_vals else None
+            oc = (counts_out if counts_out is not None else torch.empty(n_b, dtype=torch.int64, device=pk.device)) if want_counts else None
+            dummy = torch.empty(2, dtype=torch.int64, device=pk.device) if n_b == 0 else None      # (an empty tensor has no address; nothing is written)
+            ptr = lambda x: None if x is None else (x.data_ptr() if n_b else dummy.data_ptr())
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            with self._lock:
+                if not self._ctx:
+                    raise RuntimeError("this Index is closed")
+                check(L.fj_join_device(self._ctx, algo, 0, 1, None, pv.data_ptr() if want_vals and n_p else None, 0, pk.data_ptr() if n_p else None, n_p,
+                                       stream, 64, ctypes.byref(cnt), ptr(oc), ptr(ov), n_b, ctypes.byref(t)))
+            _last = t
+            return int(cnt.value), t.total_ms * 1e-3, ov, oc
+        if _is_torch_tensor(pk):
+            pk = pk.numpy()
+        if _is_torch_tensor(pv):
+            pv = pv.cpu().numpy()
+        pk = _as_u64_host(pk, "probe_keys")
+        n_p = pk.size
+        if want_vals:
+            pv = _as_u64_host(pv, "probe_values")
+            if pv.size < n_p:
+                raise ValueError(f"{name}: probe_values has {pv.size} elements, probe_keys has {n_p}")
+        vals = (out if out is not None else np.empty(n_b, np.int64)) if want_vals else None
+        counts = (counts_out if counts_out is not None else np.empty(n_b, np.int64)) if want_counts else None
+        with self._lock:
+            if not self._ctx:
+                raise RuntimeError("this Index is closed")
+            with _device_scope(self.device), _Staged() as st:
+                d_pk = st.upload(pk)
+                d_pv = st.upload(pv[:n_p]) if want_vals else None
+                d_ov = st.alloc(max(n_b, 2) * 8) if want_vals else None
+                d_oc = st.alloc(max(n_b, 2) * 8) if want_counts else None
+                if accumulate and n_b:                               # the running aggregate goes up, is combined into and comes back
+                    for d, h in ((d_ov, vals), (d_oc, counts)):
+                        if h is not None:
+                            check(L.fj_memcpy_h2d(d, h.ctypes.data, n_b * 8))
+                check(L.fj_join_device(self._ctx, algo, 0, 1, None, d_pv if n_p else None, 0, d_pk if n_p else None, n_p, None, 64, ctypes.byref(cnt), d_oc, d_ov, n_b, ctypes.byref(t)))
+                for d, h in ((d_ov, vals), (d_oc, counts)):
+                    if h is not None and n_b:
+                        check(L.fj_memcpy_d2h(h.ctypes.data, d, n_b * 8))
+        _last = t
+        return int(cnt.value), t.total_ms * 1e-3, vals, counts
+
+    def group_count(self, probe_keys, out=None):
+        """Orders per customer over a batch: (m, seconds, counts), counts[i] = the rows of probe_keys whose key equals the index's build
+        key i, int64 of num_rows, aligned with the build rows; m = probe rows with a partner = counts.sum() of this batch.
+        FIRST-OCCURRENCE RULE (the Index rule: lookup_indices names the first row): a duplicated build key's count lands at the key's
+        FIRST build row and every further copy holds 0 - group_join_count gives every copy the count; on distinct build keys the two
+        agree bit for bit.  out=: a buffer of num_rows int64 (a contiguous device tensor on the index's device, used on the current
+        stream, for device probe_keys; a writable C-contiguous int64 / uint64 NumPy array, staged up and back, for NumPy probe_keys) that
+        the call ADDS into in place and returns (ALGO_ACCUMULATE): `m, s, acc = idx.group_count(pk0)`, then `idx.group_count(pk1, out=acc)`
+        is a running aggregate over morsels.  Without out= a fresh, filled array is returned each time.  No build value is read: a
+        keys-only index serves every group_* form."""
+        m, sec, _, counts = self._group("Index.group_count", probe_keys, None, 0, out, None, True)
+        return m, sec, counts
+
+    def group_sum(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None):
+        """Revenue per product over a batch: (m, seconds, sums) or, with return_counts / counts_out, (m, seconds, sums, counts).  sums[i] =
+        the sum modulo 2^64 of probe_values[j] over the rows j of probe_keys whose key equals build key i (int64 storage of the uint64
+        words), at the key's FIRST build row; 0 in every other row (group_count: the first-occurrence rule).  probe_values has at least
+        len(probe_keys) words; the first len(probe_keys) are read.  out= / counts_out=: accumulators the call combines into in place and
+        returns (group_count); when counts are asked for, both are given or neither - one flag covers the call - and counts_out implies
+        return_counts."""
+        if probe_values is None:
+            raise ValueError("Index.group_sum: probe_values is required (group_count takes none)")
+        m, sec, vals, counts = self._group("Index.group_sum", probe_keys, probe_values, 0, out, counts_out, return_counts)
+        return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
+
+    def _group_minmax(self, name: str, flag: int, probe_keys, probe_values, out, return_counts, counts_out, signed):
+        if probe_values is None:
+            raise ValueError(f"{name}: probe_values is required (group_count takes none)")
+        if signed is not None and not isinstance(signed, (bool, np.bool_)):
+            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+        probe_values = _from_dlpack_if_device(probe_values)
+        if _is_torch_tensor(probe_values):                       # the sign of the container, as in group_join_min
+            unsigned_in = str(probe_values.dtype) == "torch.uint64"
+        else:
+            probe_values = np.asarray(probe_values)
+            unsigned_in = probe_values.dtype == np.uint64
+        signed = (not unsigned_in) if signed is None else bool(signed)
+        m, sec, vals, counts = self._group(name, probe_keys, probe_values, flag | (ALGO_AGG_SIGNED if signed else 0), out, counts_out, return_counts)
+        return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
+
+    def group_min(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None):
+        """Cheapest offer per product over a batch: values[i] = the minimum of probe_values[j] over the rows j whose key equals build
+        key i, at the key's FIRST build row (group_count: the first-occurrence rule).  signed=None follows the rule of group_join_min: a
+        NumPy uint64 (torch.uint64) value column compares unsigned, everything else signed; True / False force it.  A row without a
+        partner - every further copy of a duplicated key among them - holds the aggregate's identity, 2^64 - 1 (unsigned) or 2^63 - 1
+        (signed); a true minimum equal to it is told apart by the counts.  The outputs are int64 storage of the words.  out= /
+        counts_out= as for group_sum: the call takes the minimum of what `out` holds and the batch's - start a running minimum from a
+        call without out=, or from a buffer filled with the identity - and rows without a partner keep their contents."""
+        return self._group_minmax("Index.group_min", ALGO_AGG_MIN, probe_keys, probe_values, out, return_counts, counts_out, signed)
+
+    def group_max(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None):
+        """Latest event per user over a batch: the max form of group_min.  Identity: 0 (unsigned) or -2^63 (signed)."""
+        return self._group_minmax("Index.group_max", ALGO_AGG_MAX, probe_keys, probe_values, out, return_counts, counts_out, signed)
+
 
 
 def build_index(build_keys, build_values=None, device: Optional[int] = None) -> Index:

@@ -342,6 +342,11 @@ int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, si
 void prepared_free(fj_ctx* c);
 int prepared_retain(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t);
 int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid);
+// FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD: the probe side aggregated onto the prepared side - d_cnt / d_val (prep.nb words each, either
+// may be null) receive the counts / the aggregate `agg` (FJ_GJ_SUM or a min / max form) of pv at every key's FIRST build row; filled
+// first unless `accumulate`; *out_count = probe rows with a partner
+int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_val,
+                   int agg, bool accumulate);
 
 // ---- build-order aggregate joins (fj_group.hip): FJ_ALGO_BUILD_ORDER; d_cnt[i] and / or d_sum[i] (nb words each) for every build row i,
 // either may be null; pv: the probe side's value column (np words, read for d_sum only); agg: the aggregate d_sum receives, FJ_GJ_SUM or

@@ -206,6 +206,9 @@ int fj_join_host(int algo, int bloom, int materialize,
     }
     if (bo) {                                                  // build-order aggregate join: *out_keys nb counts, *out_vals nb sums (minima, maxima); bv = the PROBE values (np words)
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
+        if (algo & FJ_ALGO_REUSE_BUILD)                        // onto a prepared build side, with or without FJ_ALGO_ACCUMULATE (that flag without this one: an unknown algo below)
+            return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD%s is not served here (the internal context is shared by every host-buffer call of the process): call fj_join_device on a context of your own",
+                           (algo & FJ_ALGO_ACCUMULATE) ? " | FJ_ALGO_ACCUMULATE" : "");
         if (many_host || left || anti || rid || full || allc || po)
             return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");

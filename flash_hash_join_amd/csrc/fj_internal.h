@@ -366,6 +366,27 @@ struct FjPrepProbeArgs {
     u32* err;
 };
 hipError_t fj_launch_prep_probe(const FjPrepProbeArgs& a, hipStream_t s);
+// The build-order aggregate join's probe phase against those runs (FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD); work items as above.  The
+// table is loaded from the run with one accumulator per slot at the aggregate's identity; a hit is one LDS atomic; the flush reads the
+// run once more and combines every accumulator that left the identity into out[rows[row of the key]] with ONE global atomic - several
+// items may serve one partition, and out may hold a running aggregate (it holds the identity, or whatever the caller accumulates into,
+// before the launch).  agg: FJ_GJ_* below; every form but FJ_GJ_COUNT reads probe.vals.  total / miss_total (both or neither) count the
+// hits and the misses; a first position >= nb is not written (FJ_ERR_OUTCAP); a foreign run: FJ_ERR_LDS_FULL.
+struct FjPrepGroupArgs {
+    FjChunkSet probe;
+    u32 nparts, nsplit;
+    const uint4* items; const u32* nitems_dev; u32 items_cap;
+    const u64* keys; const u64* rows; const FjPrepRun* runs; u64 nkeys;
+    u64* out; u64 nb;
+    unsigned long long* total; unsigned long long* miss_total;
+    u32* err;
+};
+hipError_t fj_launch_prep_group(const FjPrepGroupArgs& a, int agg, hipStream_t s);
+// ... and against the HBM-table form (the table of fj_launch_gt_build_first, vals = true: a.tkeys / a.tvals / a.flags / a.empty_val):
+// thread i serves probe row a.pk[i]; a hit adds 1 at out_cnt[first position] and / or combines pv[i] into out_val[first position] with
+// the typed global atomic - no accumulator arrays, no flush; a hot key serialises at its output word.  a.total counts the hits
+hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u64* out_cnt, u64* out_val, u64 nb,
+                                   unsigned long long* miss_total, u32* err, hipStream_t s);
 
 // ---- build-order aggregate joins (csrc/fj_group.hip; FJ_ALGO_BUILD_ORDER of include/flashjoin.h) ------------------------------------
 // One output word per build row at the row's own position (the build chunk pool's vals plane; flat arrays: the index).  sum = false:

@@ -688,6 +688,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
+    const bool bo_reuse = bo && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // the aggregate join onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD stays unknown)
+    const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
     const uint64_t* d_rv = nullptr;                         // FJ_ALGO_RETAIN_BUILD: the caller's d_build_vals as given (null: a keys-only side)
     const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
                asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0;
@@ -734,14 +736,18 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // d_out_keys = the counts, d_out_vals = the sums (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX: the minima / maxima), nb words each.
         // The three aggregate flags are modifiers of this one: without it they are an unknown algo below
         algo &= ~(FJ_ALGO_BUILD_ORDER | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED);
+        if (bo_reuse) algo &= ~(FJ_ALGO_REUSE_BUILD | FJ_ALGO_ACCUMULATE);
         if (many || left || anti || rid || full || allc || po)
             return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        // onto the prepared build side (csrc/fj_prepared.hip): no build side in the call - d_build_vals is the PROBE side's value column
+        // here, so it is not looked at; the outputs hold NB words, the rows the side was prepared from (checked on the context)
+        if (bo_reuse && (d_bk || nb)) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD takes no build side (d_build_keys must be NULL and nb 0: the context's prepared side is aggregated onto; d_build_vals is the probe side's value column)");
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if (!materialize) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
-        if (nb && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs an output (the counts d_out_keys, the sums d_out_vals, or both)");
-        if (nb && (amin || amax) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_%s needs d_out_vals (the counts alone are the plain count form of FJ_ALGO_BUILD_ORDER)", amin ? "MIN" : "MAX");
+        if ((nb || bo_reuse) && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs an output (the counts d_out_keys, the sums d_out_vals, or both)");
+        if ((nb || bo_reuse) && (amin || amax) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_%s needs d_out_vals (the counts alone are the plain count form of FJ_ALGO_BUILD_ORDER)", amin ? "MIN" : "MAX");
         if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu build rows (FJ_ALGO_BUILD_ORDER writes every build row)", out_capacity, nb);
         if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
         if (np && d_out_vals && !d_bv) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER with d_out_vals needs d_build_vals (here the probe side's value column, np words)");
@@ -847,6 +853,16 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     if (gb) {                                               // one row per distinct key, never a pending result
         if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,
                      materialize ? (u64*)d_out_vals : nullptr, out_capacity, agg, rid, inv)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (bo_reuse) {                                         // ... onto the build side the context keeps prepared (csrc/fj_prepared.hip)
+        if (!c->prep.valid) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD without a prepared build side on this context (FJ_ALGO_RETAIN_BUILD makes one)");
+        if (hash_top_bits != c->prep.top_bits) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with hash_top_bits %d, the build side was prepared with %d", hash_top_bits, c->prep.top_bits);
+        if (out_capacity < c->prep.nb) return set_err("fj_join_device: output capacity %zu < %zu rows of the prepared build side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD defines every one of them)", out_capacity, c->prep.nb);
+        if (prepared_group(c, d_pk, d_pv, np, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, agg, accum)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

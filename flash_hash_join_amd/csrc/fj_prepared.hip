@@ -275,6 +275,191 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_probe_kernel(FjPrepProbeArgs
     }
 }
 
+struct PgHdr { u32 bad, has_empty, hits, rows; u64 empty_acc, flushed; };       // 32 B: the key slots behind it stay 16-byte aligned
+
+// The build-order aggregate join (csrc/fj_group.hip) onto the prepared side: its probe phase behind the table build of the kernel above,
+// one 8-byte accumulator per slot.  AGG (FJ_GJ_*): FJ_GJ_COUNT adds 1 per hit; every other form takes the probe rows' values
+// (a.probe.vals) - FJ_GJ_SUM adds them, the four min / max forms combine them with gj_combine.  The flush reads the run once more -
+// keys and first positions, coalesced - and combines every accumulator that left the identity into a.out[first position]: a partition
+// may be cut into several items and a.out may hold a running aggregate, so it is always the global atomic (its result is unused).  The
+// run's keys are distinct: the hits ARE the count, nothing like FJ_STAT_DUPS exists here.  They are counted as the one-shot kernel
+// counts P - the count form adds up what it flushes (its accumulators are this call's counts), the forms with values one ballot per
+// row - and the misses are the item's rows minus its hits, the rows one popcount of the round's mask per thread.
+template <int AGG>
+__global__ __launch_bounds__(PP_NT, 1) void fj_prep_group_kernel(FjPrepGroupArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PgHdr* hdr = reinterpret_cast<PgHdr*>(smem);
+    u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(PgHdr));
+    u64* acc = tkeys + PP_TS;
+    constexpr bool VALS = AGG != FJ_GJ_COUNT;                 // the probe side carries values
+    constexpr u64 IDENT = gj_identity<AGG>();
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 item = blockIdx.x;
+    u32 p, s_lo, s_hi;
+    if (a.items) {
+        if (item >= *a.nitems_dev) return;
+        const uint4 it = a.items[item];
+        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
+    } else {
+        const u32 slice = item % a.nsplit;
+        p = item / a.nsplit;
+        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
+    }
+    if (s_lo >= s_hi || p >= a.nparts) return;
+    const FjPrepRun run = a.runs[p];
+    if (run.n > PP_LIMIT + 1 || run.off + run.n > a.nkeys) {  // (uniform) not a run fj_prep_build_kernel wrote: nothing is loaded
+        if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL);
+        return;
+    }
+
+    for (u32 i = tid; i < PP_TS; i += PP_NT) { tkeys[i] = FJ_EMPTY_KEY; acc[i] = IDENT; }
+    if (tid == 0) { hdr->bad = 0; hdr->has_empty = 0; hdr->hits = 0; hdr->rows = 0; hdr->empty_acc = IDENT; hdr->flushed = 0; }
+    __syncthreads();
+
+    // ---- build: the partition's dense run, distinct keys: one coalesced load and one CAS each; the empty marker stays out of band ----
+    for (u32 i = tid; i < (u32)run.n; i += PP_NT) {
+        const u64 key = a.keys[run.off + i];
+        if (key == FJ_EMPTY_KEY) { hdr->has_empty = 1; continue; }
+        u32 pos = FJ_HW2(key) & (PP_TS - 1);
+        bool placed = false;
+        for (u32 step = 0; step < PP_TS; ++step) {
+            const u64 old = atomicCAS((unsigned long long*)&tkeys[pos], (unsigned long long)FJ_EMPTY_KEY, (unsigned long long)key);
+            if (old == FJ_EMPTY_KEY) { placed = true; break; }
+            if (old == key) break;                           // (a key twice in a run: not a prepared side)
+            pos = (pos + 1) & (PP_TS - 1);
+        }
+        if (!placed) hdr->bad = 1;
+    }
+    __syncthreads();
+    if (hdr->bad) { if (tid == 0) atomicOr(a.err, FJ_ERR_LDS_FULL); return; }      // (an internal error on this path: there is no fallback)
+    const bool has_empty = hdr->has_empty != 0;
+
+    // ---- probe: rounds of PP_NT * PP_KPT rows; the next round's loads are requested before this round's lookups.  A hit is one LDS
+    // atomic on its slot's accumulator and nothing else: no global traffic ----
+    u64 k[PP_KPT], pv[VALS ? PP_KPT : 1];
+    u32 okm = 0, nh = 0, nrows = 0;                          // nh: wave-uniform count of this wave's hits (VALS); nrows: this thread's rows
+    auto load_round = [&](u32 pc, u64 (&kk)[PP_KPT], u64 (&vv)[VALS ? PP_KPT : 1], u32& ok) {
+        ok = 0;
+#pragma unroll
+        for (u32 u = 0; u < PP_KPT; ++u) {
+            const u32 c = pc + u * (PP_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+            kk[u] = 0; if (VALS) vv[VALS ? u : 0] = 0;
+            if (c >= s_hi) continue;
+            const u32 e = gj_entry(a.probe, c);
+            if (off >= FJ_LIST_CNT(e)) continue;
+            const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+            kk[u] = a.probe.keys[src];
+            if (VALS) vv[VALS ? u : 0] = a.probe.vals[src];
+            ok |= 1u << u;
+        }
+    };
+    load_round(s_lo, k, pv, okm);
+    for (u32 pc = s_lo; pc < s_hi; pc += PP_ROUND_CHUNKS) {
+        u64 kn[PP_KPT], pvn[VALS ? PP_KPT : 1];
+        u32 okn = 0;
+        if (pc + PP_ROUND_CHUNKS < s_hi) load_round(pc + PP_ROUND_CHUNKS, kn, pvn, okn);
+        nrows += (u32)__popc(okm);
+#pragma unroll
+        for (u32 u = 0; u < PP_KPT; ++u) {
+            bool h = false;
+            if ((okm >> u) & 1u) {
+                const u64 key = a.probe.list ? k[u] : fj_key_mix(k[u]);           // chunk pools hold mixed keys, flat arrays raw ones
+                const unsigned long long add = VALS ? (unsigned long long)pv[VALS ? u : 0] : 1ull;
+                if (key == FJ_EMPTY_KEY) {
+                    h = has_empty;
+                    if (h) gj_combine<AGG>(&hdr->empty_acc, add);
+                } else {
+                    u32 pos = FJ_HW2(key) & (PP_TS - 1);
+                    for (;;) {                               // the run left >= 1/16 of the slots empty: always terminates
+                        const u64 t = tkeys[pos];
+                        if (t == key) { h = true; gj_combine<AGG>(&acc[pos], add); break; }
+                        if (t == FJ_EMPTY_KEY) break;
+                        pos = (pos + 1) & (PP_TS - 1);
+                    }
+                }
+            }
+            if (VALS) nh += (u32)__popcll(__ballot(h));
+        }
+#pragma unroll
+        for (u32 u = 0; u < PP_KPT; ++u) { k[u] = kn[u]; if (VALS) pv[VALS ? u : 0] = pvn[VALS ? u : 0]; }
+        okm = okn;
+    }
+    const u32 wrows = (u32)gj_wave_sum64(nrows);
+    if (lane == 0) { if (VALS && nh) atomicAdd(&hdr->hits, nh); if (wrows) atomicAdd(&hdr->rows, wrows); }
+    __syncthreads();
+
+    // ---- flush: the run once more, keys and first positions; a slot that still holds the identity has nothing to say (count, sum: 0
+    // adds nothing; min / max: the identity changes no word) ----
+    const u64 empty_acc = hdr->empty_acc;
+    u64 flushed = 0;
+    for (u32 i = tid; i < (u32)run.n; i += PP_NT) {
+        const u64 key = a.keys[run.off + i];
+        const u64 o = a.rows[run.off + i];
+        u64 v = empty_acc;
+        if (key != FJ_EMPTY_KEY) {
+            u32 pos = FJ_HW2(key) & (PP_TS - 1);
+            while (tkeys[pos] != key) pos = (pos + 1) & (PP_TS - 1);              // (the build phase placed it)
+            v = acc[pos];
+        }
+        if (v == IDENT) continue;
+        if (!VALS) flushed += v;
+        if (o < a.nb) gj_combine<AGG>(&a.out[o], v);                              // (always: first positions are 0 .. nb - 1)
+        else atomicOr(a.err, FJ_ERR_OUTCAP);
+    }
+    if (!a.total) return;                                    // (uniform: the other launch of a two-output call has them)
+    if (!VALS) {
+        flushed = gj_wave_sum64(flushed);
+        if (lane == 0 && flushed) atomicAdd((unsigned long long*)&hdr->flushed, (unsigned long long)flushed);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const u64 hits = VALS ? (u64)hdr->hits : hdr->flushed, rows = hdr->rows;
+        if (hits) atomicAdd(a.total, (unsigned long long)hits);
+        if (rows > hits) atomicAdd(a.miss_total, (unsigned long long)(rows - hits));
+    }
+}
+
+// the HBM-table form: thread i serves probe row i against the owned table (raw keys, the raw empty key out of band: its flag and first
+// position in a.flags / a.empty_val); a hit goes straight to the output words of the key's first build row with the typed global
+// atomic - no accumulators, no flush.  AGG is out_val's aggregate (FJ_GJ_SUM for the counts alone).  Global atomics serialise on a hot key
+template <int AGG>
+__global__ __launch_bounds__(1024) void fj_prep_gt_group_kernel(FjGtArgs a, const u64* __restrict__ pv, u64* out_cnt, u64* out_val, u64 nb,
+                                                                unsigned long long* miss_total, u32* err) {
+    __shared__ u32 s_hits, s_misses;
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) { s_hits = 0; s_misses = 0; }
+    __syncthreads();
+    const bool has_empty = a.flags[0] != 0;
+    const u64 np = a.np;
+    u32 nh = 0, nm = 0;                                                           // (wave-uniform)
+    for (u64 base = (u64)blockIdx.x * 1024; base < np; base += (u64)gridDim.x * 1024) {     // (uniform per workgroup)
+        const u64 i = base + tid;
+        const bool ok = i < np;
+        bool h = false;
+        if (ok) {
+            const u64 key = a.pk[i];
+            u64 where = 0;
+            if (key == FJ_EMPTY_KEY) h = has_empty;
+            else h = gj_gt_find(a.tkeys, a.cap_mask, key, where);
+            if (h) {
+                const u64 o = key == FJ_EMPTY_KEY ? *a.empty_val : a.tvals[where];
+                if (o < nb) {                                                     // (always: first positions are 0 .. nb - 1)
+                    if (out_cnt) atomicAdd((unsigned long long*)&out_cnt[o], 1ull);
+                    if (out_val) gj_combine<AGG>(&out_val[o], pv[i]);
+                } else atomicOr(err, FJ_ERR_OUTCAP);
+            }
+        }
+        nh += (u32)__popcll(__ballot(h)); nm += (u32)__popcll(__ballot(ok && !h));
+    }
+    if (lane == 0) { if (nh) atomicAdd(&s_hits, nh); if (nm) atomicAdd(&s_misses, nm); }
+    __syncthreads();
+    if (tid == 0) {
+        if (s_hits) atomicAdd(a.total, (unsigned long long)s_hits);
+        if (s_misses) atomicAdd(miss_total, (unsigned long long)s_misses);
+    }
+}
+
 }  // namespace
 
 hipError_t fj_launch_prep_build(const FjPrepBuildArgs& a, hipStream_t s) {
@@ -297,6 +482,37 @@ hipError_t fj_launch_prep_probe(const FjPrepProbeArgs& a, hipStream_t s) {
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(PP_NT), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_prep_group(const FjPrepGroupArgs& a, int agg, hipStream_t s) {
+    const u32 grid = a.items ? a.items_cap : a.nparts * a.nsplit;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S) return hipErrorInvalidValue;
+    if (!a.err || !a.runs || !a.keys || !a.rows || !a.out || (a.total && !a.miss_total)) return hipErrorInvalidValue;
+    if (agg != FJ_GJ_COUNT && !a.probe.vals) return hipErrorInvalidValue;         // the probe side carries the values
+    const u32 lds = (u32)sizeof(PgHdr) + PP_TS * 16u;
+    void (*kern)(FjPrepGroupArgs) =
+        agg == FJ_GJ_COUNT ? fj_prep_group_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_prep_group_kernel<FJ_GJ_SUM> :
+        agg == FJ_GJ_MIN_U ? fj_prep_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_group_kernel<FJ_GJ_MIN_S> :
+        agg == FJ_GJ_MAX_U ? fj_prep_group_kernel<FJ_GJ_MAX_U> : fj_prep_group_kernel<FJ_GJ_MAX_S>;
+    hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
+    if (e != hipSuccess) return e;
+    if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(PP_NT), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u64* out_cnt, u64* out_val, u64 nb,
+                                   unsigned long long* miss_total, u32* err, hipStream_t s) {
+    if (a.np == 0) return hipSuccess;
+    if (!a.total || !miss_total || !err || !a.tkeys || !a.tvals || !a.flags || !a.empty_val || !a.pk) return hipErrorInvalidValue;
+    if ((!out_cnt && !out_val) || (out_val && !pv)) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || (out_val && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
+    const u64 rounds = (a.np + 1023) / 1024;
+    void (*kern)(FjGtArgs, const u64*, u64*, u64*, u64, unsigned long long*, u32*) =
+        agg == FJ_GJ_MIN_U ? fj_prep_gt_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_gt_group_kernel<FJ_GJ_MIN_S> :
+        agg == FJ_GJ_MAX_U ? fj_prep_gt_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_gt_group_kernel<FJ_GJ_MAX_S> :
+        fj_prep_gt_group_kernel<FJ_GJ_SUM>;                                       // (the counts alone: out_val == nullptr)
+    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, out_cnt, out_val, nb, miss_total, err);
     return hipGetLastError();
 }
 
@@ -473,6 +689,94 @@ int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timing
     }
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (hits + misses != np) return set_err("internal error: probe-order join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
+    *out_count = hits;
+    return 0;
+}
+
+// FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD (fj_join_device has checked the arguments, the prepared side and the capacity): the probe
+// side aggregated onto the prepared side.  d_cnt / d_val: P.nb words each, either may be null; agg: what d_val receives (FJ_GJ_SUM or a
+// min / max form); pv: the probe side's value column, read for d_val only.  A key's aggregate lands at its FIRST build row: the runs (the
+// HBM table) hold first positions only, so every further copy of a duplicated key keeps what the fill - or, accumulating, the caller -
+// left there.  Unless `accumulate`, the outputs are filled with the aggregate's identity on the stream first; with it they are combined
+// into as they are.  Same shape as prepared_probe; the prepared planes are read and never written.  *out_count = probe rows with a partner
+int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream_t s, fj_timings* t, u64* out_count, u64* d_cnt, u64* d_val,
+                   int agg, bool accumulate) {
+    const Prepared& P = c->prep;
+    const size_t nb = P.nb;
+    *out_count = 0;
+    t->path = P.path; t->passes = P.form == Prepared::LDS ? P.plan.npass : 0; t->radix_bits = P.form == Prepared::LDS ? P.plan.bits : 0;
+    t->partitions = P.form == Prepared::LDS ? P.nparts : 1;
+    t->build_phase_ms = 0;
+    if (P.form == Prepared::EMPTY || nb == 0) return 0;      // the outputs have zero words
+    if (np == 0 && accumulate) return 0;                     // nothing to combine: nothing is touched
+    auto fill = [&]() -> int {
+        if (accumulate) return 0;
+        if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
+        if (d_val) HIPCHK(fj_launch_group_fill(d_val, nb, agg, s));
+        return 0;
+    };
+    if (np == 0) {                                           // no build row has a partner
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        if (fill()) return 1;
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        HIPCHK(hipStreamSynchronize(s));
+        t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        return 0;
+    }
+    if (P.form == Prepared::HBM) {
+        FjGtArgs a{};
+        a.tkeys = P.keys; a.tvals = P.rows; a.cap_mask = P.cap_mask; a.flags = (u32*)P.aux; a.empty_val = (u64*)P.aux + 1;
+        a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+        if (fill()) return 1;
+        HIPCHK(fj_launch_prep_gt_group(a, d_val ? agg : FJ_GJ_SUM, pv, d_cnt, d_val, nb, &c->d_sc->expected, &c->d_sc->err, s));
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        if (read_scalars(c, s)) return 1;
+        t->join_ms = t->probe_phase_ms = t->total_ms = ev_ms(c, E_START, E_JOIN);
+    } else {
+        begin_plan(c);
+        HIPCHK(hipEventRecord(c->ev[E_START], s));
+        if (clear_plan_scalars(c, s)) return 1;              // (total = the hits, expected = the misses)
+        HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+        FjPrepGroupArgs ga{};
+        PassIter pit;
+        int evc = 0;
+        pass_init(pit, 1, d_val != nullptr, np, P.plan, P.top_bits);             // the counts alone: the keys-only pass
+        pit.want_items = true;
+        if (run_passes(c, pit, pk, d_val ? pv : nullptr, s, &ga.probe, &evc)) return 1;
+        HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+        ga.nparts = P.nparts;
+        if (ga.probe.list) {
+            if (ga.probe.nb != P.nparts) return set_err("internal error: the probe side has %u partitions, the prepared build side %u", ga.probe.nb, P.nparts);
+            ga.items = pit.tiles; ga.nitems_dev = pit.ntiles; ga.items_cap = pit.items_cap; ga.nsplit = 1;
+        } else {                                             // zero-pass plan: slices of the flat probe side
+            if (P.nparts != 1) return set_err("internal error: a flat probe side against %u prepared partitions", P.nparts);
+            const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
+            ga.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32));
+        }
+        ga.keys = P.keys; ga.rows = P.rows; ga.runs = (const FjPrepRun*)P.aux; ga.nkeys = P.g; ga.nb = nb;
+        ga.err = &c->d_sc->err;
+        if (fill()) return 1;
+        if (d_cnt) {                                         // both outputs: the passes ran once, the kernel runs once per accumulator
+            ga.out = d_cnt; ga.total = &c->d_sc->total; ga.miss_total = &c->d_sc->expected;
+            HIPCHK(fj_launch_prep_group(ga, FJ_GJ_COUNT, s));
+        }
+        if (d_val) {
+            ga.out = d_val; ga.total = d_cnt ? nullptr : &c->d_sc->total; ga.miss_total = d_cnt ? nullptr : &c->d_sc->expected;   // (the count launch has them)
+            HIPCHK(fj_launch_prep_group(ga, agg, s));
+        }
+        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+        if (read_scalars(c, s)) return 1;
+        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        end_plan(c);
+        plan_timings(c, P.plan, P.nparts, evc, t);
+        t->build_phase_ms = 0;                               // (nothing touched the build relation: its passes ran when it was prepared)
+        if (c->h_sc->err & FJ_ERR_LDS_FULL) return set_err("internal error: a run of the prepared build side does not fit the LDS table");
+    }
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a first-occurrence position lies beyond the prepared build side");
+    const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
+    if (hits + misses != np) return set_err("internal error: aggregate join onto the prepared side placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
     *out_count = hits;
     return 0;
 }

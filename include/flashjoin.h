@@ -250,6 +250,34 @@ extern "C" {
  * context of your own. */
 #define FJ_ALGO_RETAIN_BUILD 0x400000
 #define FJ_ALGO_REUSE_BUILD  0x800000
+/* EXTENSION (csrc/fj_prepared.hip): FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD, plus a base value 0..2 and optionally FJ_ALGO_AGG_MIN /
+ * FJ_ALGO_AGG_MAX / FJ_ALGO_AGG_SIGNED, through fj_join_device: the build-order aggregate join of the probe side onto the context's
+ * PREPARED build side - orders per customer, revenue per product, latest event per user over a fact column that arrives in morsels,
+ * without the build side's passes in every call.  With NB = the number of rows the side was prepared from:
+ *   d_build_keys must be NULL and nb 0 (the context's prepared side is aggregated onto).
+ *   d_build_vals the PROBE side's value column, np words, exactly as in the one-shot FJ_ALGO_BUILD_ORDER call.  NULL: counts only.
+ *   d_out_keys   optional; 8-byte aligned, NB words: the counts.          d_out_vals  optional; NB words: the sums / minima / maxima.
+ *   out_capacity >= NB.
+ * FIRST-OCCURRENCE RULE: the prepared side is deduplicated to first occurrences, so the aggregate of a key lands AT THE POSITION OF
+ * THE KEY'S FIRST BUILD ROW; every further copy of a duplicated build key holds 0 (count, sum) or the aggregate's identity (min /
+ * max).  This is the rule of the prepared side's other forms (FJ_ALGO_ROW_IDS names the first row) and DELIBERATELY DIFFERS from the
+ * one-shot FJ_ALGO_BUILD_ORDER call, where every copy carries the aggregate.  On distinct build keys the two calls agree bit for bit.
+ * *out_count = the probe rows of THIS call that have a partner.  Every requested word below NB is defined by the call, nothing at or
+ * beyond NB is touched; never a pending result.  fj_timings: build_phase_ms = 0; passes, radix_bits, partitions and path are the
+ * prepared side's.  A side prepared without d_build_vals serves every form (no build value is read); a side prepared from nb == 0
+ * writes nothing and returns 0.  On the HBM-table form every hit is a global atomic at the output word: a hot key serialises there.
+ *
+ * FJ_ALGO_ACCUMULATE: a modifier of that combination ONLY (anywhere else an unknown algo).  Without it the library fills the outputs
+ * first, as the one-shot call does (zeros; the identity for min / max).  With it the call does NOT fill: it combines into whatever the
+ * outputs hold - add for counts and sums, the typed min / max otherwise - so N morsels make ONE running aggregate in N calls on the
+ * same buffers.  The flag applies to every output of the call; np == 0 touches nothing.
+ *
+ * Refused up front, before any device work: FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD (an unknown algo); FJ_ALGO_ACCUMULATE without
+ * both FJ_ALGO_BUILD_ORDER and FJ_ALGO_REUSE_BUILD (an unknown algo); a build side (non-NULL d_build_keys or nb != 0 - d_build_vals is
+ * the probe value column here and is no build side); everything FJ_ALGO_BUILD_ORDER refuses.  Refused on the context, which stays
+ * usable: no prepared side, another hash_top_bits than the prepared side's, out_capacity < NB.  fj_join_host refuses the combination
+ * with and without FJ_ALGO_ACCUMULATE: use fj_join_device on a context of your own. */
+#define FJ_ALGO_ACCUMULATE 0x1000000
 
 typedef struct fj_ctx fj_ctx;
 
