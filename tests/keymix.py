@@ -74,6 +74,84 @@ def special_raw_keys(radix_bits):
     return names, raw
 
 
+# ---- keys crafted to collide in a partition's table -----------------------------------------------------------------------------
+# The mixer is a bijection, so any (hash word 1, hash word 2) pair names exactly one raw key.  A partition of a plan of radix_bits
+# bits is the top radix_bits bits of hash word 1; every table takes its slots, groups, buckets and tags from hash word 2 alone
+# (csrc/fj_common.h FJ_HW2).  craft() fixes both and lets the keys differ in the rest of hash word 1 only - bits no table looks at.
+def _w2_array(w2, n):
+    w = np.asarray(w2, dtype=np.uint64)
+    if w.ndim == 0:
+        w = np.full(n, w, dtype=np.uint64)
+    if w.shape != (n,) or np.any(w > _M32):
+        raise ValueError("w2: a 32-bit scalar or an array of n of them")
+    return w
+
+
+def craft_mixed(radix_bits, partition, w2, n, seed=0, low_bits=None, allow_special=False, skip=0):
+    """The mixed words of craft(): n distinct words (partition << (32 - radix_bits) | low) << 32 | w2.  low runs through
+    (start + i * odd) mod 2^low_bits for i = skip .. (start and odd drawn from seed): distinct as long as skip + n <= 2^low_bits, and
+    for one seed the ranges [0, n) and [n, ...) never meet - which is how ghosts() stays clear of craft().  low_bits defaults to all
+    32 - radix_bits remaining bits; a smaller value keeps the bits right below the partition bits at zero (keys that further radix
+    bits cannot tell apart).  The empty marker and the wide filler are left out unless allow_special (the sequence's next word stands in)."""
+    if not 0 <= radix_bits <= 31 or not 0 <= partition < (1 << radix_bits):
+        raise ValueError("partition must be one of the plan's 2^radix_bits")
+    rest = 32 - radix_bits
+    low_bits = rest if low_bits is None else low_bits
+    if not 1 <= low_bits <= rest:
+        raise ValueError("low_bits must be 1 .. 32 - radix_bits")
+    w = _w2_array(w2, n)
+    rng = np.random.default_rng([seed, radix_bits, partition, low_bits])
+    start, odd = int(rng.integers(0, 1 << low_bits)), int(rng.integers(0, 1 << low_bits)) | 1
+    if skip + n > (1 << low_bits):
+        raise ValueError("not that many distinct keys in 2^low_bits")
+    top, mask = np.uint64(partition) << np.uint64(rest), np.uint64((1 << low_bits) - 1)
+    word = lambda idx: (((top | ((np.uint64(start) + idx * np.uint64(odd)) & mask)) << np.uint64(32)) | w)
+    idx = np.arange(skip, skip + n, dtype=np.uint64)
+    h, spare = word(idx), skip + n
+    while not allow_special:                                              # a special word gives its place to the sequence's next one
+        bad = np.flatnonzero((h == np.uint64(EMPTY_MIXED)) | (h == np.uint64(FILLER_MIXED)))
+        if bad.size == 0:
+            break
+        if spare + bad.size > (1 << low_bits):
+            raise ValueError("not that many distinct keys in 2^low_bits")
+        idx[bad] = np.arange(spare, spare + bad.size, dtype=np.uint64)
+        spare += bad.size
+        h = word(idx)
+    return h
+
+
+def craft(radix_bits, partition, w2, n, seed=0, low_bits=None, allow_special=False):
+    """n distinct raw uint64 keys whose mixed form has the top radix_bits bits of hash word 1 equal to partition and hash word 2
+    exactly w2 (a scalar, or an array of n words: key i gets w2[i]).  They differ from each other in the remaining bits of hash
+    word 1 only (the lowest low_bits of them)."""
+    return unmix(craft_mixed(radix_bits, partition, w2, n, seed, low_bits, allow_special))
+
+
+def ghosts(radix_bits, partition, w2, n, not_in, seed=0, low_bits=None):
+    """n more keys of the same partition and w2 as craft(..., seed, low_bits) that are not among not_in (raw keys): what a table
+    must report as a miss after walking everything the crafted keys put in its way."""
+    not_in = np.asarray(not_in, dtype=np.uint64)
+    g = unmix(craft_mixed(radix_bits, partition, w2, n, seed, low_bits, skip=not_in.size + n))
+    if np.isin(g, not_in).any() or np.unique(g).size != n:
+        raise ValueError("ghosts: the sequence met not_in (another seed, or more low_bits)")
+    return g
+
+
+def twins(keys, radix_bits, partition):
+    """The keys whose mixed form equals that of `keys` except for the top radix_bits bits of hash word 1, which become `partition`:
+    same slot, same tag, same remaining bits - in another partition's table."""
+    if not 1 <= radix_bits <= 31 or not 0 <= partition < (1 << radix_bits):
+        raise ValueError("partition must be one of the plan's 2^radix_bits")
+    h = mix(keys)
+    keep = np.uint64((1 << (64 - radix_bits)) - 1)
+    return unmix((h & keep) | (np.uint64(partition) << np.uint64(64 - radix_bits)))
+
+
+def partition_of(k, radix_bits):
+    """the partition of raw keys under a plan of radix_bits bits (0 bits: partition 0)"""
+    return (mix(k) >> np.uint64(64 - radix_bits)).astype(np.int64) if radix_bits else np.zeros(np.asarray(k).shape, dtype=np.int64)
+
+
 def hash_w1(k):
     """hash word 1 of raw keys (csrc/fj_common.h fj_hash_w1) as uint32"""
     return (mix(k) >> np.uint64(32)).astype(np.uint32)
