@@ -147,9 +147,51 @@ def twins(keys, radix_bits, partition):
     return unmix((h & keep) | (np.uint64(partition) << np.uint64(64 - radix_bits)))
 
 
-def partition_of(k, radix_bits):
-    """the partition of raw keys under a plan of radix_bits bits (0 bits: partition 0)"""
-    return (mix(k) >> np.uint64(64 - radix_bits)).astype(np.int64) if radix_bits else np.zeros(np.asarray(k).shape, dtype=np.int64)
+def partition_of(k, radix_bits, top_bits=64):
+    """the partition of raw keys under a plan of radix_bits bits (0 bits: partition 0): the radix_bits bits of the mixed key below
+    its 64 - top_bits owner bits (hash_top_bits of the C ABI; 64: no owner bits, the partition is the top of hash word 1)"""
+    if not radix_bits:
+        return np.zeros(np.asarray(k).shape, dtype=np.int64)
+    return ((mix(k) >> np.uint64(top_bits - radix_bits)) & np.uint64((1 << radix_bits) - 1)).astype(np.int64)
+
+
+# ---- one crafted key per row ---------------------------------------------------------------------------------------------------
+def craft_rows(bits, bucket_of_row, top_bits=64, distinct=True, seed=0, keys_per_bucket=1):
+    """One raw key per row whose radix bucket under a plan of `bits` bits is bucket_of_row[i]: the `bits` bits of hash word 1 below
+    the 64 - top_bits owner bits (partition_of(keys, bits, top_bits) gives bucket_of_row back).  The owner bits (top_bits = 48: 16 of
+    them) and the bits of hash word 1 below the bucket are pseudo-random per key; hash word 2 runs through an odd multiple of the
+    key's number and never is 0xFFFFFFFF, so that neither the empty marker nor the wide filler (both end in that word) is made.
+    distinct=True: the keys are pairwise distinct (key number = row).  distinct=False: the j-th row of a bucket (in row order) gets
+    that bucket's key number j % keys_per_bucket - keys_per_bucket distinct keys per bucket, distinct across buckets."""
+    b = np.asarray(bucket_of_row, dtype=np.int64)
+    n, owner_bits = b.size, 64 - top_bits
+    low_bits = 32 - owner_bits - bits
+    if b.ndim != 1 or not 1 <= bits <= 31 or not 0 <= owner_bits <= 31 or low_bits < 0:
+        raise ValueError("craft_rows: bits and 64 - top_bits must fit into hash word 1")
+    if n and (b.min() < 0 or b.max() >= (1 << bits)):
+        raise ValueError("craft_rows: a bucket outside the plan's 2^bits")
+    if distinct:
+        kid = np.arange(n, dtype=np.uint64)
+    else:
+        if keys_per_bucket < 1:
+            raise ValueError("craft_rows: keys_per_bucket must be >= 1")
+        order = np.argsort(b, kind="stable")
+        sb = b[order]
+        first = np.flatnonzero(np.r_[True, sb[1:] != sb[:-1]]) if n else np.zeros(0, dtype=np.int64)
+        occ = np.empty(n, dtype=np.int64)
+        occ[order] = np.arange(n) - np.repeat(first, np.diff(np.r_[first, n]))
+        kid = (b * keys_per_bucket + occ % keys_per_bucket).astype(np.uint64)
+    if kid.size and int(kid.max()) >= 2**32 - 1:
+        raise ValueError("craft_rows: not that many distinct words in hash word 2")
+    odd = np.uint64((0x9E3779B1 + 2 * seed) | 1)
+    w2 = (_M32 + odd * (kid + np.uint64(1))) & _M32                       # a bijection of the key number; 0xFFFFFFFF only at number 2^32 - 1
+    r = _fmix32((kid * np.uint64(0x85EBCA77) + np.uint64(seed * 0x9E3779B1 + 0x1234567)) & _M32)
+    r2 = _fmix32(r ^ np.uint64(0x5BD1E995))
+    low = r & np.uint64((1 << low_bits) - 1)
+    owner = r2 & np.uint64((1 << owner_bits) - 1)
+    w1 = (owner << np.uint64(32 - owner_bits)) | (b.astype(np.uint64) << np.uint64(low_bits)) | low if owner_bits \
+        else (b.astype(np.uint64) << np.uint64(low_bits)) | low
+    return unmix((w1 << np.uint64(32)) | w2)
 
 
 def hash_w1(k):

@@ -497,8 +497,8 @@ def test_device_tensor_inputs_and_device_generators(fj, oracle):
                                                 (2_500_000, 18, True), (1_000_000, 20, False), (1_500_000, 9, False), (800_000, 9, True)])
 def test_partition_pass_in_isolation(fj, n, bits, with_vals):
     """fj_debug_partition: the chunk lists are a permutation of the input and every row sits in the
-    bucket named by the top `bits` bits of its hash (1 pass for bits <= 8, 2 passes up to 18 bits -- 512-bucket passes
-    above 16 --, 3 passes above)."""
+    bucket named by the top `bits` bits of its hash (1 pass for bits <= 9 -- a 512-bucket pass at exactly 9 --, 2 passes up to
+    18 bits -- 512-bucket passes above 16 --, 3 passes above)."""
     import ctypes
     import torch
     from flash_hash_join_amd import _lib, api
