@@ -48,6 +48,7 @@ ALGO_INVERSE = 0x100000           # FJ_ALGO_INVERSE: modifier of ALGO_GROUP_BY -
 ALGO_RETAIN_BUILD = 0x400000      # FJ_ALGO_RETAIN_BUILD: modifier of ALGO_PROBE_ORDER - the call also leaves its build side prepared on the context (extension)
 ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_ORDER - no build side in the call: the context's prepared one is probed (extension)
 ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_ORDER | ALGO_REUSE_BUILD - the outputs are combined into as they are instead of filled first (extension)
+ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_ORDER / ALGO_GROUP_BY - the value column and the values output hold IEEE-754 float64 words: float sum, or float min / max with AGG_MIN / AGG_MAX (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -73,6 +74,49 @@ def _as_u64_host(a: Any, name: str) -> np.ndarray:
     if arr.ctypes.data % 16:
         arr = np.require(arr.copy(), requirements=["ALIGNED", "C"])
     return arr
+
+
+_FLOAT64_HINT = "; a floating-point column is aggregated as numbers with float64=True"
+
+
+def _float_words(name: str, what: str, values: Any, signed: Any = None):
+    """float64=True: a floating-point value column as the 8-byte words the native library reads (FJ_ALGO_AGG_FLOAT), in the container
+    it came in.  NumPy float64 and torch.float64 are reinterpreted in place (a view, no copy); narrower floats are widened first, which
+    is exact.  Anything that is not floating point is refused: its words would be read as doubles."""
+    if signed is not None:
+        raise TypeError(f"{name}: signed must be None with float64=True (a float64 carries its own sign), got {signed!r}")
+    values = _from_dlpack_if_device(values)
+    if _is_torch_tensor(values):
+        import torch
+        if not values.dtype.is_floating_point:
+            raise TypeError(f"{name}: float64=True needs floating-point {what}, got {values.dtype}")
+        if values.dtype != torch.float64:
+            values = values.double()
+        return values.view(torch.int64)
+    values = np.asarray(values)
+    if values.dtype.kind != "f" or values.dtype.itemsize > 8:
+        raise TypeError(f"{name}: float64=True needs floating-point {what} (float64, float32 or float16), got dtype {values.dtype}")
+    if values.dtype != np.float64:
+        values = values.astype(np.float64)
+    return values.view(np.uint64)
+
+
+def _as_float64_words(buf: Any):
+    """the int64 words of a float64 buffer (a view), where it lives"""
+    if _is_torch_tensor(buf):
+        import torch
+        return buf.view(torch.int64)
+    return buf.view(np.int64)
+
+
+def _as_float64(words: Any):
+    """the float64 numbers an aggregate's int64 / uint64 words hold (a view), where they live"""
+    if words is None:
+        return None
+    if _is_torch_tensor(words):
+        import torch
+        return words.view(torch.float64)
+    return words.view(np.float64)
 
 
 def context(device: int) -> int:
@@ -779,8 +823,19 @@ class Index:
         return m, sec, idx
 
     # ---- build-order aggregates onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD [| FJ_ALGO_ACCUMULATE]) ----
-    def _check_out(self, name: str, what: str, buf, on_device: bool):
-        """a caller's accumulator: of the kind of probe_keys, int64 storage, num_rows elements, contiguous (before any native call)"""
+    def _check_out(self, name: str, what: str, buf, on_device: bool, float64: bool = False):
+        """a caller's accumulator: of the kind of probe_keys, int64 storage, num_rows elements, contiguous (before any native call).
+        float64: a float aggregate's accumulator instead - float64, and everything about its kind is a TypeError that says so"""
+        if float64:
+            if on_device:
+                import torch
+                if not _is_torch_tensor(buf) or buf.dtype != torch.float64:
+                    raise TypeError(f"{name}: with float64=True {what} must be a float64 torch tensor on the index's device, like probe_keys "
+                                    f"(got {buf.dtype if _is_torch_tensor(buf) else type(buf).__name__})")
+            elif not isinstance(buf, np.ndarray) or buf.dtype != np.float64 or not buf.flags.c_contiguous or not buf.flags.writeable:
+                raise TypeError(f"{name}: with float64=True {what} must be a writable C-contiguous float64 NumPy array, like probe_keys "
+                                f"(got {buf.dtype if isinstance(buf, np.ndarray) else type(buf).__name__})")
+            buf = _as_float64_words(buf)                         # (the rest: the checks of the integer forms)
         if on_device:
             if not _is_torch_tensor(buf):
                 raise TypeError(f"{name}: {what} must be a torch tensor on the index's device, like probe_keys (got {type(buf).__name__})")
@@ -803,9 +858,10 @@ class Index:
             if not buf.flags.c_contiguous or not buf.flags.writeable:
                 raise ValueError(f"{name}: {what} must be a writable C-contiguous array (it is combined into in place)")
 
-    def _group(self, name: str, probe_keys, probe_values, agg: int, out, counts_out, want_counts: bool):
+    def _group(self, name: str, probe_keys, probe_values, agg: int, out, counts_out, want_counts: bool, float64: bool = False):
         """(m, seconds, values or None, counts or None): num_rows int64 words each, where probe_keys live.  probe_values None: the
-        count form (`out` is then the counts).  out / counts_out given: ALGO_ACCUMULATE, combined into in place and returned"""
+        count form (`out` is then the counts).  out / counts_out given: ALGO_ACCUMULATE, combined into in place and returned.
+        float64 (agg carries ALGO_AGG_FLOAT, probe_values are the words of _float_words): the values, and `out`, are float64"""
         global _last
         L = _lib.load()
         want_vals = probe_values is not None
@@ -819,7 +875,10 @@ class Index:
         accumulate = out is not None or counts_out is not None
         for what, buf in (("out" if want_vals else "out (the counts)", out if want_vals else counts_out), ("counts_out", counts_out if want_vals else None)):
             if buf is not None:
-                self._check_out(name, what, buf, on_device)
+                self._check_out(name, what, buf, on_device, float64 and want_vals and what == "out")
+        out_given = out
+        if float64 and out is not None:                          # the words of the caller's float64 accumulator: a view, combined into in place
+            out = _as_float64_words(out)
         algo = ALGO_BUILD_ORDER | ALGO_REUSE_BUILD | agg | (ALGO_ACCUMULATE if accumulate else 0)
         n_b = self.num_rows
         cnt, t = ctypes.c_uint64(0), FjTimings()
@@ -847,6 +906,8 @@ class Index:
                 check(L.fj_join_device(self._ctx, algo, 0, 1, None, pv.data_ptr() if want_vals and n_p else None, 0, pk.data_ptr() if n_p else None, n_p,
                                        stream, 64, ctypes.byref(cnt), ptr(oc), ptr(ov), n_b, ctypes.byref(t)))
             _last = t
+            if float64:
+                ov = out_given if out_given is not None else _as_float64(ov)
             return int(cnt.value), t.total_ms * 1e-3, ov, oc
         if _is_torch_tensor(pk):
             pk = pk.numpy()
@@ -877,6 +938,8 @@ class Index:
                     if h is not None and n_b:
                         check(L.fj_memcpy_d2h(h.ctypes.data, d, n_b * 8))
         _last = t
+        if float64:
+            vals = out_given if out_given is not None else _as_float64(vals)
         return int(cnt.value), t.total_ms * 1e-3, vals, counts
 
     def group_count(self, probe_keys, out=None):
@@ -892,21 +955,35 @@ class Index:
         m, sec, _, counts = self._group("Index.group_count", probe_keys, None, 0, out, None, True)
         return m, sec, counts
 
-    def group_sum(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None):
+    def group_sum(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, float64: bool = False):
         """Revenue per product over a batch: (m, seconds, sums) or, with return_counts / counts_out, (m, seconds, sums, counts).  sums[i] =
         the sum modulo 2^64 of probe_values[j] over the rows j of probe_keys whose key equals build key i (int64 storage of the uint64
         words), at the key's FIRST build row; 0 in every other row (group_count: the first-occurrence rule).  probe_values has at least
         len(probe_keys) words; the first len(probe_keys) are read.  out= / counts_out=: accumulators the call combines into in place and
         returns (group_count); when counts are asked for, both are given or neither - one flag covers the call - and counts_out implies
-        return_counts."""
+        return_counts.
+        float64=True: probe_values is a floating-point column (NumPy float64 and torch.float64 / DLPack are read in place, float32 /
+        float16 are widened exactly; integers raise TypeError) and sums is float64 - a NumPy array, or a torch.float64 tensor on the
+        device - 0.0 in every row without a partner; counts stay int64.  out= must then be float64 (a torch.float64 tensor on the
+        index's device, or a writable C-contiguous NumPy float64 array; anything else is a TypeError), counts_out stays int64.  The sum
+        is accumulated with atomic adds in an UNSPECIFIED ORDER: it can differ in its last bits from run to run and from a sequential
+        sum.  A NaN makes the sum of its own key NaN and touches no other key."""
         if probe_values is None:
             raise ValueError("Index.group_sum: probe_values is required (group_count takes none)")
+        if float64:
+            pv = _float_words("Index.group_sum", "probe_values", probe_values)
+            m, sec, vals, counts = self._group("Index.group_sum", probe_keys, pv, ALGO_AGG_FLOAT, out, counts_out, return_counts, float64=True)
+            return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
         m, sec, vals, counts = self._group("Index.group_sum", probe_keys, probe_values, 0, out, counts_out, return_counts)
         return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
 
-    def _group_minmax(self, name: str, flag: int, probe_keys, probe_values, out, return_counts, counts_out, signed):
+    def _group_minmax(self, name: str, flag: int, probe_keys, probe_values, out, return_counts, counts_out, signed, float64: bool = False):
         if probe_values is None:
             raise ValueError(f"{name}: probe_values is required (group_count takes none)")
+        if float64:
+            pv = _float_words(name, "probe_values", probe_values, signed)
+            m, sec, vals, counts = self._group(name, probe_keys, pv, flag | ALGO_AGG_FLOAT, out, counts_out, return_counts, float64=True)
+            return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
         if signed is not None and not isinstance(signed, (bool, np.bool_)):
             raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
         probe_values = _from_dlpack_if_device(probe_values)
@@ -919,19 +996,23 @@ class Index:
         m, sec, vals, counts = self._group(name, probe_keys, probe_values, flag | (ALGO_AGG_SIGNED if signed else 0), out, counts_out, return_counts)
         return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
 
-    def group_min(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None):
+    def group_min(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None, float64: bool = False):
         """Cheapest offer per product over a batch: values[i] = the minimum of probe_values[j] over the rows j whose key equals build
         key i, at the key's FIRST build row (group_count: the first-occurrence rule).  signed=None follows the rule of group_join_min: a
         NumPy uint64 (torch.uint64) value column compares unsigned, everything else signed; True / False force it.  A row without a
         partner - every further copy of a duplicated key among them - holds the aggregate's identity, 2^64 - 1 (unsigned) or 2^63 - 1
         (signed); a true minimum equal to it is told apart by the counts.  The outputs are int64 storage of the words.  out= /
         counts_out= as for group_sum: the call takes the minimum of what `out` holds and the batch's - start a running minimum from a
-        call without out=, or from a buffer filled with the identity - and rows without a partner keep their contents."""
-        return self._group_minmax("Index.group_min", ALGO_AGG_MIN, probe_keys, probe_values, out, return_counts, counts_out, signed)
+        call without out=, or from a buffer filled with the identity - and rows without a partner keep their contents.
+        float64=True: probe_values is a floating-point column (as for group_sum), `signed` must stay None (TypeError otherwise) and the
+        minima are float64, compared as numbers; the identity is +inf, out= must be float64 (group_sum), counts_out stays int64.  Which
+        zero comes back for a key that holds both -0.0 and +0.0 is unspecified; a NaN makes the minimum of its own key unspecified and
+        touches no other key."""
+        return self._group_minmax("Index.group_min", ALGO_AGG_MIN, probe_keys, probe_values, out, return_counts, counts_out, signed, float64)
 
-    def group_max(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None):
-        """Latest event per user over a batch: the max form of group_min.  Identity: 0 (unsigned) or -2^63 (signed)."""
-        return self._group_minmax("Index.group_max", ALGO_AGG_MAX, probe_keys, probe_values, out, return_counts, counts_out, signed)
+    def group_max(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None, float64: bool = False):
+        """Latest event per user over a batch: the max form of group_min.  Identity: 0 (unsigned) or -2^63 (signed); float64=True: -inf."""
+        return self._group_minmax("Index.group_max", ALGO_AGG_MAX, probe_keys, probe_values, out, return_counts, counts_out, signed, float64)
 
 
 
@@ -1040,19 +1121,32 @@ def group_join_count(build_keys, probe_keys):
     return P, sec, counts
 
 
-def group_join_sum(build_keys, probe_keys, probe_values, return_counts: bool = False):
+def group_join_sum(build_keys, probe_keys, probe_values, return_counts: bool = False, float64: bool = False):
     """Sum form: (P, seconds, sums) or, return_counts=True, (P, seconds, sums, counts).  sums[i] = the sum modulo 2^64 of
     probe_values[j] over the probe rows j whose key equals build_keys[i] (int64 storage of the uint64 words), 0 where there are none;
-    probe_values has one word per probe row.  The mean is sums / counts."""
+    probe_values has one word per probe row.  The mean is sums / counts.
+    float64=True: probe_values is a floating-point column - NumPy float64 and torch.float64 / DLPack are read in place, float32 /
+    float16 are widened exactly, integers raise TypeError - and sums is float64 (a NumPy array, or a torch.float64 tensor on the
+    inputs' device), 0.0 where there is no partner; counts stay int64.  The sum is accumulated with atomic adds in an
+    UNSPECIFIED ORDER: it can differ in its last bits from run to run and from a sequential sum.  A NaN makes the sum of its own
+    key NaN and touches no other key.  Without the keyword a NumPy float column is value-cast to uint64 words, as ever."""
     if probe_values is None:
         raise ValueError("group_join_sum: probe_values is required (group_join_count takes none)")
+    if float64:
+        pv = _float_words("group_join_sum", "probe_values", probe_values)
+        P, sec, counts, sums = _group(build_keys, probe_keys, pv, bool(return_counts), ALGO_AGG_FLOAT)
+        return (P, sec, _as_float64(sums), counts) if return_counts else (P, sec, _as_float64(sums))
     P, sec, counts, sums = _group(build_keys, probe_keys, probe_values, bool(return_counts))
     return (P, sec, sums, counts) if return_counts else (P, sec, sums)
 
 
-def _group_minmax(name: str, flag: int, build_keys, probe_keys, probe_values, return_counts: bool, signed):
+def _group_minmax(name: str, flag: int, build_keys, probe_keys, probe_values, return_counts: bool, signed, float64: bool = False):
     if probe_values is None:
         raise ValueError(f"{name}: probe_values is required (group_join_count takes none)")
+    if float64:
+        pv = _float_words(name, "probe_values", probe_values, signed)
+        P, sec, counts, vals = _group(build_keys, probe_keys, pv, bool(return_counts), flag | ALGO_AGG_FLOAT)
+        return (P, sec, _as_float64(vals), counts) if return_counts else (P, sec, _as_float64(vals))
     if signed is not None and not isinstance(signed, (bool, np.bool_)):
         raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
     # the sign of the container: a NumPy uint64 column (a torch.uint64 tensor) compares unsigned, everything else signed
@@ -1069,7 +1163,7 @@ def _group_minmax(name: str, flag: int, build_keys, probe_keys, probe_values, re
     return (P, sec, vals, counts) if return_counts else (P, sec, vals)
 
 
-def group_join_min(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None):
+def group_join_min(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None, float64: bool = False):
     """Min form: (P, seconds, values) or, return_counts=True, (P, seconds, values, counts).  values[i] = the minimum of probe_values[j]
     over the probe rows j whose key equals build_keys[i] ("cheapest offer per product"); every copy of a duplicated build key carries
     the key's minimum; P = the sum of all counts.  signed=None takes the sign from the container: a NumPy uint64 value column
@@ -1078,16 +1172,20 @@ def group_join_min(build_keys, probe_keys, probe_values, return_counts: bool = F
     equals the identity looks the same: return_counts=True is how to tell them apart (counts[i] == 0: no partner).
     NumPy in, NumPy out: values has the dtype of probe_values when that is uint64 / int64 and `signed` agrees with it, otherwise it is
     the int64 storage of the words; counts is int64.  Torch ROCm tensors / DLPack are joined in place, the outputs are torch.int64 on
-    their device.  The probe side moves keys and values once; no pairs are made (csrc/fj_group.hip)."""
-    return _group_minmax("group_join_min", ALGO_AGG_MIN, build_keys, probe_keys, probe_values, return_counts, signed)
+    their device.  The probe side moves keys and values once; no pairs are made (csrc/fj_group.hip).
+    float64=True: probe_values is a floating-point column (as for group_join_sum), `signed` must stay None (TypeError otherwise) and
+    values is float64, compared as numbers; a build row without a partner holds +inf (group_join_max: -inf) and count 0.  Which zero
+    comes back for a key that holds both -0.0 and +0.0 is unspecified; a NaN makes the minimum / maximum of its own key unspecified
+    and touches no other key."""
+    return _group_minmax("group_join_min", ALGO_AGG_MIN, build_keys, probe_keys, probe_values, return_counts, signed, float64)
 
 
-def group_join_max(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None):
+def group_join_max(build_keys, probe_keys, probe_values, return_counts: bool = False, signed=None, float64: bool = False):
     """Max form of group_join_min ("latest order date per customer"): values[i] = the maximum of probe_values[j] over the probe rows j
     whose key equals build_keys[i].  A build row WITHOUT a partner holds the aggregate's identity: 0 (unsigned) or -2^63 (signed); a
     key whose true maximum equals it looks the same, so ask for return_counts=True to tell them apart (counts[i] == 0: no partner).
-    Arguments, `signed`, containers and dtypes as for group_join_min."""
-    return _group_minmax("group_join_max", ALGO_AGG_MAX, build_keys, probe_keys, probe_values, return_counts, signed)
+    Arguments, `signed`, `float64` (identity -inf), containers and dtypes as for group_join_min."""
+    return _group_minmax("group_join_max", ALGO_AGG_MAX, build_keys, probe_keys, probe_values, return_counts, signed, float64)
 
 
 # ---- extension: group-by on one relation (the distinct keys and one aggregate per key; csrc/fj_groupby.hip) ----------------------------
@@ -1235,28 +1333,39 @@ def group_by_count(keys):
     return _group_by(keys, None, 0)
 
 
-def group_by_sum(keys, values):
+def group_by_sum(keys, values, float64: bool = False):
     """GROUP BY keys, SUM(values): (g, seconds, group_keys, sums), sums[i] = the sum modulo 2^64 of values[j] over the rows j whose
-    key is group_keys[i] (int64 storage of the uint64 words).  values has one word per row."""
+    key is group_keys[i] (int64 storage of the uint64 words).  values has one word per row.
+    float64=True: values is a floating-point column - NumPy float64 and torch.float64 / DLPack are read in place, float32 / float16
+    are widened exactly, integers raise TypeError - and sums is float64 (a NumPy array, or a torch.float64 tensor on the inputs'
+    device).  The sum is accumulated with atomic adds in an UNSPECIFIED ORDER: it can differ in its last bits from run to run and
+    from a sequential sum.  A NaN makes the sum of its own group NaN and touches no other group.  Without the keyword a NumPy float
+    column is value-cast to uint64 words, as ever, and a torch float tensor is refused."""
     if values is None:
         raise ValueError("group_by_sum: values is required (group_by_count takes none)")
+    if float64:
+        g, sec, gk, sums = _group_by(keys, _float_words("group_by_sum", "values", values), ALGO_AGG_FLOAT)
+        return g, sec, gk, _as_float64(sums)
     return _group_by(keys, values, 0)
 
 
-def _group_by_minmax(name: str, flag: int, keys, values, signed):
+def _group_by_minmax(name: str, flag: int, keys, values, signed, float64: bool = False):
     if values is None:
         raise ValueError(f"{name}: values is required")
+    if float64:
+        g, sec, gk, vals = _group_by(keys, _float_words(name, "values", values, signed), flag | ALGO_AGG_FLOAT)
+        return g, sec, gk, _as_float64(vals)
     if signed is not None and not isinstance(signed, (bool, np.bool_)):
         raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
     values = _from_dlpack_if_device(values)
     if _is_torch_tensor(values):
         if values.dtype.is_floating_point:
-            raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers)")
+            raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
         unsigned_in = str(values.dtype) == "torch.uint64"
     else:
         values = np.asarray(values)
         if values.dtype.kind not in "iub":
-            raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers)")
+            raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
         unsigned_in = values.dtype == np.uint64
     signed = (not unsigned_in) if signed is None else bool(signed)
     g, sec, gk, vals = _group_by(keys, values, flag | (ALGO_AGG_SIGNED if signed else 0))
@@ -1265,16 +1374,19 @@ def _group_by_minmax(name: str, flag: int, keys, values, signed):
     return g, sec, gk, vals
 
 
-def group_by_min(keys, values, signed=None):
+def group_by_min(keys, values, signed=None, float64: bool = False):
     """GROUP BY keys, MIN(values): (g, seconds, group_keys, values).  signed=None takes the sign from the container, as group_join_min
     does: a NumPy uint64 column compares unsigned, everything else signed; True / False force it.  Every group has a row, so no
-    identity appears.  NumPy in: the minima have the dtype of `values` when that is uint64 / int64 and `signed` agrees, else int64."""
-    return _group_by_minmax("group_by_min", ALGO_AGG_MIN, keys, values, signed)
+    identity appears.  NumPy in: the minima have the dtype of `values` when that is uint64 / int64 and `signed` agrees, else int64.
+    float64=True: values is a floating-point column (as for group_by_sum), `signed` must stay None (TypeError otherwise) and the
+    minima are float64, compared as numbers.  Which zero comes back for a group that holds both -0.0 and +0.0 is unspecified; a NaN
+    makes the minimum of its own group unspecified and touches no other group."""
+    return _group_by_minmax("group_by_min", ALGO_AGG_MIN, keys, values, signed, float64)
 
 
-def group_by_max(keys, values, signed=None):
-    """GROUP BY keys, MAX(values): the max form of group_by_min."""
-    return _group_by_minmax("group_by_max", ALGO_AGG_MAX, keys, values, signed)
+def group_by_max(keys, values, signed=None, float64: bool = False):
+    """GROUP BY keys, MAX(values): the max form of group_by_min (`float64` included)."""
+    return _group_by_minmax("group_by_max", ALGO_AGG_MAX, keys, values, signed, float64)
 
 
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------

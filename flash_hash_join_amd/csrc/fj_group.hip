@@ -23,6 +23,11 @@
 // the flush skips a slot that still holds the identity and combines the others into out[position] with the matching global atomic.  No
 // pass over the outputs afterwards.  P and the duplicates are handled as in the sum form.
 //
+// Float aggregates (FJ_ALGO_AGG_FLOAT: FJ_GJ_SUM_F / FJ_GJ_MIN_F / FJ_GJ_MAX_F): three more aggregate parameters of the same kernels.  The
+// values and accumulators are IEEE-754 binary64 in the same 8-byte words; the sum is one native f64 atomic add per hit (LDS) and per
+// flushed row (HBM), min / max one integer atomic on the raw bits chosen by the value's sign bit (gj_combine, csrc/fj_group_dev.h);
+// identities +0.0, +inf, -inf.  Every word they touch is LDS or device memory of the call (DESIGN.md "Float aggregates").
+//
 // Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole join on the global HBM table (the kernels at
 // the end of this file), timings.fell_back = 1.
 #include "fj_host.h"
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     u64* tkeys = reinterpret_cast<u64*>(smem + sizeof(GjHdr));
     u64* acc = tkeys + GJ_TS;
     constexpr bool SUM = AGG != FJ_GJ_COUNT;                 // the probe side carries values; hits are counted instead of counts flushed
-    constexpr bool MINMAX = AGG >= FJ_GJ_MIN_U;
+    constexpr bool MINMAX = AGG >= FJ_GJ_MIN_U && AGG != FJ_GJ_SUM_F;
     constexpr u64 IDENT = gj_identity<AGG>();
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
                 v = acc[pos];
             }
             if (v == IDENT) continue;                        // (count, sum: 0 adds nothing; min / max: out[] holds the identity already)
-            if (!MINMAX) flushed += v;
+            if (!SUM && !MINMAX) flushed += v;               // (the count form's total: never a value's bits)
             if (!out) continue;
             const u64 o = a.build.vals ? a.build.vals[src] : src;             // (zero-pass plan: the flat index IS the position)
             if (o < nb) gj_combine<AGG>(&out[o], v);                          // (always: positions are 0 .. nb - 1)
@@ -228,7 +233,7 @@ __global__ __launch_bounds__(1024) void fj_gt_group_flush_kernel(FjGtArgs a, con
     if (tid == 0 && s_total) atomicAdd(a.total, s_total);
 }
 
-// out[i] = v for i < n: the identities that are no byte pattern (INT64_MAX, INT64_MIN)
+// out[i] = v for i < n: the identities that are no byte pattern (INT64_MAX, INT64_MIN, the bits of +inf and -inf)
 __global__ __launch_bounds__(256) void fj_fill64_kernel(u64* __restrict__ out, u64 v, u64 n) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = v;
@@ -237,7 +242,8 @@ __global__ __launch_bounds__(256) void fj_fill64_kernel(u64* __restrict__ out, u
 }  // namespace
 
 u64 fj_group_identity(int agg) {
-    return agg == FJ_GJ_MIN_U ? ~0ull : agg == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : agg == FJ_GJ_MAX_S ? 0x8000000000000000ull : 0ull;
+    return agg == FJ_GJ_MIN_U ? ~0ull : agg == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : agg == FJ_GJ_MAX_S ? 0x8000000000000000ull :
+           agg == FJ_GJ_MIN_F ? 0x7FF0000000000000ull : agg == FJ_GJ_MAX_F ? 0xFFF0000000000000ull : 0ull;      // (+inf, -inf; the float sum: +0.0)
 }
 
 hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s) {
@@ -252,14 +258,16 @@ hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s) {
 hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 nb, hipStream_t s) {
     const u32 grid = a.items ? a.items_cap : a.nparts * a.nsplit;
     const bool vals = agg != FJ_GJ_COUNT;
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST) return hipErrorInvalidValue;
     if (!a.err || (!out && (vals || !a.total))) return hipErrorInvalidValue;
     if (vals && !a.probe.vals) return hipErrorInvalidValue;                       // the probe side carries the values
     const u32 lds = (u32)sizeof(GjHdr) + GJ_TS * 16u;
     void (*kern)(FjLdsJoinArgs, u64*, u64) =
         agg == FJ_GJ_COUNT ? fj_group_join_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_group_join_kernel<FJ_GJ_SUM> :
         agg == FJ_GJ_MIN_U ? fj_group_join_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_group_join_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_group_join_kernel<FJ_GJ_MAX_U> : fj_group_join_kernel<FJ_GJ_MAX_S>;
+        agg == FJ_GJ_MAX_U ? fj_group_join_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_group_join_kernel<FJ_GJ_MAX_S> :
+        agg == FJ_GJ_SUM_F ? fj_group_join_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_group_join_kernel<FJ_GJ_MIN_F> :
+        fj_group_join_kernel<FJ_GJ_MAX_F>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(GJ_NT), lds, s, a, out, nb);
@@ -268,12 +276,14 @@ hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 n
 
 hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigned long long* cnt, unsigned long long* sum, u64* out_cnt, u64* out_sum, hipStream_t s) {
     if (!a.total || !cnt || (!out_cnt && !out_sum) || (out_sum && (!sum || !pv))) return hipErrorInvalidValue;
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || (out_sum && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_sum && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     if (a.np) {
         const u64 rounds = (a.np + 1023) / 1024;
         void (*probe)(FjGtArgs, const u64*, unsigned long long*, unsigned long long*) =
             agg == FJ_GJ_MIN_U ? fj_gt_group_probe_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_probe_kernel<FJ_GJ_MIN_S> :
             agg == FJ_GJ_MAX_U ? fj_gt_group_probe_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_probe_kernel<FJ_GJ_MAX_S> :
+            agg == FJ_GJ_SUM_F ? fj_gt_group_probe_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_probe_kernel<FJ_GJ_MIN_F> :
+            agg == FJ_GJ_MAX_F ? fj_gt_group_probe_kernel<FJ_GJ_MAX_F> :
             fj_gt_group_probe_kernel<FJ_GJ_SUM>;                                  // (the count form: sum == nullptr)
         hipLaunchKernelGGL(probe, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
     }

@@ -21,16 +21,31 @@ __device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
 
 // the aggregate's identity: what an accumulator holds before its first hit and a build row without a partner receives
 template <int AGG> __device__ __forceinline__ constexpr u64 gj_identity() {
-    return AGG == FJ_GJ_MIN_U ? ~0ull : AGG == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : AGG == FJ_GJ_MAX_S ? 0x8000000000000000ull : 0ull;
+    return AGG == FJ_GJ_MIN_U ? ~0ull : AGG == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : AGG == FJ_GJ_MAX_S ? 0x8000000000000000ull :
+           AGG == FJ_GJ_MIN_F ? 0x7FF0000000000000ull : AGG == FJ_GJ_MAX_F ? 0xFFF0000000000000ull : 0ull;      // (+inf, -inf; the float sum: +0.0)
 }
 
 // one atomic of the aggregate's own type on an accumulator, in LDS or in HBM (count and sum: the add; min / max: the native 64-bit
-// atomic of the value's signedness - no transform of the words, so nothing to undo afterwards)
+// atomic of the value's signedness - no transform of the words, so nothing to undo afterwards).
+// The float forms (the word holds an IEEE-754 binary64): the sum is the native f64 atomic add - p must be LDS or ordinary device
+// memory.  Min / max work on the raw bits, split by the value's sign BIT (not v >= 0: -0.0 has it set): doubles of a clear sign
+// order like int64, doubles of a set sign order backwards as uint64 and lie below every one of a clear sign.  So a minimum is the
+// signed integer minimum for a value of a clear sign (an accumulator of a set sign is negative as int64 and stays) and the unsigned
+// integer MAXIMUM for one of a set sign (an accumulator of a clear sign is smaller as uint64 and gives way); the maximum is the
+// mirror image.  One integer atomic either way, no transform of the words: it works in place on a caller's running aggregate.
 template <int AGG> __device__ __forceinline__ void gj_combine(u64* p, u64 v) {
     if constexpr (AGG == FJ_GJ_MIN_U) atomicMin((unsigned long long*)p, (unsigned long long)v);
     else if constexpr (AGG == FJ_GJ_MIN_S) atomicMin((long long*)p, (long long)v);
     else if constexpr (AGG == FJ_GJ_MAX_U) atomicMax((unsigned long long*)p, (unsigned long long)v);
     else if constexpr (AGG == FJ_GJ_MAX_S) atomicMax((long long*)p, (long long)v);
+    else if constexpr (AGG == FJ_GJ_SUM_F) atomicAdd(reinterpret_cast<double*>(p), __longlong_as_double((long long)v));
+    else if constexpr (AGG == FJ_GJ_MIN_F) {
+        if (v >> 63) atomicMax((unsigned long long*)p, (unsigned long long)v);
+        else atomicMin((long long*)p, (long long)v);
+    } else if constexpr (AGG == FJ_GJ_MAX_F) {
+        if (v >> 63) atomicMin((unsigned long long*)p, (unsigned long long)v);
+        else atomicMax((long long*)p, (long long)v);
+    }
     else atomicAdd((unsigned long long*)p, (unsigned long long)v);
 }
 

@@ -15,6 +15,9 @@
 // relation, at the row's own position (fj_group_by_inverse_kernel: the table from the keys, the ranks, then a second sweep over the
 // partition's rows).  np.unique(return_inverse=True) / pandas.factorize without the sort.
 //
+// Float aggregates (FJ_ALGO_AGG_FLOAT: FJ_GJ_SUM_F / FJ_GJ_MIN_F / FJ_GJ_MAX_F): the value column and the accumulators hold IEEE-754
+// binary64 in the same words - one native f64 LDS atomic add per row, or one integer atomic on the raw bits for min / max (gj_combine).
+//
 // Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition, and its LDS atomics hit
 // one address; fewer than ~256 distinct keys leave CUs idle.  Correct at any distribution (DESIGN.md "Group-by on one relation").
 //
@@ -341,7 +344,9 @@ template <bool EMIT> hipError_t launch_lds(const FjGroupByArgs& a, int agg, hipS
     if constexpr (EMIT)
         kern = agg == FJ_GJ_COUNT ? fj_group_by_kernel<FJ_GJ_COUNT, true> : agg == FJ_GJ_SUM ? fj_group_by_kernel<FJ_GJ_SUM, true> :
                agg == FJ_GJ_MIN_U ? fj_group_by_kernel<FJ_GJ_MIN_U, true> : agg == FJ_GJ_MIN_S ? fj_group_by_kernel<FJ_GJ_MIN_S, true> :
-               agg == FJ_GJ_MAX_U ? fj_group_by_kernel<FJ_GJ_MAX_U, true> : fj_group_by_kernel<FJ_GJ_MAX_S, true>;
+               agg == FJ_GJ_MAX_U ? fj_group_by_kernel<FJ_GJ_MAX_U, true> : agg == FJ_GJ_MAX_S ? fj_group_by_kernel<FJ_GJ_MAX_S, true> :
+               agg == FJ_GJ_SUM_F ? fj_group_by_kernel<FJ_GJ_SUM_F, true> : agg == FJ_GJ_MIN_F ? fj_group_by_kernel<FJ_GJ_MIN_F, true> :
+               fj_group_by_kernel<FJ_GJ_MAX_F, true>;
     else kern = fj_group_by_kernel<FJ_GJ_COUNT, false>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -352,7 +357,7 @@ template <bool EMIT> hipError_t launch_lds(const FjGroupByArgs& a, int agg, hipS
 }  // namespace
 
 hipError_t fj_launch_group_by(const FjGroupByArgs& a, int agg, bool emit, hipStream_t s) {
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || !a.cursor || !a.err || !a.nparts) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || !a.cursor || !a.err || !a.nparts) return hipErrorInvalidValue;
     if (emit && !a.out_keys) return hipErrorInvalidValue;
     if (!emit && agg != FJ_GJ_COUNT) return hipErrorInvalidValue;                 // (the total needs no aggregate)
     return emit ? launch_lds<true>(a, agg, s) : launch_lds<false>(a, agg, s);
@@ -368,13 +373,15 @@ hipError_t fj_launch_group_by_inverse(const FjGroupByArgs& a, hipStream_t s) {
 }
 
 hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s) {
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
     const u64 rounds = (a.nb + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*) =
         agg == FJ_GJ_COUNT ? fj_gt_group_by_combine_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM> :
         agg == FJ_GJ_MIN_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_U> : fj_gt_group_by_combine_kernel<FJ_GJ_MAX_S>;
+        agg == FJ_GJ_MAX_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_S> :
+        agg == FJ_GJ_SUM_F ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_F> :
+        fj_gt_group_by_combine_kernel<FJ_GJ_MAX_F>;
     hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, vals, acc);
     return hipGetLastError();
 }

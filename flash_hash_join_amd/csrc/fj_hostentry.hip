@@ -183,7 +183,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
-    const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
+    const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
                           (gb ? FJ_ALGO_INVERSE : 0);                                                     // a modifier of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
@@ -191,6 +191,11 @@ int fj_join_host(int algo, int bloom, int materialize,
             return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (pk || np) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (algo & FJ_ALGO_AGG_FLOAT) {                        // the value column and *out_vals hold IEEE-754 doubles
+            if (asigned) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (rid || inv) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_%s (positions and group ids are integers)", rid ? "ROW_IDS" : "INVERSE");
+            if (nb && !bv) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT with FJ_ALGO_GROUP_BY needs build_vals (the float64 value column, nb words: the count form has no float form)");
+        }
         if (inv) {                                             // the group id of every row: *out_vals nb words, no aggregate beside it
             if (amin || amax || asigned)
                 return set_err("fj_join_host: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_AGG_%s (the ids group the rows once: every aggregate is a pass of the caller's over them)",
@@ -212,6 +217,11 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (many_host || left || anti || rid || full || allc || po)
             return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
+        if (algo & FJ_ALGO_AGG_FLOAT) {                        // the probe side's value column and *out_vals hold IEEE-754 doubles
+            if (asigned) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (np && !bv) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs build_vals (here the probe side's float64 value column, np words: the count form has no float form)");
+            if (!out_vals) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs out_vals (the float64 aggregates; the counts alone are the plain count form)");
+        }
         if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if (!materialize) return set_err("fj_join_host: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");

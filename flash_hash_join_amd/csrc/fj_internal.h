@@ -396,9 +396,11 @@ hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u6
 // raises FJ_STAT_DUPS where a partition's build keys repeat (then the hits are not P).  A partition beyond the table: FJ_ERR_LDS_FULL.
 // agg: FJ_GJ_COUNT / FJ_GJ_SUM as above; the four min / max forms combine the values with the native 64-bit atomic min / max of their
 // signedness instead of adding them - out then holds the aggregate's identity (fj_group_identity) before the launch, not zeros - and
-// report P like the sum form.
-enum { FJ_GJ_COUNT = 0, FJ_GJ_SUM = 1, FJ_GJ_MIN_U = 2, FJ_GJ_MIN_S = 3, FJ_GJ_MAX_U = 4, FJ_GJ_MAX_S = 5 };
-u64 fj_group_identity(int agg);                                         // 0, 0, UINT64_MAX, INT64_MAX, 0, INT64_MIN
+// report P like the sum form.  The three float forms (FJ_ALGO_AGG_FLOAT) read the words as IEEE-754 binary64: FJ_GJ_SUM_F is the sum
+// form with the native f64 atomic add, FJ_GJ_MIN_F / FJ_GJ_MAX_F are min / max forms whose identities are the bits of +inf / -inf.
+enum { FJ_GJ_COUNT = 0, FJ_GJ_SUM = 1, FJ_GJ_MIN_U = 2, FJ_GJ_MIN_S = 3, FJ_GJ_MAX_U = 4, FJ_GJ_MAX_S = 5,
+       FJ_GJ_SUM_F = 6, FJ_GJ_MIN_F = 7, FJ_GJ_MAX_F = 8, FJ_GJ_LAST = FJ_GJ_MAX_F };
+u64 fj_group_identity(int agg);                                         // 0, 0, UINT64_MAX, INT64_MAX, 0, INT64_MIN, +0.0, +inf, -inf
 hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s);      // out[0 .. n) = the identity: a memset where it is a byte pattern, else a fill kernel
 hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 nb, hipStream_t s);
 // global table built by fj_launch_gt_build_first (vals = false): one thread per probe row adds to cnt[slot] (and sum[slot] += pv[i] when

@@ -692,7 +692,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
     const uint64_t* d_rv = nullptr;                         // FJ_ALGO_RETAIN_BUILD: the caller's d_build_vals as given (null: a keys-only side)
     const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
-               asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0;
+               asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0, afloat = (bo || gb) && (algo & FJ_ALGO_AGG_FLOAT) != 0;
     int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
     const int algo_word = algo;
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
@@ -702,11 +702,16 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE);
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (afloat) {                                       // the value column and d_out_vals hold IEEE-754 doubles
+            if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_%s (positions and group ids are integers)", rid ? "ROW_IDS" : "INVERSE");
+            if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_GROUP_BY needs d_build_vals (the float64 value column, nb words: the count form has no float form)");
+        }
         if (inv) {                                          // the group id of every row (d_out_vals: nb words), no aggregate beside it
             if (amin || amax || asigned)
                 return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_AGG_%s (the ids group the rows once: every aggregate is a pass of the caller's over them)",
@@ -727,6 +732,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         }
         if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
         if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+        if (afloat) agg = amin ? FJ_GJ_MIN_F : amax ? FJ_GJ_MAX_F : FJ_GJ_SUM_F;
         if (!amin && !amax && !d_bv) agg = FJ_GJ_COUNT;
         d_gv = (rid || inv) ? nullptr : d_bv;
         if (!d_bv || rid || inv) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
@@ -735,13 +741,18 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
         // d_out_keys = the counts, d_out_vals = the sums (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX: the minima / maxima), nb words each.
         // The three aggregate flags are modifiers of this one: without it they are an unknown algo below
-        algo &= ~(FJ_ALGO_BUILD_ORDER | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED);
+        algo &= ~(FJ_ALGO_BUILD_ORDER | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT);
         if (bo_reuse) algo &= ~(FJ_ALGO_REUSE_BUILD | FJ_ALGO_ACCUMULATE);
         if (many || left || anti || rid || full || allc || po)
             return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
         // onto the prepared build side (csrc/fj_prepared.hip): no build side in the call - d_build_vals is the PROBE side's value column
         // here, so it is not looked at; the outputs hold NB words, the rows the side was prepared from (checked on the context)
+        if (afloat) {                                       // the probe side's value column and d_out_vals hold IEEE-754 doubles
+            if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (np && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs d_build_vals (here the probe side's float64 value column, np words: the count form has no float form)");
+            if ((nb || bo_reuse) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs d_out_vals (the float64 aggregates; the counts alone are the plain count form)");
+        }
         if (bo_reuse && (d_bk || nb)) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD takes no build side (d_build_keys must be NULL and nb 0: the context's prepared side is aggregated onto; d_build_vals is the probe side's value column)");
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
@@ -753,6 +764,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (np && d_out_vals && !d_bv) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER with d_out_vals needs d_build_vals (here the probe side's value column, np words)");
         if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
         if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+        if (afloat) agg = amin ? FJ_GJ_MIN_F : amax ? FJ_GJ_MAX_F : FJ_GJ_SUM_F;
         d_pv = d_bv;
         if (!d_bv) d_bv = d_bk;                             // the counts read no value (the checks below want a pointer)
     }

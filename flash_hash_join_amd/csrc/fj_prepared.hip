@@ -20,6 +20,10 @@
 // The HBM-table form (a partition beyond the LDS table when the side is prepared, scalar_hbm_table = 1, a build side below
 // radix_threshold) needs no kernel of its own: the global table of fj_launch_gt_build_first in owned memory, beside an owned copy of
 // the values and the table's two out-of-band words, probed by fj_launch_gt_probe_order.
+//
+// The aggregate join onto the prepared side (fj_prep_group_kernel, fj_prep_gt_group_kernel) takes the float aggregates too
+// (FJ_ALGO_AGG_FLOAT: FJ_GJ_SUM_F / FJ_GJ_MIN_F / FJ_GJ_MAX_F, gj_combine in csrc/fj_group_dev.h): binary64 values and accumulators in the
+// same words, combined in place into the call's - or the caller's running - float64 output, which must be device memory.
 #include "fj_host.h"
 #include "fj_group_dev.h"
 
@@ -487,14 +491,16 @@ hipError_t fj_launch_prep_probe(const FjPrepProbeArgs& a, hipStream_t s) {
 
 hipError_t fj_launch_prep_group(const FjPrepGroupArgs& a, int agg, hipStream_t s) {
     const u32 grid = a.items ? a.items_cap : a.nparts * a.nsplit;
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST) return hipErrorInvalidValue;
     if (!a.err || !a.runs || !a.keys || !a.rows || !a.out || (a.total && !a.miss_total)) return hipErrorInvalidValue;
     if (agg != FJ_GJ_COUNT && !a.probe.vals) return hipErrorInvalidValue;         // the probe side carries the values
     const u32 lds = (u32)sizeof(PgHdr) + PP_TS * 16u;
     void (*kern)(FjPrepGroupArgs) =
         agg == FJ_GJ_COUNT ? fj_prep_group_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_prep_group_kernel<FJ_GJ_SUM> :
         agg == FJ_GJ_MIN_U ? fj_prep_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_group_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_prep_group_kernel<FJ_GJ_MAX_U> : fj_prep_group_kernel<FJ_GJ_MAX_S>;
+        agg == FJ_GJ_MAX_U ? fj_prep_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_group_kernel<FJ_GJ_MAX_S> :
+        agg == FJ_GJ_SUM_F ? fj_prep_group_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_prep_group_kernel<FJ_GJ_MIN_F> :
+        fj_prep_group_kernel<FJ_GJ_MAX_F>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(PP_NT), lds, s, a);
@@ -506,11 +512,13 @@ hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u6
     if (a.np == 0) return hipSuccess;
     if (!a.total || !miss_total || !err || !a.tkeys || !a.tvals || !a.flags || !a.empty_val || !a.pk) return hipErrorInvalidValue;
     if ((!out_cnt && !out_val) || (out_val && !pv)) return hipErrorInvalidValue;
-    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_MAX_S || (out_val && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_val && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     const u64 rounds = (a.np + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*, u64*, u64, unsigned long long*, u32*) =
         agg == FJ_GJ_MIN_U ? fj_prep_gt_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_gt_group_kernel<FJ_GJ_MIN_S> :
         agg == FJ_GJ_MAX_U ? fj_prep_gt_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_gt_group_kernel<FJ_GJ_MAX_S> :
+        agg == FJ_GJ_SUM_F ? fj_prep_gt_group_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_prep_gt_group_kernel<FJ_GJ_MIN_F> :
+        agg == FJ_GJ_MAX_F ? fj_prep_gt_group_kernel<FJ_GJ_MAX_F> :
         fj_prep_gt_group_kernel<FJ_GJ_SUM>;                                       // (the counts alone: out_val == nullptr)
     hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, out_cnt, out_val, nb, miss_total, err);
     return hipGetLastError();

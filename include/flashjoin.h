@@ -167,6 +167,24 @@ extern "C" {
 #define FJ_ALGO_AGG_MIN    0x4000
 #define FJ_ALGO_AGG_MAX    0x8000
 #define FJ_ALGO_AGG_SIGNED 0x10000
+/* EXTENSION: one more modifier of FJ_ALGO_BUILD_ORDER and FJ_ALGO_GROUP_BY (without either an unknown algo), the FJ_ALGO_REUSE_BUILD and
+ * FJ_ALGO_ACCUMULATE combinations of the former included.  FJ_ALGO_AGG_FLOAT: the value column and the values output hold IEEE-754
+ * binary64 ("double") numbers in their uint64_t slots - d_build_vals (the relation's value column under FJ_ALGO_GROUP_BY, the PROBE
+ * side's under FJ_ALGO_BUILD_ORDER) and d_out_vals; the counts in d_out_keys stay integers.  Alone it is the float SUM, with
+ * FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX the float minimum / maximum.  A build row without a partner receives the aggregate's identity:
+ *   sum +0.0 | min +infinity | max -infinity
+ * and FJ_ALGO_ACCUMULATE combines into what a float64 output holds.  Everything else - the outputs' layout, *out_count, the
+ * first-occurrence rule of the prepared side, the fallback - is that of the integer forms.
+ *   The sum is accumulated with atomic adds in an UNSPECIFIED ORDER: it can differ in its last bits from run to run and from a
+ *   sequential sum (it is exact, and then reproducible, whenever every partial sum is representable).
+ *   Min / max compare as numbers; which zero comes back for a group that holds both -0.0 and +0.0 is unspecified.
+ *   A NaN makes the sum of ITS group NaN and the minimum / maximum of its group unspecified; no other group is affected.
+ * d_out_vals (and a running aggregate under FJ_ALGO_ACCUMULATE) must be ordinary device memory: the float sum is a hardware f64 atomic.
+ * fj_join_host stages through device buffers of its own and returns malloc'ed arrays as for the integer forms.
+ * Refused up front, before any device work, in addition to what the base flag refuses: combined with FJ_ALGO_AGG_SIGNED (a double has
+ * its own sign), with FJ_ALGO_ROW_IDS or FJ_ALGO_INVERSE (positions and ids are integers); without a value column (d_build_vals ==
+ * NULL: the count forms have no float form); under FJ_ALGO_BUILD_ORDER with d_out_vals == NULL. */
+#define FJ_ALGO_AGG_FLOAT  0x2000000
 /* EXTENSION (no reference counterpart; csrc/fj_groupby.hip): OR this into `algo` together with a base value (ADAPTIVE, SCALAR or RADIX:
  * the partitioned plan or the global HBM table exactly as for FJ_ALGO_BUILD_ORDER) for a GROUP BY / DISTINCT on ONE relation: the
  * list of groups that FJ_ALGO_BUILD_ORDER asks its caller for, and one aggregate per group.  The relation is passed as the build side:

@@ -3,7 +3,10 @@ and its inverse (factorize, FJ_ALGO_INVERSE) on device tensors next to the compo
 form, appended to --out:
 
   (a) unique, unique(return_index=True), distinct_count, group_by_count, group_by_sum, group_by_min, group_by_max, factorize,
-      factorize followed by zeros(g).index_add_(0, codes, values) (the sums from the ids: one grouping, then any aggregate)
+      factorize followed by zeros(g).index_add_(0, codes, values) (the sums from the ids: one grouping, then any aggregate);
+      the float64 aggregates (float64=True) beside their integer forms: group_by_sum_f64 / group_by_min_f64, group_join_sum and
+      group_join_sum_f64 (the g distinct keys as the build side), Index.group_sum and Index.group_sum_f64 (an index on them, built
+      outside the timed region), and factorize+index_add_f64, the torch composition on a float64 column
   (b) the composition: torch.unique(keys, return_counts=True) (counts), torch.unique(keys, return_inverse=True) alone (the ids), or
       followed by zeros(g).index_add_(0, inverse, values) (sums) / full(g, INT64_MAX).scatter_reduce_(0, inverse, values, "amin")
       (minima) - the wall time of the steps between two device synchronisations
@@ -91,9 +94,23 @@ def main():
             uk, inv = torch.unique(keys, return_inverse=True)
             return uk.numel(), None, uk, inv
 
-        def factorize_sum():
+        def factorize_sum(v=vals):
             n_g, sec, codes, uk = flash_join.factorize(keys)
-            return n_g, sec, uk, torch.zeros(n_g, dtype=torch.int64, device=keys.device).index_add_(0, codes, vals)
+            return n_g, sec, uk, torch.zeros(n_g, dtype=v.dtype, device=keys.device).index_add_(0, codes, v)
+
+        fvals = torch.randint(-2**20, 2**20, (n,), dtype=torch.int64, device="cuda:0").to(torch.float64) * 2.0**-10      # (exact sums in any order)
+        dkeys = flash_join.unique(keys)[2]                                        # the build side of the join forms: every row has a partner
+        index = []                                                                # built on first use, outside the timed region
+
+        def joined(fn):
+            """a join form's (P or m, seconds, ...) as (g, seconds): every row of `keys` has its partner among the g distinct keys"""
+            def run():
+                if fn.__code__.co_argcount and not index:
+                    index.append(flash_join.build_index(dkeys))
+                r = fn(index[0]) if fn.__code__.co_argcount else fn()
+                assert r[0] == n, (r[0], n)
+                return (g,) + tuple(r[1:])
+            return run
 
         runs = []
         if "a" in forms:
@@ -105,7 +122,14 @@ def main():
                      ("a", "group_by_min", lambda: flash_join.group_by_min(keys, vals)),
                      ("a", "group_by_max", lambda: flash_join.group_by_max(keys, vals)),
                      ("a", "factorize", lambda: flash_join.factorize(keys)),
-                     ("a", "factorize+index_add", factorize_sum)]
+                     ("a", "factorize+index_add", factorize_sum),
+                     ("a", "group_by_sum_f64", lambda: flash_join.group_by_sum(keys, fvals, float64=True)),
+                     ("a", "group_by_min_f64", lambda: flash_join.group_by_min(keys, fvals, float64=True)),
+                     ("a", "group_join_sum", joined(lambda: flash_join.group_join_sum(dkeys, keys, vals))),
+                     ("a", "group_join_sum_f64", joined(lambda: flash_join.group_join_sum(dkeys, keys, fvals, float64=True))),
+                     ("a", "Index.group_sum", joined(lambda ix: ix.group_sum(keys, vals))),
+                     ("a", "Index.group_sum_f64", joined(lambda ix: ix.group_sum(keys, fvals, float64=True))),
+                     ("a", "factorize+index_add_f64", lambda: factorize_sum(fvals))]
         if "b" in forms:
             runs += [("b", "torch.unique(return_counts)", composed_count), ("b", "torch.unique(return_inverse)", composed_inverse),
                      ("b", "torch.unique(return_inverse)+index_add", composed_sum),
@@ -123,7 +147,9 @@ def main():
             out.write(line + "\n")
             out.flush()
             torch.cuda.empty_cache()
-        del keys, vals
+        for ix in index:
+            ix.close()
+        del keys, vals, fvals, dkeys
         torch.cuda.empty_cache()
     out.close()
 
