@@ -12,19 +12,13 @@
 // build side once more with row indices, the FIRST form overwrites every row (a scatter by position is idempotent);
 // FJ_ERR_LDS_FULL -> the whole join on the global HBM table (fj_gt_probe_order_kernel, csrc/fj_join.hip), timings.fell_back = 1.
 #include "fj_host.h"
+#include "fj_lds_table_dev.h"
 
 namespace {
 
 constexpr u32 PO_NT = 1024, PO_KPT = 8, PO_ROUND_CHUNKS = PO_NT * PO_KPT / FJ_CHUNK;
 constexpr u32 PO_TS = 8192, PO_LIMIT = PO_TS - PO_TS / 16;
 struct PoHdr { u32 full, dups, empty_cnt, nkeys, hits, misses, pad0, pad1; u64 empty_val, pad2; };
-
-__device__ __forceinline__ u32 po_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
 
 // FIRST: build 'values' are row indices, the smallest wins (LDS atomic minimum), then - unless RID - one gather from a.orig_vals;
 //        !FIRST: unique build keys expected, a duplicate raises FJ_STAT_DUPS and the item writes nothing
@@ -41,20 +35,9 @@ __global__ __launch_bounds__(PO_NT, 1) void fj_probe_order_join_kernel(FjLdsJoin
     u64* tvals = tkeys + PO_TS;                               // (VALS only)
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
-    u32 p, b0 = 0, nbc, s_lo, s_hi;
-    if (a.items) {
-        if (item >= *a.nitems_dev) return;
-        const uint4 it = a.items[item];
-        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
-    } else {
-        const u32 slice = item % a.nsplit;
-        p = item / a.nsplit;
-        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
-        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
-    }
-    if (s_lo >= s_hi) return;
-    if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
-    else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 p, b0, nbc, s_lo, s_hi;
+    if (!fj_item_slice(a.items, a.nitems_dev, a.nsplit, a.probe.n_flat, item, p, s_lo, s_hi) || s_lo >= s_hi) return;
+    fj_part_chunks(a.build, p, b0, nbc);
 
     for (u32 i = tid; i < PO_TS; i += PO_NT) { tkeys[i] = FJ_EMPTY_KEY; if (FIRST) tvals[i] = ~0ull; }
     if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->hits = 0; hdr->misses = 0; hdr->empty_val = FIRST ? ~0ull : 0ull; }
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(PO_NT, 1) void fj_probe_order_join_kernel(FjLdsJoin
     for (u32 c0 = 0; c0 < nbc; c0 += PO_NT / FJ_CHUNK) {
         const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         if (c >= nbc) continue;
-        const u32 e = po_entry(a.build, b0 + c);
+        const u32 e = fj_chunk_entry(a.build, b0 + c);
         if (off >= FJ_LIST_CNT(e)) continue;
         const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
         const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(PO_NT, 1) void fj_probe_order_join_kernel(FjLdsJoin
             const u32 c = pc + u * (PO_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; pp[u] = 0;
             if (c >= s_hi) continue;
-            const u32 e = po_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.probe.keys[src];

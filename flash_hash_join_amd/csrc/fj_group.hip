@@ -52,20 +52,9 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     constexpr u64 IDENT = gj_identity<AGG>();
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
-    u32 p, b0 = 0, nbc, s_lo, s_hi;
-    if (a.items) {
-        if (item >= *a.nitems_dev) return;
-        const uint4 it = a.items[item];
-        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
-    } else {
-        const u32 slice = item % a.nsplit;
-        p = item / a.nsplit;
-        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
-        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
-    }
-    if (s_lo >= s_hi) return;
-    if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
-    else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 p, b0, nbc, s_lo, s_hi;
+    if (!fj_item_slice(a.items, a.nitems_dev, a.nsplit, a.probe.n_flat, item, p, s_lo, s_hi) || s_lo >= s_hi) return;
+    fj_part_chunks(a.build, p, b0, nbc);
 
     for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; acc[i] = IDENT; }
     if (tid == 0) { hdr->full = 0; hdr->dups = 0; hdr->empty_cnt = 0; hdr->nkeys = 0; hdr->hits = 0; hdr->empty_acc = IDENT; hdr->total = 0; }
@@ -75,7 +64,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
     for (u32 c0 = 0; c0 < nbc; c0 += GJ_NT / FJ_CHUNK) {
         const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         if (c >= nbc) continue;
-        const u32 e = gj_entry(a.build, b0 + c);
+        const u32 e = fj_chunk_entry(a.build, b0 + c);
         if (off >= FJ_LIST_CNT(e)) continue;
         const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
         const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
@@ -112,7 +101,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
             const u32 c = pc + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; if (SUM) vv[SUM ? u : 0] = 0;
             if (c >= s_hi) continue;
-            const u32 e = gj_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.probe.keys[src];
@@ -160,7 +149,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_join_kernel(FjLdsJoinArgs a
         for (u32 c0 = 0; c0 < nbc; c0 += GJ_NT / FJ_CHUNK) {
             const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             if (c >= nbc) continue;
-            const u32 e = gj_entry(a.build, b0 + c);
+            const u32 e = fj_chunk_entry(a.build, b0 + c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);

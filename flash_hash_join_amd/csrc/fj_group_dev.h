@@ -1,17 +1,11 @@
 // fj_group_dev.h -- device-side pieces shared by the two users of the 8192-slot LDS table with one 8-byte accumulator per slot:
-// the build-order aggregate joins (csrc/fj_group.hip) and the group-by on one relation (csrc/fj_groupby.hip).
+// the build-order aggregate joins (csrc/fj_group.hip) and the group-by on one relation (csrc/fj_groupby.hip).  The table itself -
+// home slot, probing, insert and find - is csrc/fj_lds_table_dev.h's; here are the aggregates.
 #pragma once
-#include "fj_internal.h"
+#include "fj_lds_table_dev.h"
 
 constexpr u32 GJ_NT = 1024, GJ_KPT = 8, GJ_ROUND_CHUNKS = GJ_NT * GJ_KPT / FJ_CHUNK;
 constexpr u32 GJ_TS = 8192, GJ_LIMIT = GJ_TS - GJ_TS / 16;
-
-__device__ __forceinline__ u32 gj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
 
 __device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
 #pragma unroll

@@ -43,9 +43,8 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_kernel(FjGroupByArgs a) 
     constexpr u64 IDENT = gj_identity<AGG>();
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 p = blockIdx.x;
-    u32 b0 = 0, nbc;
-    if (a.rel.list) { b0 = a.rel.boff[p]; nbc = a.rel.boff[p + 1] - b0; }
-    else nbc = (u32)((a.rel.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 b0, nbc;
+    fj_part_chunks(a.rel, p, b0, nbc);
     if (nbc == 0) return;
 
     for (u32 i = tid; i < GJ_TS; i += GJ_NT) { tkeys[i] = FJ_EMPTY_KEY; if (EMIT) acc[i] = IDENT; }
@@ -63,7 +62,7 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_kernel(FjGroupByArgs a) 
             const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; if (VALS) vv[VALS ? u : 0] = 0;
             if (c >= nbc) continue;
-            const u32 e = gj_entry(a.rel, b0 + c);
+            const u32 e = fj_chunk_entry(a.rel, b0 + c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.rel.keys[src];
@@ -159,7 +158,7 @@ __device__ __forceinline__ void gb_load_round(const FjChunkSet& rel, u32 b0, u32
         const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         kk[u] = 0; if (POS) vv[POS ? u : 0] = 0;
         if (c >= nbc) continue;
-        const u32 e = gj_entry(rel, b0 + c);
+        const u32 e = fj_chunk_entry(rel, b0 + c);
         if (off >= FJ_LIST_CNT(e)) continue;
         const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
         kk[u] = rel.keys[src];
@@ -175,9 +174,8 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_inverse_kernel(FjGroupBy
     u64* ids = tkeys + GJ_TS;                                // written for every occupied slot before stream 2 reads it: no fill
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 p = blockIdx.x;
-    u32 b0 = 0, nbc;
-    if (a.rel.list) { b0 = a.rel.boff[p]; nbc = a.rel.boff[p + 1] - b0; }
-    else nbc = (u32)((a.rel.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 b0, nbc;
+    fj_part_chunks(a.rel, p, b0, nbc);
     if (nbc == 0) return;
 
     for (u32 i = tid; i < GJ_TS; i += GJ_NT) tkeys[i] = FJ_EMPTY_KEY;

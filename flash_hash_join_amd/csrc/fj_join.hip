@@ -21,7 +21,7 @@
 // Materialisation is two-pass like the reference's small-table strategy (hash_join.cpp:394-444): count per work item
 // -> exclusive scan -> re-probe and write at exact offsets, so the output arrays have exactly `count` rows and no
 // global cursor is contended.
-#include "fj_internal.h"
+#include "fj_lds_table_dev.h"
 
 namespace {
 
@@ -199,14 +199,6 @@ __device__ __forceinline__ void lds_probe(const u64* __restrict__ tkeys, const u
     }
 }
 
-// encoded chunk-list entry ((count-1) << 24 | id) of chunk `idx`; a flat array is read as a virtual chunk list
-__device__ __forceinline__ u32 chunk_entry(const FjChunkSet& cs, u32 idx) {
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
-
 constexpr u32 JB_META = 128;    // build-side chunk-list entries staged in LDS per batch
 constexpr u32 JP_META = 512;    // probe-side chunk-list entries staged in LDS per batch
 
@@ -234,7 +226,7 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
     const u32 tid = threadIdx.x, lane = tid & 63;
 #define FJ_STAMP(i) do { if (a.dbg && tid == 0 && blockIdx.x < 4096) a.dbg[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     FJ_STAMP(0);
-    // work item -> (partition p, probe chunk-list range [p0 + s_lo, p0 + s_hi))
+    // work item -> (partition p, probe chunk-list range [p0 + s_lo, p0 + s_hi)); fj_item_slice / fj_part_chunks (fj_lds_table_dev.h) kept in place: they move this kernel's SGPR spills
     const u32 item = blockIdx.x;
     u32 p, b0 = 0, nbc, p0 = 0, s_lo, s_hi;
     if (a.items) {                                   // chunk-list probe side: the item table (skew-proof slices)
@@ -317,9 +309,9 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
 
     // ---- chunk-list entries of both sides, table init; then the first two probe rounds go in flight
     u32 nbatch = (s_hi - s_lo) < JP_META ? (s_hi - s_lo) : JP_META;
-    for (u32 i = tid; i < nbatch; i += NT) pm[i] = chunk_entry(a.probe, p0 + s_lo + i);
+    for (u32 i = tid; i < nbatch; i += NT) pm[i] = fj_chunk_entry(a.probe, p0 + s_lo + i);
     u32 nbb = nbc < JB_META ? nbc : JB_META;
-    if (tid < nbb) bm[tid] = chunk_entry(a.build, b0 + tid);
+    if (tid < nbb) bm[tid] = fj_chunk_entry(a.build, b0 + tid);
     for (u32 i = tid; i < S / 4 + NGRP / 2; i += NT) ttags[i] = 0;       // tags and group counters
     const bool dedup = MAT && a.dedup != 0;
     if (dedup) for (u32 i = tid; i < S; i += NT) tvals[i] = ~0ull;        // row indices: the minimum wins
@@ -339,7 +331,7 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
         if (bb) {                                   // only partitions with > 128 build chunks get here
             nbb = (nbc - bb) < JB_META ? (nbc - bb) : JB_META;
             __syncthreads();
-            if (tid < nbb) bm[tid] = chunk_entry(a.build, b0 + bb + tid);
+            if (tid < nbb) bm[tid] = fj_chunk_entry(a.build, b0 + bb + tid);
             __syncthreads();
         }
         for (u32 c0 = 0; c0 < nbb; c0 += 16) {
@@ -420,7 +412,7 @@ __global__ __launch_bounds__(NT, 4) void fj_lds_join_kernel(FjLdsJoinArgs a) {
         if (pb != s_lo) {                           // later batches (only very large partitions get here)
             nbatch = (s_hi - pb) < JP_META ? (s_hi - pb) : JP_META;
             __syncthreads();
-            for (u32 i = tid; i < nbatch; i += NT) pm[i] = chunk_entry(a.probe, p0 + pb + i);
+            for (u32 i = tid; i < nbatch; i += NT) pm[i] = fj_chunk_entry(a.probe, p0 + pb + i);
             __syncthreads();
             nrounds = (nbatch + CPR - 1) / CPR;
             load_round(0, nbatch, ka, oka);
@@ -556,7 +548,7 @@ __global__ __launch_bounds__(NT, 4) void fj_count_join_kernel(FjLdsJoinArgs a) {
     u64* ovf = reinterpret_cast<u64*>(bits + S / 32);        // its overflow list
     const u32 tid = threadIdx.x, lane = tid & 63;
     FJ_STAMP(0);
-    // work item -> (partition p, probe chunk-list range [p0 + s_lo, p0 + s_hi))
+    // work item -> (partition p, probe chunk-list range [p0 + s_lo, p0 + s_hi)); fj_item_slice / fj_part_chunks (fj_lds_table_dev.h) kept in place: they move this kernel's SGPR spills
     const u32 item = blockIdx.x;
     u32 p, b0 = 0, nbc, p0 = 0, s_lo, s_hi;
     if (a.items) {                                   // chunk-list probe side: the item table (skew-proof slices)
@@ -626,9 +618,9 @@ __global__ __launch_bounds__(NT, 4) void fj_count_join_kernel(FjLdsJoinArgs a) {
     };
 
     u32 nbatch = (s_hi - s_lo) < JP_META ? (s_hi - s_lo) : JP_META;
-    for (u32 i = tid; i < nbatch; i += NT) pm[i] = chunk_entry(a.probe, p0 + s_lo + i);
+    for (u32 i = tid; i < nbatch; i += NT) pm[i] = fj_chunk_entry(a.probe, p0 + s_lo + i);
     u32 nbb = nbc < JB_META ? nbc : JB_META;
-    if (tid < nbb) bm[tid] = chunk_entry(a.build, b0 + tid);
+    if (tid < nbb) bm[tid] = fj_chunk_entry(a.build, b0 + tid);
     for (u32 i = tid; i < S; i += NT) tkeys[i] = FJ_EMPTY_KEY;
     if (tid < S / 32) bits[tid] = 0;
     if (tid == 0) { hdr->cnt = 0; hdr->has_empty = 0; hdr->nstash = 0; hdr->full = 0; hdr->dups = 0; hdr->empties = 0; hdr->novf = 0; }
@@ -646,7 +638,7 @@ __global__ __launch_bounds__(NT, 4) void fj_count_join_kernel(FjLdsJoinArgs a) {
         if (bb) {
             nbb = (nbc - bb) < JB_META ? (nbc - bb) : JB_META;
             __syncthreads();
-            if (tid < nbb) bm[tid] = chunk_entry(a.build, b0 + bb + tid);
+            if (tid < nbb) bm[tid] = fj_chunk_entry(a.build, b0 + bb + tid);
             __syncthreads();
         }
         for (u32 c0 = 0; c0 < nbb; c0 += 16) {
@@ -694,7 +686,7 @@ __global__ __launch_bounds__(NT, 4) void fj_count_join_kernel(FjLdsJoinArgs a) {
         if (pb != s_lo) {
             nbatch = (s_hi - pb) < JP_META ? (s_hi - pb) : JP_META;
             __syncthreads();
-            for (u32 i = tid; i < nbatch; i += NT) pm[i] = chunk_entry(a.probe, p0 + pb + i);
+            for (u32 i = tid; i < nbatch; i += NT) pm[i] = fj_chunk_entry(a.probe, p0 + pb + i);
             __syncthreads();
             nrounds = (nbatch + CPR - 1) / CPR;
             load_round(0, nbatch, ka, oka);

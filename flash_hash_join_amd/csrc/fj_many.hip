@@ -38,20 +38,13 @@
 // its probe rows hit (one bit per slot, one word for the empty marker's slot MM_S, behind soff) and walks its chunks once more to
 // OR the rows of hit slots into the per-build-row bitmap, counting the newly set bits - fj_mm_join_kernel<.., FULL>'s scheme on
 // the tile; the tiles of a partition hold disjoint rows, so r = nb - marked holds as before.
-#include "fj_internal.h"
+#include "fj_lds_table_dev.h"
 
 namespace {
 
 constexpr u32 MM_S = 8192, MM_ROWS = 4096, MM_NT = 1024, MM_NONE = 0xFFFFFFFFu;
 constexpr u32 MM_SBITS_WORDS = MM_S / 32 + 4;               // FULL: hit bits of the slots + the empty marker's word (16-byte multiple)
 struct MmHdr { u32 nrows, full, empty_head, cursor; unsigned long long cnt; u32 miss, marked; };   // miss: the item's misses (counting) / its miss cursor (emitting)
-
-__device__ __forceinline__ u32 mm_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
 
 // RID (MAT only): the row-id form (FjLdsJoinArgs::row_ids) - build values are row positions, and the probe row's position
 // (its vals plane; flat arrays: the index) takes the key's place
@@ -69,19 +62,9 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
     u32* sbits = rnext + MM_ROWS;                              // (FULL only) [MM_S / 32] hit slots, [MM_S / 32] != 0: the empty marker key was hit
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
-    u32 p, b0 = 0, nbc, s_lo, s_hi;
-    if (a.items) {
-        if (item >= *a.nitems_dev) return;
-        const uint4 it = a.items[item];
-        p = it.z; s_lo = it.x; s_hi = it.x + it.y;
-    } else {
-        const u32 slice = item % a.nsplit;
-        p = item / a.nsplit;
-        const u32 npc = (u32)((a.probe.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
-        s_lo = (u32)(((u64)slice * npc) / a.nsplit); s_hi = (u32)(((u64)(slice + 1) * npc) / a.nsplit);
-    }
-    if (a.build.list) { b0 = a.build.boff[p]; nbc = a.build.boff[p + 1] - b0; }
-    else nbc = (u32)((a.build.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 p, b0, nbc, s_lo, s_hi;
+    if (!fj_item_slice(a.items, a.nitems_dev, a.nsplit, a.probe.n_flat, item, p, s_lo, s_hi)) return;
+    fj_part_chunks(a.build, p, b0, nbc);
     // (OUTER: a partition without build rows still has its probe rows to report - the build loop below runs zero times)
     if ((!OUTER && nbc == 0) || s_lo >= s_hi) { if (!MAT && tid == 0) { a.part_count[item] = 0; if (OUTER) oa.miss_count[item] = 0; } return; }
     if (MAT && a.part_count[item] == 0 && (!OUTER || oa.miss_count[item] == 0)) return;
@@ -95,7 +78,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
     for (u32 c0 = 0; c0 < nbc; c0 += MM_NT / FJ_CHUNK) {
         const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         if (c < nbc) {
-            const u32 e = mm_entry(a.build, b0 + c);
+            const u32 e = fj_chunk_entry(a.build, b0 + c);
             if (off < FJ_LIST_CNT(e)) {
                 const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
                 const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);     // chunk pools hold mixed keys, flat arrays raw ones (fj_common.h)
@@ -138,7 +121,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
         const u32 c = pc + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         u64 key = 0, psrc = 0; bool ok = false;
         if (c < s_hi) {
-            const u32 e = mm_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             psrc = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             if (off < FJ_LIST_CNT(e)) { key = a.probe.keys[psrc]; if (!a.probe.list) key = fj_key_mix(key); ok = true; }
         }
@@ -224,7 +207,7 @@ __global__ __launch_bounds__(MM_NT, 1) void fj_mm_join_kernel(FjLdsJoinArgs a, F
                 bool mt = false;
                 u64 src = 0;
                 if (c < nbc) {
-                    const u32 e = mm_entry(a.build, b0 + c);
+                    const u32 e = fj_chunk_entry(a.build, b0 + c);
                     src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
                     if (off < FJ_LIST_CNT(e)) {
                         const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);

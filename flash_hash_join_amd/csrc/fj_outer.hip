@@ -25,19 +25,13 @@
 // Full outer join (FJ_ALGO_FULL_OUTER): the left join's launch in its FULL form also marks, in a bitmap in HBM, the build rows its
 // probe rows matched; fj_full_sweep_kernel then appends the unmarked build rows behind row np (join_full below).
 #include "fj_host.h"
+#include "fj_lds_table_dev.h"
 
 namespace {
 
 constexpr u32 OJ_NT = 1024, OJ_KPT = 8, OJ_ROUND_CHUNKS = OJ_NT * OJ_KPT / FJ_CHUNK;
 constexpr u32 OJ_MBITS_WORDS = 8192 / 32 + 4;                 // full outer join: hit bits of the 8192 slots + the empty marker's word (16-byte multiple)
 struct OjHdr { u32 full, dups, empty_cnt, nkeys; FjOjCursor cur; u64 empty_val; };
-
-__device__ __forceinline__ u32 oj_entry(const FjChunkSet& cs, u32 idx) {       // ((count-1) << 24) | chunk id; flat arrays as virtual chunks
-    if (cs.list) return cs.list[idx];
-    const u64 rem = cs.n_flat - (u64)idx * FJ_CHUNK;
-    const u32 cnt = rem >= FJ_CHUNK ? FJ_CHUNK : (u32)rem;
-    return ((cnt - 1u) << 24) | idx;
-}
 
 // RID: the row-id form (FjLdsJoinArgs::row_ids; MODE LEFT_FIRST or ANTI) - build values are row positions and the smallest is
 // written as it is; every output row gets the probe row's position (its vals plane; flat arrays: the index), a miss the value ~0
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
     for (u32 c0 = 0; c0 < nbc; c0 += OJ_NT / FJ_CHUNK) {
         const u32 c = c0 + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
         if (c >= nbc) continue;
-        const u32 e = oj_entry(a.build, b0 + c);
+        const u32 e = fj_chunk_entry(a.build, b0 + c);
         if (off >= FJ_LIST_CNT(e)) continue;
         const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
         const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);   // chunk pools hold mixed keys, flat arrays raw ones
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
             kk[u] = 0;
             if (RID) pp[RID ? u : 0] = 0;
             if (c >= s_hi) continue;
-            const u32 e = oj_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.probe.keys[src];
@@ -220,7 +214,7 @@ __global__ __launch_bounds__(OJ_NT, 1) void fj_outer_join_kernel(FjLdsJoinArgs a
             bool mt = false;
             u64 src = 0;
             if (c < nbc) {
-                const u32 e = oj_entry(a.build, b0 + c);
+                const u32 e = fj_chunk_entry(a.build, b0 + c);
                 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
                 if (off < FJ_LIST_CNT(e)) {
                     const u64 key = a.build.list ? a.build.keys[src] : fj_key_mix(a.build.keys[src]);
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(OJ_NT) void fj_full_sweep_kernel(FjChunkSet b, cons
         bool un = false;
         u64 src = 0;
         if (c < nch) {
-            const u32 e = oj_entry(b, c);
+            const u32 e = fj_chunk_entry(b, c);
             src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             if (off < FJ_LIST_CNT(e)) un = !((bits[src >> 6] >> (src & 63)) & 1ull);
         }

@@ -42,9 +42,8 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_build_kernel(FjPrepBuildArgs
     u64* trows = tkeys + PP_TS;
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 p = blockIdx.x;
-    u32 b0 = 0, nbc;
-    if (a.rel.list) { b0 = a.rel.boff[p]; nbc = a.rel.boff[p + 1] - b0; }
-    else nbc = (u32)((a.rel.n_flat + FJ_CHUNK - 1) >> FJ_CHUNK_LOG);
+    u32 b0, nbc;
+    fj_part_chunks(a.rel, p, b0, nbc);
     if (nbc == 0) return;                                    // (its record stays {0, 0}: the host cleared them)
 
     for (u32 i = tid; i < PP_TS; i += PP_NT) { tkeys[i] = FJ_EMPTY_KEY; trows[i] = ~0ull; }
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_build_kernel(FjPrepBuildArgs
             const u32 c = c0 + u * (PP_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; pp[u] = 0;
             if (c >= nbc) continue;
-            const u32 e = gj_entry(a.rel, b0 + c);
+            const u32 e = fj_chunk_entry(a.rel, b0 + c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.rel.keys[src];
@@ -160,6 +159,7 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_probe_kernel(FjPrepProbeArgs
     u64* tvals = tkeys + PP_TS;                               // (PAYLOAD only)
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
+    // (fj_item_slice of csrc/fj_lds_table_dev.h, kept in place: the helper changes this kernel's code, and it is a hot one)
     u32 p, s_lo, s_hi;
     if (a.items) {
         if (item >= *a.nitems_dev) return;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_probe_kernel(FjPrepProbeArgs
             const u32 c = pc + u * (PP_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; pp[u] = 0;
             if (c >= s_hi) continue;
-            const u32 e = gj_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.probe.keys[src];
@@ -299,6 +299,7 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_group_kernel(FjPrepGroupArgs
     constexpr u64 IDENT = gj_identity<AGG>();
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 item = blockIdx.x;
+    // (fj_item_slice of csrc/fj_lds_table_dev.h, kept in place: the helper changes this kernel's code, and it is a hot one)
     u32 p, s_lo, s_hi;
     if (a.items) {
         if (item >= *a.nitems_dev) return;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(PP_NT, 1) void fj_prep_group_kernel(FjPrepGroupArgs
             const u32 c = pc + u * (PP_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
             kk[u] = 0; if (VALS) vv[VALS ? u : 0] = 0;
             if (c >= s_hi) continue;
-            const u32 e = gj_entry(a.probe, c);
+            const u32 e = fj_chunk_entry(a.probe, c);
             if (off >= FJ_LIST_CNT(e)) continue;
             const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
             kk[u] = a.probe.keys[src];
