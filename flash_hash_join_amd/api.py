@@ -49,6 +49,7 @@ ALGO_RETAIN_BUILD = 0x400000      # FJ_ALGO_RETAIN_BUILD: modifier of ALGO_PROBE
 ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_ORDER - no build side in the call: the context's prepared one is probed (extension)
 ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_ORDER | ALGO_REUSE_BUILD - the outputs are combined into as they are instead of filled first (extension)
 ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_ORDER / ALGO_GROUP_BY - the value column and the values output hold IEEE-754 float64 words: float sum, or float min / max with AGG_MIN / AGG_MAX (extension)
+ALGO_AGG_ALL = 0x4000000          # FJ_ALGO_AGG_ALL: modifier of ALGO_GROUP_BY - the values output holds FOUR planes: row count, sum, minimum and maximum of the value column (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -1389,6 +1390,138 @@ def group_by_max(keys, values, signed=None, float64: bool = False):
     return _group_by_minmax("group_by_max", ALGO_AGG_MAX, keys, values, signed, float64)
 
 
+# ---- extension: group-by with count, sum, min and max of a column in one call (csrc/fj_groupby_multi.hip) -------------------------------
+def _group_by_all(keys, values, flags: int, max_groups: Optional[int] = None):
+    """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL | flags.  planes is a (4, g) array of
+    int64 words where the inputs live - row counts, sums, minima, maxima - each row aligned with group_keys.  flags: a base value
+    (ALGO_SCALAR, ALGO_RADIX), ALGO_AGG_SIGNED or ALGO_AGG_FLOAT.  max_groups: the rows the device buffers hold (None: len(keys));
+    a result beyond it is a ValueError that names g."""
+    global _last
+    keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | flags
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    if _is_torch_tensor(keys) and keys.is_cuda:
+        import torch
+        k, v = _dev_tensor(keys, "keys"), _dev_tensor(values, "values")
+        if v.numel() != k.numel():
+            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
+        n = k.numel()
+        cap = max(1, n if max_groups is None else min(n, max_groups))
+        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
+        ov = torch.empty((4, cap), dtype=torch.int64, device=k.device)
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            rc = L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), v.data_ptr(), n, None, 0, stream, 64, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(),
+                                  cap, ctypes.byref(t))
+            g = int(cnt.value)
+            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
+                raise ValueError(f"group_by_agg: the relation has g = {g} distinct keys, max_groups = {max_groups}")
+            check(rc)
+        _last = t
+        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
+    if _is_torch_tensor(keys):
+        keys = keys.numpy()
+    if _is_torch_tensor(values):
+        values = values.numpy()
+    k, v = _as_u64_host(keys, "keys"), _as_u64_host(values, "values")
+    if v.size != k.size:
+        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        gk, planes = take(ok, g), take(ov, 4 * g).view(np.int64).reshape(4, g)
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
+        raise ValueError(f"group_by_agg: the relation has g = {g} distinct keys, max_groups = {max_groups}")
+    return g, float(sec.value), gk, planes
+
+
+_AGG_NAMES = ("count", "sum", "min", "max", "mean")
+
+
+def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None, float64: bool = False, max_groups: Optional[int] = None):
+    """GROUP BY keys with several aggregates of ONE value column - SELECT k, COUNT(*), SUM(v), MIN(v), MAX(v), AVG(v) ... GROUP BY k:
+    (g, seconds, group_keys, *columns), one column per entry of `aggs`, in that order, every one aligned with group_keys (whose order
+    is unspecified).  ONE library call whatever `aggs` names: the relation goes through the partition passes once, where
+    group_by_count + group_by_sum + group_by_min + group_by_max take four trips and three alignments by key.
+    aggs: a non-empty sequence without repeats of "count", "sum", "min", "max", "mean".  "mean" is sum / count as float64, computed
+    where the data lives, and needs float64=True: the integer sum wraps modulo 2^64, so an integer mean would be silently wrong.
+    signed and float64 follow group_by_min and group_by_sum exactly: signed=None takes the sign from the container (a NumPy uint64
+    column compares unsigned, everything else signed), True / False force it; float64=True reads a floating-point column as numbers
+    (`signed` must stay None, integers raise TypeError).  Dtypes are those of the single forms: counts int64; the sum int64 storage of
+    the words, or float64; min and max the column's own dtype for a NumPy uint64 column compared unsigned, else int64, or float64.
+    max_groups: a caller who knows a bound on the number of groups gets device buffers of min(len(keys), max_groups) rows instead of
+    len(keys) - five arrays of len(keys) words are 40 bytes per input row; a result beyond the bound raises ValueError naming g, and
+    the context stays usable.  NumPy in, NumPy out; torch ROCm tensors / DLPack are read in place on the current stream and every
+    output is a tensor on their device."""
+    if isinstance(aggs, str) or not hasattr(aggs, "__iter__"):
+        raise ValueError(f"group_by_agg: aggs must be a sequence of names from {_AGG_NAMES}, got {aggs!r}")
+    aggs = tuple(aggs)
+    if not aggs:
+        raise ValueError(f"group_by_agg: aggs is empty (name at least one of {_AGG_NAMES})")
+    for a in aggs:
+        if a not in _AGG_NAMES:
+            raise ValueError(f"group_by_agg: unknown aggregate {a!r} (aggs takes {_AGG_NAMES})")
+    if len(set(aggs)) != len(aggs):
+        raise ValueError(f"group_by_agg: aggs repeats a name: {aggs!r}")
+    if "mean" in aggs and not float64:
+        raise ValueError("group_by_agg: 'mean' needs float64=True (the integer sum wraps modulo 2^64: an integer mean would be silently wrong)")
+    if max_groups is not None:
+        if isinstance(max_groups, (bool, np.bool_)) or not isinstance(max_groups, (int, np.integer)) or max_groups < 1:
+            raise ValueError(f"group_by_agg: max_groups must be None or an integer >= 1, got {max_groups!r}")
+        max_groups = int(max_groups)
+    if values is None:
+        raise ValueError("group_by_agg: values is required (group_by_count takes none)")
+    unsigned_out = False
+    if float64:
+        flags = ALGO_AGG_FLOAT
+        values = _float_words("group_by_agg", "values", values, signed)
+    else:
+        if signed is not None and not isinstance(signed, (bool, np.bool_)):
+            raise TypeError(f"group_by_agg: signed must be None, True or False, got {type(signed).__name__}")
+        values = _from_dlpack_if_device(values)
+        if _is_torch_tensor(values):
+            if values.dtype.is_floating_point:
+                raise TypeError(f"group_by_agg: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = str(values.dtype) == "torch.uint64"
+        else:
+            values = np.asarray(values)
+            if values.dtype.kind not in "iub":
+                raise TypeError(f"group_by_agg: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = values.dtype == np.uint64
+        signed = (not unsigned_in) if signed is None else bool(signed)
+        flags = ALGO_AGG_SIGNED if signed else 0
+        unsigned_out = unsigned_in and not signed
+    g, sec, gk, planes = _group_by_all(keys, values, flags, max_groups)
+    cols = []
+    for a in aggs:
+        if a == "count":
+            col = planes[0]
+        elif a == "mean":
+            cnt = planes[0].double() if _is_torch_tensor(planes) else planes[0].astype(np.float64)
+            col = _as_float64(planes[1]) / cnt
+        else:
+            col = planes[_AGG_NAMES.index(a)]
+            if float64:
+                col = _as_float64(col)
+            elif a != "sum" and unsigned_out and isinstance(col, np.ndarray):
+                col = col.view(np.uint64)                    # the column's own dtype; otherwise int64 storage of the words
+        cols.append(col)
+    return (g, sec, gk, *cols)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
@@ -1478,5 +1611,5 @@ ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_rad
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
               "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
-              "factorize", "build_index"]
+              "group_by_agg", "factorize", "build_index"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

@@ -43,6 +43,28 @@ template <int AGG> __device__ __forceinline__ void gj_combine(u64* p, u64 v) {
     else atomicAdd((unsigned long long*)p, (unsigned long long)v);
 }
 
+// one round of a partition's stream for the group-by kernels (csrc/fj_groupby.hip, csrc/fj_groupby_multi.hip): GJ_KPT rows per thread
+// from the chunks [c0, c0 + GJ_ROUND_CHUNKS) of the partition's nbc chunks behind chunk-list entry b0 - the keys, and with POS the word
+// that travels beside each (rel.vals: the value column or the positions the first pass made; flat arrays without one: the row's index).
+// ok: one bit per row that exists.  Loads only: the callers request the next round before they work on this one
+template <bool POS>
+__device__ __forceinline__ void gb_load_round(const FjChunkSet& rel, u32 b0, u32 nbc, u32 c0, u32 tid, u64 (&kk)[GJ_KPT],
+                                              u64 (&vv)[POS ? GJ_KPT : 1], u32& ok) {
+    ok = 0;
+#pragma unroll
+    for (u32 u = 0; u < GJ_KPT; ++u) {
+        const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
+        kk[u] = 0; if (POS) vv[POS ? u : 0] = 0;
+        if (c >= nbc) continue;
+        const u32 e = fj_chunk_entry(rel, b0 + c);
+        if (off >= FJ_LIST_CNT(e)) continue;
+        const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
+        kk[u] = rel.keys[src];
+        if (POS) vv[POS ? u : 0] = rel.vals ? rel.vals[src] : src;                // (zero-pass plan: the flat index IS the position)
+        ok |= 1u << u;
+    }
+}
+
 // ---- the global-table form.  The table is fj_gt_build_first_kernel's, keys only (csrc/fj_join.hip: group-aligned home slot, linear
 // probing, the raw empty key out of band); the accumulators are arrays of capacity + 1 words, the last one the empty key's ----
 __device__ __forceinline__ bool gj_gt_find(const u64* __restrict__ tkeys, u64 cap_mask, u64 key, u64& where) {

@@ -18,6 +18,9 @@
 // Float aggregates (FJ_ALGO_AGG_FLOAT: FJ_GJ_SUM_F / FJ_GJ_MIN_F / FJ_GJ_MAX_F): the value column and the accumulators hold IEEE-754
 // binary64 in the same words - one native f64 LDS atomic add per row, or one integer atomic on the raw bits for min / max (gj_combine).
 //
+// Count, sum, minimum and maximum of the value column in ONE call (FJ_ALGO_AGG_ALL) are csrc/fj_groupby_multi.hip's: a 4096-slot table
+// with four accumulators per slot; the stream's loads (gb_load_round, csrc/fj_group_dev.h) are shared with it.
+//
 // Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition, and its LDS atomics hit
 // one address; fewer than ~256 distinct keys leave CUs idle.  Correct at any distribution (DESIGN.md "Group-by on one relation").
 //
@@ -149,24 +152,6 @@ __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_kernel(FjGroupByArgs a) 
 //             table - no CAS, no atomic - and out_vals[position] = id, one 8-byte scattered store per row.
 // A partition beyond the table skips the last two phases (all threads alike: hdr->full is read behind a barrier) and the host runs the
 // call again on the HBM table, which overwrites every id the other partitions wrote from the abandoned cursor.
-template <bool POS>
-__device__ __forceinline__ void gb_load_round(const FjChunkSet& rel, u32 b0, u32 nbc, u32 c0, u32 tid, u64 (&kk)[GJ_KPT],
-                                              u64 (&vv)[POS ? GJ_KPT : 1], u32& ok) {
-    ok = 0;
-#pragma unroll
-    for (u32 u = 0; u < GJ_KPT; ++u) {
-        const u32 c = c0 + u * (GJ_NT / FJ_CHUNK) + tid / FJ_CHUNK, off = tid % FJ_CHUNK;
-        kk[u] = 0; if (POS) vv[POS ? u : 0] = 0;
-        if (c >= nbc) continue;
-        const u32 e = fj_chunk_entry(rel, b0 + c);
-        if (off >= FJ_LIST_CNT(e)) continue;
-        const u64 src = (u64)FJ_LIST_ID(e) * FJ_CHUNK + off;
-        kk[u] = rel.keys[src];
-        if (POS) vv[POS ? u : 0] = rel.vals ? rel.vals[src] : src;                // (zero-pass plan: the flat index IS the position)
-        ok |= 1u << u;
-    }
-}
-
 __global__ __launch_bounds__(GJ_NT, 1) void fj_group_by_inverse_kernel(FjGroupByArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GbHdr* hdr = reinterpret_cast<GbHdr*>(smem);

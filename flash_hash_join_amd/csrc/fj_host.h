@@ -360,6 +360,10 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
 // (its key's row in d_ok) at the row's position; *out_count = g ----
 int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
              u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid, bool inv = false);
+// ... with FJ_ALGO_AGG_ALL (fj_groupby_multi.hip): d_ov is four planes of cap_out words - count, sum, min, max of bv; kind 0 / 1 / 2: bv
+// holds uint64 / int64 / binary64; cap_out >= 1; g > cap_out fails after the device work with *out_count = g
+int group_by_all(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+                 u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

@@ -183,14 +183,22 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
+    const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
     const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
-                          (gb ? FJ_ALGO_INVERSE : 0);                                                     // a modifier of FJ_ALGO_GROUP_BY: unknown without it
+                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL : 0);                                   // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (many_host || left || anti || full || allc || po || bo)
             return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (pk || np) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (aall) {                                            // four aggregates: *out_vals is 4 * g words, plane-major with stride g
+            if (amin || amax) return set_err("fj_join_host: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_AGG_%s (it holds both the minimum and the maximum)", amin ? "MIN" : "MAX");
+            if (rid || inv) return set_err("fj_join_host: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (out_vals is taken by the four aggregates)", rid ? "ROW_IDS" : "INVERSE");
+            if (asigned && (algo & FJ_ALGO_AGG_FLOAT)) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_AGG_ALL needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (!out_keys || !out_vals || (nb && !bv)) return set_err("fj_join_host: FJ_ALGO_AGG_ALL needs build_vals, out_keys and out_vals (the value column, the g distinct keys and four planes of g words)");
+        }
         if (algo & FJ_ALGO_AGG_FLOAT) {                        // the value column and *out_vals hold IEEE-754 doubles
             if (asigned) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
             if (rid || inv) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_%s (positions and group ids are integers)", rid ? "ROW_IDS" : "INVERSE");
@@ -204,7 +212,7 @@ int fj_join_host(int algo, int bloom, int materialize,
             if (!materialize) return set_err("fj_join_host: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
         }
         if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
-        if (asigned && !amin && !amax) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
+        if (asigned && !amin && !amax && !aall) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if ((amin || amax) && nb && !bv) return set_err("fj_join_host: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
         if (rid && (amin || amax)) return set_err("fj_join_host: FJ_ALGO_ROW_IDS cannot be combined with FJ_ALGO_AGG_%s under FJ_ALGO_GROUP_BY (the first occurrence's position IS the aggregate)", amin ? "MIN" : "MAX");
         if (rid && !materialize) return set_err("fj_join_host: FJ_ALGO_ROW_IDS with FJ_ALGO_GROUP_BY needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
@@ -425,7 +433,26 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hs;
         joined = true;
     }
-    if (gb) {                                                                  // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
+    if (aall) {                                                                // g keys and four planes of g words; the device planes have stride nb
+        void *dok = nullptr, *dov = nullptr;
+        const size_t cap = std::max<size_t>(nb, 1);
+        if (get_buf(c, W_H_OK, cap * 8, &dok) || get_buf(c, W_H_OV, 4 * cap * 8, &dov)) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
+                           &count, (u64*)dok, (u64*)dov, cap, &t)) return 1;
+        const size_t g = (size_t)count;
+        u64* hk = (u64*)malloc(std::max<size_t>(g, 1) * 8);
+        u64* hv = (u64*)malloc(std::max<size_t>(g, 1) * 4 * 8);
+        if (!hk || !hv) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", g); }
+        auto t1 = std::chrono::steady_clock::now();
+        if (g) {
+            HIPCHK(hipMemcpy(hk, dok, g * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy2D(hv, g * 8, dov, cap * 8, g * 8, 4, hipMemcpyDeviceToHost));
+        }
+        d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        *out_keys = hk; *out_vals = hv;
+        joined = true;
+    }
+    if (gb && !aall) {                                                         // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
         void *dok = nullptr, *dov = nullptr;
         const bool ids = inv && out_vals;                                       // (nobody takes the ids: the plain distinct form)
         if (inv && !ids) algo &= ~FJ_ALGO_INVERSE;

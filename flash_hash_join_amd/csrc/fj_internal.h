@@ -440,6 +440,17 @@ hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* o
                                        unsigned long long* cursor, u32* err, hipStream_t s, u64* ids = nullptr);
 // ... and, behind that sweep on the same stream, out_vals[i] = ids[slot of a.bk[i]] for the rows i < min(a.nb, out_capacity)
 hipError_t fj_launch_gt_group_by_inverse(const FjGtArgs& a, const u64* ids, u64* out_vals, u64 out_capacity, hipStream_t s);
+// the four-aggregate form (csrc/fj_groupby_multi.hip; FJ_ALGO_AGG_ALL): as fj_launch_group_by, but out_vals is FOUR planes of
+// out_capacity words - row count, sum, minimum, maximum of rel.vals (required) - and the table takes 3840 distinct keys per partition.
+// kind: the words of the value column as 0 uint64, 1 int64, 2 binary64.  out_capacity >= 1 may be below the number of groups: a row at
+// or beyond it is not written (FJ_ERR_OUTCAP) while the cursor goes on counting
+hipError_t fj_launch_group_by_all(const FjGroupByArgs& a, int kind, hipStream_t s);
+// ... on the global table of fj_launch_gt_build_first (vals = false) over a.bk: acc is four planes of capacity + 1 words holding the
+// identities of count, sum, min and max (the last word of each the empty key's); one thread per row combines into all four, and the
+// sweep compacts the occupied slots into out rows [0, *cursor) of out_keys and of the four planes of out_vals at stride out_capacity
+hipError_t fj_launch_gt_group_by_all_combine(const FjGtArgs& a, int kind, const u64* vals, u64* acc, hipStream_t s);
+hipError_t fj_launch_gt_group_by_all_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
+                                           unsigned long long* cursor, u32* err, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

@@ -687,6 +687,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
+    const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
     const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
     const bool bo_reuse = bo && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // the aggregate join onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD stays unknown)
     const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
@@ -702,11 +703,19 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL);
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
         if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (aall) {                                         // four aggregates in four planes of d_out_vals; any out_capacity >= 1 (g is checked after the device work)
+            if (amin || amax) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_AGG_%s (it holds both the minimum and the maximum)", amin ? "MIN" : "MAX");
+            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the four aggregates)", rid ? "ROW_IDS" : "INVERSE");
+            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs d_build_vals, d_out_keys and d_out_vals (the value column, the g distinct keys and four planes of out_capacity words)");
+            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs an output capacity of at least 1 row (any bound on the number of groups will do)");
+        }
         if (afloat) {                                       // the value column and d_out_vals hold IEEE-754 doubles
             if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
             if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_%s (positions and group ids are integers)", rid ? "ROW_IDS" : "INVERSE");
@@ -721,13 +730,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
             if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_INVERSE needs d_out_keys and d_out_vals (the g distinct keys and the nb group ids that index them)");
         }
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
-        if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
+        if (asigned && !amin && !amax && !aall) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if ((amin || amax) && nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs d_build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
         if (rid && (amin || amax)) return set_err("fj_join_device: FJ_ALGO_ROW_IDS cannot be combined with FJ_ALGO_AGG_%s under FJ_ALGO_GROUP_BY (the first occurrence's position IS the aggregate)", amin ? "MIN" : "MAX");
         if (rid && !materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS with FJ_ALGO_GROUP_BY needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
         if (materialize) {
             if (nb && !d_out_keys) return set_err("fj_join_device: FJ_ALGO_GROUP_BY with materialize = 1 needs d_out_keys (d_out_vals is optional; materialize = 0 returns the number of distinct keys alone)");
-            if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu rows (FJ_ALGO_GROUP_BY: every row may be a group of its own)", out_capacity, nb);
+            if (!aall && out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu rows (FJ_ALGO_GROUP_BY: every row may be a group of its own)", out_capacity, nb);
             if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
         }
         if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
@@ -861,6 +870,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (timings) *timings = t;
         last_timings() = t;
         return 0;
+    }
+    if (aall) {                                             // ... and four aggregates beside it; g beyond the capacity fails with *out_count = g
+        const int rc = group_by_all(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
+                                    afloat ? 2 : asigned ? 1 : 0);
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return rc;
     }
     if (gb) {                                               // one row per distinct key, never a pending result
         if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,

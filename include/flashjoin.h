@@ -296,6 +296,32 @@ extern "C" {
  * usable: no prepared side, another hash_top_bits than the prepared side's, out_capacity < NB.  fj_join_host refuses the combination
  * with and without FJ_ALGO_ACCUMULATE: use fj_join_device on a context of your own. */
 #define FJ_ALGO_ACCUMULATE 0x1000000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY (without it an unknown algo; csrc/fj_groupby_multi.hip): the row count, the sum, the
+ * minimum AND the maximum of the value column in ONE call - SELECT k, COUNT(*), SUM(v), MIN(v), MAX(v) ... GROUP BY k - where the
+ * single forms take four calls, four trips of the relation through the partition passes and an alignment by key.  OR it into `algo`
+ * together with FJ_ALGO_GROUP_BY and a base value (ADAPTIVE, SCALAR or RADIX), optionally with FJ_ALGO_AGG_SIGNED or with
+ * FJ_ALGO_AGG_FLOAT, materialize = 1:
+ *   d_build_keys / d_build_vals   the relation and its value column, nb words each; both required (nb > 0).
+ *   d_out_keys[0 .. g)            the distinct raw keys in an unspecified order, exactly as without the flag.
+ *   d_out_vals                    FOUR planes of out_capacity words each: plane j starts at d_out_vals + j * out_capacity, and row i of
+ *                                 every plane belongs to d_out_keys[i] -
+ *                                   plane 0  the group's row count (uint64)
+ *                                   plane 1  the sum modulo 2^64, or the IEEE-754 binary64 sum with FJ_ALGO_AGG_FLOAT
+ *                                   plane 2  the minimum
+ *                                   plane 3  the maximum
+ *                                 compared as uint64, as int64 with FJ_ALGO_AGG_SIGNED, as numbers with FJ_ALGO_AGG_FLOAT (NaN and
+ *                                 -0.0 / +0.0 as in the float forms of FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX).
+ * *out_count = g.  Every group has a row, so no identity appears.  out_capacity may be ANY value >= 1: a caller who knows a bound on
+ * the number of groups need not hold five arrays of nb words.  When g > out_capacity the call fails AFTER the device work with an error
+ * that states g and the capacity, and *out_count = g; the buffers' contents are then unspecified and the context stays usable.  Nothing at or beyond word
+ * out_capacity of d_out_keys or word 4 * out_capacity of d_out_vals is ever touched.  nb == 0: g = 0, nothing is written.  bloom is
+ * ignored.  Never a pending result for fj_emit_pairs.  fj_timings as for FJ_ALGO_GROUP_BY; fell_back = 1 when a final partition held
+ * more distinct keys than this form's LDS table takes (3840) and the call ran again on the HBM table.  fj_join_host: *out_keys is a
+ * malloc'ed array of g words, *out_vals one of 4 * g words, plane-major with stride g; both pointers are required.
+ * Refused up front, before any device work, in addition to what FJ_ALGO_GROUP_BY refuses: combined with FJ_ALGO_AGG_MIN or
+ * FJ_ALGO_AGG_MAX (it holds both), with FJ_ALGO_ROW_IDS or FJ_ALGO_INVERSE, with FJ_ALGO_AGG_SIGNED and FJ_ALGO_AGG_FLOAT together;
+ * materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity == 0 (and nb > 0); a misaligned output. */
+#define FJ_ALGO_AGG_ALL    0x4000000
 
 typedef struct fj_ctx fj_ctx;
 
