@@ -50,6 +50,7 @@ ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_
 ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_ORDER | ALGO_REUSE_BUILD - the outputs are combined into as they are instead of filled first (extension)
 ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_ORDER / ALGO_GROUP_BY - the value column and the values output hold IEEE-754 float64 words: float sum, or float min / max with AGG_MIN / AGG_MAX (extension)
 ALGO_AGG_ALL = 0x4000000          # FJ_ALGO_AGG_ALL: modifier of ALGO_GROUP_BY - the values output holds FOUR planes: row count, sum, minimum and maximum of the value column (extension)
+ALGO_AGG_ARG = 0x8000000          # FJ_ALGO_AGG_ARG: modifier of ALGO_GROUP_BY with AGG_MIN or AGG_MAX - the values output holds TWO planes: the row index of each group's extreme (smallest index on ties) and the extreme (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
 _ctxs: Dict[int, int] = {}
@@ -1522,6 +1523,114 @@ def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None,
     return (g, sec, gk, *cols)
 
 
+# ---- extension: the row that holds each group's minimum / maximum (csrc/fj_groupby_arg.hip) ------------------------------------------------
+def _group_by_arg(keys, values, flags: int):
+    """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ARG | flags.  planes is a (2, g) array of int64
+    words where the inputs live - the row indices and the extremes - each row aligned with group_keys.  flags: ALGO_AGG_MIN or
+    ALGO_AGG_MAX, a base value (ALGO_SCALAR, ALGO_RADIX), ALGO_AGG_SIGNED or ALGO_AGG_FLOAT."""
+    global _last
+    keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ARG | flags
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    if _is_torch_tensor(keys) and keys.is_cuda:
+        import torch
+        k, v = _dev_tensor(keys, "keys"), _dev_tensor(values, "values")
+        if v.numel() != k.numel():
+            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
+        n = k.numel()
+        cap = max(1, n)
+        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
+        ov = torch.empty((2, cap), dtype=torch.int64, device=k.device)
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), v.data_ptr(), n, None, 0, stream, 64, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(),
+                                   cap, ctypes.byref(t)))
+        _last = t
+        g = int(cnt.value)
+        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
+    if _is_torch_tensor(keys):
+        keys = keys.numpy()
+    if _is_torch_tensor(values):
+        values = values.numpy()
+    k, v = _as_u64_host(keys, "keys"), _as_u64_host(values, "values")
+    if v.size != k.size:
+        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        gk, planes = take(ok, g), take(ov, 2 * g).view(np.int64).reshape(2, g)
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    return g, float(sec.value), gk, planes
+
+
+def _group_by_argext(name: str, flag: int, keys, values, signed, float64: bool, return_values: bool):
+    if values is None:
+        raise ValueError(f"{name}: values is required")
+    unsigned_out = False
+    if float64:
+        flags = flag | ALGO_AGG_FLOAT
+        values = _float_words(name, "values", values, signed)
+    else:
+        if signed is not None and not isinstance(signed, (bool, np.bool_)):
+            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+        values = _from_dlpack_if_device(values)
+        if _is_torch_tensor(values):
+            if values.dtype.is_floating_point:
+                raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = str(values.dtype) == "torch.uint64"
+        else:
+            values = np.asarray(values)
+            if values.dtype.kind not in "iub":
+                raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = values.dtype == np.uint64
+        signed = (not unsigned_in) if signed is None else bool(signed)
+        flags = flag | (ALGO_AGG_SIGNED if signed else 0)
+        unsigned_out = unsigned_in and not signed
+    g, sec, gk, planes = _group_by_arg(keys, values, flags)
+    if not return_values:
+        return g, sec, gk, planes[0]
+    vals = planes[1]
+    if float64:
+        vals = _as_float64(vals)
+    elif unsigned_out and isinstance(vals, np.ndarray):
+        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
+    return g, sec, gk, planes[0], vals
+
+
+def group_by_argmin(keys, values, signed=None, float64: bool = False, return_values: bool = False):
+    """GROUP BY keys and, per key, the ROW that holds MIN(values) - pandas idxmin, SQL arg_min: (g, seconds, group_keys, row_index),
+    row_index int64, one per group, aligned with group_keys (whose order is unspecified): keys[row_index] == group_keys, and
+    values[row_index] are the minima - gather any other column of the relation with it ("the cheapest offer per product": which
+    offer).  Ties: the SMALLEST row index wins (first occurrence), so the result is deterministic.  ONE library call: the relation
+    goes through the partition passes once, where group_by_min + lookup + a second group_by_min over the surviving positions take
+    three trips.  return_values=True appends the minima, with the dtype group_by_min returns.
+    signed and float64 follow group_by_min exactly: signed=None takes the sign from the container (a NumPy uint64 column compares
+    unsigned, everything else signed), True / False force it; float64=True reads a floating-point column as numbers (`signed` must
+    stay None, integers raise TypeError): -0.0 and +0.0 tie, and a group that holds a NaN has an unspecified value and an index in
+    [-1, len(keys)) while every other group is unaffected.  Every group has a row, so every other index is a valid row - also where
+    the minimum equals the aggregate's identity.  NumPy in, NumPy out; torch ROCm tensors / DLPack are read in place on the current
+    stream and every output is a tensor on their device."""
+    return _group_by_argext("group_by_argmin", ALGO_AGG_MIN, keys, values, signed, float64, return_values)
+
+
+def group_by_argmax(keys, values, signed=None, float64: bool = False, return_values: bool = False):
+    """GROUP BY keys and, per key, the row that holds MAX(values): the max form of group_by_argmin.  Ties: the smallest row index,
+    as there ("the latest event per user": the first row with the latest timestamp)."""
+    return _group_by_argext("group_by_argmax", ALGO_AGG_MAX, keys, values, signed, float64, return_values)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
 _HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
@@ -1611,5 +1720,5 @@ ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_rad
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
               "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
-              "group_by_agg", "factorize", "build_index"]
+              "group_by_agg", "group_by_argmin", "group_by_argmax", "factorize", "build_index"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

@@ -364,6 +364,10 @@ int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb,
 // holds uint64 / int64 / binary64; cap_out >= 1; g > cap_out fails after the device work with *out_count = g
 int group_by_all(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
                  u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind);
+// ... with FJ_ALGO_AGG_ARG (fj_groupby_arg.hip): d_ov is two planes of cap_out >= nb words - the smallest row index that holds the
+// minimum (is_max: the maximum) of bv over the key's rows, and that extreme; kind as above
+int group_by_arg(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+                 u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind, bool is_max);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

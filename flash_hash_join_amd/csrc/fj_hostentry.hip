@@ -184,8 +184,9 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
+    const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;
     const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
-                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL : 0);                                   // modifiers of FJ_ALGO_GROUP_BY: unknown without it
+                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG : 0);                                  // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (many_host || left || anti || full || allc || po || bo)
@@ -198,6 +199,14 @@ int fj_join_host(int algo, int bloom, int materialize,
             if (asigned && (algo & FJ_ALGO_AGG_FLOAT)) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
             if (!materialize) return set_err("fj_join_host: FJ_ALGO_AGG_ALL needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
             if (!out_keys || !out_vals || (nb && !bv)) return set_err("fj_join_host: FJ_ALGO_AGG_ALL needs build_vals, out_keys and out_vals (the value column, the g distinct keys and four planes of g words)");
+        }
+        if (aarg) {                                            // the row of each group's extreme: *out_vals is 2 * g words, plane-major with stride g
+            if (aall) return set_err("fj_join_host: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_AGG_ALL (out_vals is taken by the four aggregates)");
+            if (rid || inv) return set_err("fj_join_host: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_%s (out_vals is taken by the row indices and the extremes)", rid ? "ROW_IDS" : "INVERSE");
+            if (amin == amax) return set_err("fj_join_host: FJ_ALGO_AGG_ARG needs exactly one of FJ_ALGO_AGG_MIN and FJ_ALGO_AGG_MAX (%s)", amin ? "both are set: call twice" : "neither is set");
+            if (asigned && (algo & FJ_ALGO_AGG_FLOAT)) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_AGG_ARG needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (!out_keys || !out_vals || (nb && !bv)) return set_err("fj_join_host: FJ_ALGO_AGG_ARG needs build_vals, out_keys and out_vals (the value column, the g distinct keys and two planes of g words)");
         }
         if (algo & FJ_ALGO_AGG_FLOAT) {                        // the value column and *out_vals hold IEEE-754 doubles
             if (asigned) return set_err("fj_join_host: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
@@ -433,26 +442,26 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hs;
         joined = true;
     }
-    if (aall) {                                                                // g keys and four planes of g words; the device planes have stride nb
+    if (aall || aarg) {                                                        // g keys and four (FJ_ALGO_AGG_ARG: two) planes of g words; the device planes have stride nb
         void *dok = nullptr, *dov = nullptr;
-        const size_t cap = std::max<size_t>(nb, 1);
-        if (get_buf(c, W_H_OK, cap * 8, &dok) || get_buf(c, W_H_OV, 4 * cap * 8, &dov)) return 1;
+        const size_t cap = std::max<size_t>(nb, 1), planes = aall ? 4 : 2;
+        if (get_buf(c, W_H_OK, cap * 8, &dok) || get_buf(c, W_H_OV, planes * cap * 8, &dov)) return 1;
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
                            &count, (u64*)dok, (u64*)dov, cap, &t)) return 1;
         const size_t g = (size_t)count;
         u64* hk = (u64*)malloc(std::max<size_t>(g, 1) * 8);
-        u64* hv = (u64*)malloc(std::max<size_t>(g, 1) * 4 * 8);
+        u64* hv = (u64*)malloc(std::max<size_t>(g, 1) * planes * 8);
         if (!hk || !hv) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", g); }
         auto t1 = std::chrono::steady_clock::now();
         if (g) {
             HIPCHK(hipMemcpy(hk, dok, g * 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy2D(hv, g * 8, dov, cap * 8, g * 8, 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy2D(hv, g * 8, dov, cap * 8, g * 8, planes, hipMemcpyDeviceToHost));
         }
         d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
         *out_keys = hk; *out_vals = hv;
         joined = true;
     }
-    if (gb && !aall) {                                                         // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
+    if (gb && !aall && !aarg) {                                                        // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
         void *dok = nullptr, *dov = nullptr;
         const bool ids = inv && out_vals;                                       // (nobody takes the ids: the plain distinct form)
         if (inv && !ids) algo &= ~FJ_ALGO_INVERSE;

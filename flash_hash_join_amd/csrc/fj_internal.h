@@ -451,6 +451,17 @@ hipError_t fj_launch_group_by_all(const FjGroupByArgs& a, int kind, hipStream_t 
 hipError_t fj_launch_gt_group_by_all_combine(const FjGtArgs& a, int kind, const u64* vals, u64* acc, hipStream_t s);
 hipError_t fj_launch_gt_group_by_all_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
                                            unsigned long long* cursor, u32* err, hipStream_t s);
+// the row of each group's extreme (csrc/fj_groupby_arg.hip; FJ_ALGO_AGG_ARG): as fj_launch_group_by, but a.rel.vals holds the rows'
+// POSITIONS (the first pass made them; flat arrays: the index), the kernel gathers vals[position] (nrows words) itself, and out_vals is
+// TWO planes of out_capacity >= nrows words - the smallest row index that holds the minimum (is_max: the maximum) of the key's rows, and
+// that extreme.  kind: the words of vals as 0 uint64, 1 int64, 2 binary64 (compared as numbers)
+hipError_t fj_launch_group_by_arg(const FjGroupByArgs& a, const u64* vals, u64 nrows, int kind, bool is_max, hipStream_t s);
+// ... on the global table of fj_launch_gt_build_first (vals = false) over a.bk: ext and pos are planes of capacity + 1 words, ext
+// holding every slot's extreme (fj_launch_gt_group_by_combine), pos all ones.  One thread per row offers its index to pos[slot] where
+// vals[i] equals ext[slot]; the sweep compacts the occupied slots into out rows [0, *cursor) of out_keys and of the two planes of out_vals
+hipError_t fj_launch_gt_group_by_arg_resolve(const FjGtArgs& a, int kind, const u64* vals, const u64* ext, u64* pos, hipStream_t s);
+hipError_t fj_launch_gt_group_by_arg_sweep(const FjGtArgs& a, const u64* ext, const u64* pos, u64* out_keys, u64* out_vals, u64 out_capacity,
+                                           unsigned long long* cursor, u32* err, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

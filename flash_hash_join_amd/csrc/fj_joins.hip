@@ -688,6 +688,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
+    const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
     const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
     const bool bo_reuse = bo && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // the aggregate join onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD stays unknown)
     const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
@@ -703,7 +704,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG);
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
@@ -715,6 +716,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
             if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
             if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs d_build_vals, d_out_keys and d_out_vals (the value column, the g distinct keys and four planes of out_capacity words)");
             if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs an output capacity of at least 1 row (any bound on the number of groups will do)");
+        }
+        if (aarg) {                                         // the row of each group's extreme: d_out_vals is two planes, the row index and the extreme
+            if (aall) return set_err("fj_join_device: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_AGG_ALL (d_out_vals is taken by the four aggregates)");
+            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the row indices and the extremes)", rid ? "ROW_IDS" : "INVERSE");
+            if (amin == amax) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs exactly one of FJ_ALGO_AGG_MIN and FJ_ALGO_AGG_MAX (%s)", amin ? "both are set: call twice" : "neither is set");
+            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs d_build_vals, d_out_keys and d_out_vals (the value column, the g distinct keys and two planes of out_capacity words)");
         }
         if (afloat) {                                       // the value column and d_out_vals hold IEEE-754 doubles
             if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
@@ -878,6 +887,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (timings) *timings = t;
         last_timings() = t;
         return rc;
+    }
+    if (aarg) {                                             // ... or the row index and the extreme beside it (out_capacity >= nb was checked)
+        if (group_by_arg(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
+                         afloat ? 2 : asigned ? 1 : 0, amax)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
     }
     if (gb) {                                               // one row per distinct key, never a pending result
         if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,

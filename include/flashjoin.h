@@ -322,6 +322,29 @@ extern "C" {
  * FJ_ALGO_AGG_MAX (it holds both), with FJ_ALGO_ROW_IDS or FJ_ALGO_INVERSE, with FJ_ALGO_AGG_SIGNED and FJ_ALGO_AGG_FLOAT together;
  * materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity == 0 (and nb > 0); a misaligned output. */
 #define FJ_ALGO_AGG_ALL    0x4000000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY (without it an unknown algo; csrc/fj_groupby_arg.hip): the ROW that holds each group's
+ * minimum or maximum - pandas idxmin / idxmax, SQL arg_min / arg_max - so that the caller can gather the row's other columns.  OR it
+ * into `algo` together with FJ_ALGO_GROUP_BY, a base value (ADAPTIVE, SCALAR or RADIX) and exactly one of FJ_ALGO_AGG_MIN and
+ * FJ_ALGO_AGG_MAX, optionally with FJ_ALGO_AGG_SIGNED or with FJ_ALGO_AGG_FLOAT, materialize = 1:
+ *   d_build_keys / d_build_vals   the relation and its value column, nb words each; both required (nb > 0).
+ *   d_out_keys[0 .. g)            the distinct raw keys in an unspecified order, exactly as without the flag.
+ *   d_out_vals                    TWO planes of out_capacity words each, row i of both belonging to d_out_keys[i] -
+ *                                   plane 0  (d_out_vals)                 the row index: the SMALLEST i with d_build_vals[i] equal to
+ *                                            the extreme of the key's rows, for the minimum and the maximum alike (first occurrence)
+ *                                   plane 1  (d_out_vals + out_capacity)  that extreme, what FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX return
+ *                                 compared as uint64, as int64 with FJ_ALGO_AGG_SIGNED, as numbers with FJ_ALGO_AGG_FLOAT: -0.0 and
+ *                                 +0.0 tie (the smaller index wins; which zero plane 1 holds is unspecified); a group that holds a
+ *                                 NaN has an unspecified extreme and an index that is a row of the relation or all ones, and no other
+ *                                 group is affected.
+ * *out_count = g.  Every group has a row, so every index is a row of the relation - also where the extreme equals the aggregate's
+ * identity: no counts are needed to tell such a group apart.  out_capacity >= nb, as for the single forms.  nb == 0: g = 0, nothing is
+ * written.  bloom is ignored.  Never a pending result for fj_emit_pairs.  fj_timings as for FJ_ALGO_GROUP_BY; fell_back = 1 when a
+ * final partition held more distinct keys than this form's LDS table takes (3840) and the call ran again on the HBM table.
+ * fj_join_host: *out_keys is a malloc'ed array of g words, *out_vals one of 2 * g words, plane-major with stride g; both required.
+ * Refused up front, before any device work, in addition to what FJ_ALGO_GROUP_BY refuses: without FJ_ALGO_AGG_MIN and FJ_ALGO_AGG_MAX
+ * or with both; combined with FJ_ALGO_ROW_IDS, FJ_ALGO_INVERSE or FJ_ALGO_AGG_ALL, with FJ_ALGO_AGG_SIGNED and FJ_ALGO_AGG_FLOAT
+ * together; materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity < nb; a misaligned output. */
+#define FJ_ALGO_AGG_ARG    0x8000000
 
 typedef struct fj_ctx fj_ctx;
 
