@@ -50,6 +50,7 @@ ALGO_REUSE_BUILD = 0x800000       # FJ_ALGO_REUSE_BUILD: modifier of ALGO_PROBE_
 ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_ORDER | ALGO_REUSE_BUILD - the outputs are combined into as they are instead of filled first (extension)
 ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_ORDER / ALGO_GROUP_BY - the value column and the values output hold IEEE-754 float64 words: float sum, or float min / max with AGG_MIN / AGG_MAX (extension)
 ALGO_AGG_ALL = 0x4000000          # FJ_ALGO_AGG_ALL: modifier of ALGO_GROUP_BY - the values output holds FOUR planes: row count, sum, minimum and maximum of the value column (extension)
+ALGO_AGG_MERGE = 0x10000000       # FJ_ALGO_AGG_MERGE: modifier of ALGO_GROUP_BY | ALGO_AGG_ALL - the input rows are PARTIAL aggregates (a key and four planes: count, sum, min, max) and the rows of one key are combined (extension)
 ALGO_AGG_ARG = 0x8000000          # FJ_ALGO_AGG_ARG: modifier of ALGO_GROUP_BY with AGG_MIN or AGG_MAX - the values output holds TWO planes: the row index of each group's extreme (smallest index on ties) and the extreme (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
@@ -1452,6 +1453,50 @@ def _group_by_all(keys, values, flags: int, max_groups: Optional[int] = None):
 _AGG_NAMES = ("count", "sum", "min", "max", "mean")
 
 
+def _check_aggs(name: str, aggs, float64: bool) -> tuple:
+    """the `aggs` argument of group_by_agg and GroupByAccumulator.result as a tuple of names, or the ValueError that says what is wrong"""
+    if isinstance(aggs, str) or not hasattr(aggs, "__iter__"):
+        raise ValueError(f"{name}: aggs must be a sequence of names from {_AGG_NAMES}, got {aggs!r}")
+    aggs = tuple(aggs)
+    if not aggs:
+        raise ValueError(f"{name}: aggs is empty (name at least one of {_AGG_NAMES})")
+    for a in aggs:
+        if a not in _AGG_NAMES:
+            raise ValueError(f"{name}: unknown aggregate {a!r} (aggs takes {_AGG_NAMES})")
+    if len(set(aggs)) != len(aggs):
+        raise ValueError(f"{name}: aggs repeats a name: {aggs!r}")
+    if "mean" in aggs and not float64:
+        raise ValueError(f"{name}: 'mean' needs float64=True (the integer sum wraps modulo 2^64: an integer mean would be silently wrong)")
+    return aggs
+
+
+def _check_max_groups(name: str, max_groups) -> Optional[int]:
+    if max_groups is None:
+        return None
+    if isinstance(max_groups, (bool, np.bool_)) or not isinstance(max_groups, (int, np.integer)) or max_groups < 1:
+        raise ValueError(f"{name}: max_groups must be None or an integer >= 1, got {max_groups!r}")
+    return int(max_groups)
+
+
+def _agg_columns(planes, aggs: tuple, float64: bool, unsigned_out: bool) -> list:
+    """the columns `aggs` names, from the (4, g) planes of words - counts, sums, minima, maxima - with group_by_agg's dtypes"""
+    cols = []
+    for a in aggs:
+        if a == "count":
+            col = planes[0]
+        elif a == "mean":
+            cnt = planes[0].double() if _is_torch_tensor(planes) else planes[0].astype(np.float64)
+            col = _as_float64(planes[1]) / cnt
+        else:
+            col = planes[_AGG_NAMES.index(a)]
+            if float64:
+                col = _as_float64(col)
+            elif a != "sum" and unsigned_out and isinstance(col, np.ndarray):
+                col = col.view(np.uint64)                    # the column's own dtype; otherwise int64 storage of the words
+        cols.append(col)
+    return cols
+
+
 def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None, float64: bool = False, max_groups: Optional[int] = None):
     """GROUP BY keys with several aggregates of ONE value column - SELECT k, COUNT(*), SUM(v), MIN(v), MAX(v), AVG(v) ... GROUP BY k:
     (g, seconds, group_keys, *columns), one column per entry of `aggs`, in that order, every one aligned with group_keys (whose order
@@ -1467,22 +1512,8 @@ def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None,
     len(keys) - five arrays of len(keys) words are 40 bytes per input row; a result beyond the bound raises ValueError naming g, and
     the context stays usable.  NumPy in, NumPy out; torch ROCm tensors / DLPack are read in place on the current stream and every
     output is a tensor on their device."""
-    if isinstance(aggs, str) or not hasattr(aggs, "__iter__"):
-        raise ValueError(f"group_by_agg: aggs must be a sequence of names from {_AGG_NAMES}, got {aggs!r}")
-    aggs = tuple(aggs)
-    if not aggs:
-        raise ValueError(f"group_by_agg: aggs is empty (name at least one of {_AGG_NAMES})")
-    for a in aggs:
-        if a not in _AGG_NAMES:
-            raise ValueError(f"group_by_agg: unknown aggregate {a!r} (aggs takes {_AGG_NAMES})")
-    if len(set(aggs)) != len(aggs):
-        raise ValueError(f"group_by_agg: aggs repeats a name: {aggs!r}")
-    if "mean" in aggs and not float64:
-        raise ValueError("group_by_agg: 'mean' needs float64=True (the integer sum wraps modulo 2^64: an integer mean would be silently wrong)")
-    if max_groups is not None:
-        if isinstance(max_groups, (bool, np.bool_)) or not isinstance(max_groups, (int, np.integer)) or max_groups < 1:
-            raise ValueError(f"group_by_agg: max_groups must be None or an integer >= 1, got {max_groups!r}")
-        max_groups = int(max_groups)
+    aggs = _check_aggs("group_by_agg", aggs, float64)
+    max_groups = _check_max_groups("group_by_agg", max_groups)
     if values is None:
         raise ValueError("group_by_agg: values is required (group_by_count takes none)")
     unsigned_out = False
@@ -1506,21 +1537,7 @@ def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None,
         flags = ALGO_AGG_SIGNED if signed else 0
         unsigned_out = unsigned_in and not signed
     g, sec, gk, planes = _group_by_all(keys, values, flags, max_groups)
-    cols = []
-    for a in aggs:
-        if a == "count":
-            col = planes[0]
-        elif a == "mean":
-            cnt = planes[0].double() if _is_torch_tensor(planes) else planes[0].astype(np.float64)
-            col = _as_float64(planes[1]) / cnt
-        else:
-            col = planes[_AGG_NAMES.index(a)]
-            if float64:
-                col = _as_float64(col)
-            elif a != "sum" and unsigned_out and isinstance(col, np.ndarray):
-                col = col.view(np.uint64)                    # the column's own dtype; otherwise int64 storage of the words
-        cols.append(col)
-    return (g, sec, gk, *cols)
+    return (g, sec, gk, *_agg_columns(planes, aggs, float64, unsigned_out))
 
 
 # ---- extension: the row that holds each group's minimum / maximum (csrc/fj_groupby_arg.hip) ------------------------------------------------
@@ -1631,8 +1648,354 @@ def group_by_argmax(keys, values, signed=None, float64: bool = False, return_val
     return _group_by_argext("group_by_argmax", ALGO_AGG_MAX, keys, values, signed, float64, return_values)
 
 
+# ---- extension: merging partial group-by results (csrc/fj_groupby_merge.hip) ---------------------------------------------------------------
+def _group_by_merge(k, planes, flags: int, max_groups: Optional[int] = None):
+    """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_MERGE | flags.  k: the n keys
+    of the partial rows, planes: their (4, n) words - counts, sums, minima, maxima - both NumPy (uint64) or both contiguous torch.int64
+    on one device.  Returns what _group_by_all returns.  flags: a base value, ALGO_AGG_SIGNED or ALGO_AGG_FLOAT."""
+    global _last
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | ALGO_AGG_MERGE | flags
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    if _is_torch_tensor(k):
+        import torch
+        n = k.numel()
+        if tuple(planes.shape) != (4, n) or not planes.is_contiguous() or planes.device != k.device:
+            raise ValueError(f"_group_by_merge: planes must be a contiguous (4, {n}) tensor on the keys' device")
+        cap = max(1, n if max_groups is None else min(n, max_groups))
+        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
+        ov = torch.empty((4, cap), dtype=torch.int64, device=k.device)
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            rc = L.fj_join_device(ctx, algo, 0, 1, k.data_ptr() if n else None, planes.data_ptr() if n else None, n, None, 0, stream, 64,
+                                  ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(), cap, ctypes.byref(t))
+            g = int(cnt.value)
+            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
+                raise ValueError(f"group_by_merge: the partial rows hold g = {g} distinct keys, max_groups = {max_groups}")
+            check(rc)
+        _last = t
+        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
+    n = k.size
+    if planes.shape != (4, n):
+        raise ValueError(f"_group_by_merge: planes must be a (4, {n}) array")
+    k, v = _as_u64_host(k, "keys"), _as_u64_host(planes, "planes")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, n, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        gk, out = take(ok, g), take(ov, 4 * g).view(np.int64).reshape(4, g)
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
+        raise ValueError(f"group_by_merge: the partial rows hold g = {g} distinct keys, max_groups = {max_groups}")
+    return g, float(sec.value), gk, out
+
+
+def _is_array(x: Any) -> bool:
+    return isinstance(x, np.ndarray) or _is_torch_tensor(x) or hasattr(x, "__dlpack_device__")
+
+
+def _parts(x: Any) -> list:
+    """one array, or a sequence of arrays (the partials of several batches), as a list of arrays"""
+    if isinstance(x, (list, tuple)) and (not x or all(_is_array(p) for p in x)):
+        return [_from_dlpack_if_device(p) for p in x]
+    return [_from_dlpack_if_device(x)]
+
+
+def _container(x: Any):
+    """where an array lives: "numpy", or ("device", index).  A torch tensor in host memory counts as NumPy, as everywhere"""
+    if _is_torch_tensor(x) and x.is_cuda:
+        import torch
+        return ("device", x.device.index if x.device.index is not None else torch.cuda.current_device())
+    return "numpy"
+
+
+def _same_container(name: str, arrays, want=None):
+    """the one container of all `arrays` (and `want`, where given), or the TypeError"""
+    for a in arrays:
+        c = _container(a)
+        if want is None:
+            want = c
+        if c != want:
+            raise TypeError(f"{name}: every argument must be of one kind and on one device, got {want} and {c}")
+    return want or "numpy"
+
+
+def _word_column(name: str, what: str, col: Any, signed: Any, float64: bool):
+    """(words, signed, unsigned_in): a sum / min / max column as 8-byte words in its container, under the rules of group_by_min -
+    signed=None takes the sign from the container - and of float64=True"""
+    if float64:
+        return _float_words(name, what, col, signed), False, False
+    if signed is not None and not isinstance(signed, (bool, np.bool_)):
+        raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+    if _is_torch_tensor(col):
+        if col.dtype.is_floating_point:
+            raise TypeError(f"{name}: {what} must be 64-bit integers, got {col.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+        unsigned_in = str(col.dtype) == "torch.uint64"
+    else:
+        col = np.asarray(col)
+        if col.dtype.kind not in "iub":
+            raise TypeError(f"{name}: {what} must be integers, got dtype {col.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+        unsigned_in = col.dtype == np.uint64
+    return col, ((not unsigned_in) if signed is None else bool(signed)), unsigned_in
+
+
+def _count_column(name: str, col: Any):
+    if not _is_torch_tensor(col):
+        col = np.asarray(col)
+    if str(col.dtype).replace("torch.", "") not in ("int64", "uint64"):
+        raise TypeError(f"{name}: counts must be int64 or uint64, got {col.dtype}")
+    return col
+
+
+def _pack_partials(name: str, parts, container):
+    """parts: [(keys, counts, sums, mins, maxs)] of words in one container -> (key buffer of n, (4, n) buffer): ONE copy of every
+    word into the layout the C ABI reads"""
+    n = sum(int(p[0].shape[0]) for p in parts)
+    if container == "numpy":
+        k, planes = np.empty(n, np.uint64), np.empty((4, n), np.uint64)
+        at = 0
+        for p in parts:
+            m = p[0].shape[0]
+            k[at:at + m] = _as_u64_host(p[0], "keys")
+            for q in range(4):
+                planes[q, at:at + m] = _as_u64_host(p[1 + q], name)
+            at += m
+        return k, planes
+    import torch
+    words = lambda t: t.reshape(-1).view(torch.int64) if t.dtype == torch.uint64 else t.reshape(-1)
+    dev = torch.device("cuda", container[1])
+    k, planes = torch.empty(n, dtype=torch.int64, device=dev), torch.empty((4, n), dtype=torch.int64, device=dev)
+    if parts:                                                # one torch.cat per column, whatever the number of batches
+        torch.cat([words(_dev_tensor(p[0], "keys")) for p in parts], out=k)
+        for q in range(4):
+            torch.cat([words(_dev_tensor(p[1 + q], name)) for p in parts], out=planes[q])
+    return k, planes
+
+
+def _partial_words(name: str, keys, counts, sums, mins, maxs, signed, float64: bool):
+    """the five arguments of group_by_merge, checked: ([(keys, counts, sums, mins, maxs)] as words, container, signed, unsigned_out)"""
+    cols = [_parts(x) for x in (keys, counts, sums, mins, maxs)]
+    names = ("keys", "counts", "sums", "mins", "maxs")
+    for nm, c in zip(names[1:], cols[1:]):
+        if len(c) != len(cols[0]):
+            raise ValueError(f"{name}: {nm} has {len(c)} arrays, keys has {len(cols[0])} (one of each per batch)")
+    if float64 and signed is not None:
+        raise TypeError(f"{name}: signed must be None with float64=True (a float64 carries its own sign), got {signed!r}")
+    container = _same_container(name, [a for c in cols for a in c if _is_array(a)])
+    parts, resolved, unsigned_out = [], None, False
+    for i in range(len(cols[0])):
+        k, c = cols[0][i], _count_column(name, cols[1][i])
+        if not _is_array(k):
+            k = _as_u64_host(k, "keys")
+        row = [k, c]
+        for nm, col in zip(names[2:], (cols[2][i], cols[3][i], cols[4][i])):
+            w, sg, unsigned_in = _word_column(name, nm, col, signed, float64)
+            if nm == "mins" and resolved is None:
+                resolved, unsigned_out = sg, unsigned_in and not sg
+            row.append(w)
+        lens = [int(np.prod(a.shape)) for a in row]
+        for nm, ln in zip(names[1:], lens[1:]):
+            if ln != lens[0]:
+                raise ValueError(f"{name}: {nm} has {ln} elements, keys has {lens[0]}")
+        parts.append(tuple(a.reshape(-1) for a in row))
+    return parts, container, bool(resolved), unsigned_out
+
+
+def group_by_merge(keys, counts, sums, mins, maxs, signed=None, float64: bool = False, max_groups: Optional[int] = None):
+    """Merge PARTIAL group-by results - what group_by_agg returned for every batch of a column that arrives in morsels, for every shard
+    of a relation, or Index.group_* with its counts: (g, seconds, group_keys, counts, sums, mins, maxs), one row per distinct key of
+    `keys`, the rows that share a key combined - the counts and the sums add (modulo 2^64; float64 sums in an unspecified order), the
+    minima and maxima take the extreme.  The order of group_keys is unspecified; the four columns are aligned with it.
+    Every argument is one array, or a sequence of arrays - one per batch: they are copied ONCE into one key buffer and one (4, n)
+    buffer, and the merge is ONE library call, where factorize of the concatenated keys plus four scatters over the codes takes a trip
+    through the partition passes and four scattered passes.  Containers, dtypes and errors follow group_by_agg: NumPy arrays or torch
+    ROCm tensors / DLPack, all of one kind and on one device (TypeError otherwise); counts int64 or uint64; sums, mins and maxs integer
+    words, or floating point with float64=True (an integer column is a TypeError then); signed=None takes the sign from the container
+    of `mins` as group_by_min does (a NumPy uint64 column compares unsigned, everything else signed), True / False force it.
+    Columns of unequal length are a ValueError.  A row with count 0 whose sum, min and max hold the aggregates' identities (what
+    Index.group_* leaves for a key without a partner) is legal: its key is a group of the result, with count 0 unless another row of
+    that key says otherwise.  max_groups bounds the device buffers as in group_by_agg: a result beyond it raises ValueError naming g
+    and the context stays usable.  No rows: g = 0 and empty arrays."""
+    max_groups = _check_max_groups("group_by_merge", max_groups)
+    parts, container, signed, unsigned_out = _partial_words("group_by_merge", keys, counts, sums, mins, maxs, signed, float64)
+    k, planes = _pack_partials("group_by_merge", parts, container)
+    flags = ALGO_AGG_FLOAT if float64 else (ALGO_AGG_SIGNED if signed else 0)
+    if k.shape[0] == 0:
+        g, sec, gk, out = 0, 0.0, k, (planes.view(np.int64) if container == "numpy" else planes)
+    else:
+        g, sec, gk, out = _group_by_merge(k, planes, flags, max_groups)
+    return (g, sec, gk, *_agg_columns(out, ("count", "sum", "min", "max"), float64, unsigned_out))
+
+
+class GroupByAccumulator:
+    """A running GROUP BY keys with COUNT, SUM, MIN and MAX of one value column over batches whose key set is not known beforehand:
+
+        acc = GroupByAccumulator()
+        for keys, values in batches: acc.update(keys, values)
+        g, seconds, group_keys, counts, sums, mins, maxs = acc.result()
+
+    update() groups the batch with group_by_agg (all four aggregates) and keeps the partial result; once the pending partial rows reach
+    max(rows of the merged state, compact_at) the state and all pending partials become a new state with ONE group_by_merge.  A merge
+    therefore handles at most twice the rows that arrived since the last one, and the total merge work stays within a constant factor
+    of the partial rows seen, however many batches there are.  compact_at is a policy constant, not a measured optimum: it keeps
+    small batches from merging one by one (tests set it small).
+    signed, float64 and max_groups are group_by_agg's and hold for every batch.  The accumulator keeps the container kind and the
+    device of its first batch, and the signedness that batch resolved to: a later batch of another kind, device or signedness is a
+    TypeError and leaves the accumulator as it was.  merge() takes another accumulator or a (keys, counts, sums, mins, maxs) tuple - a
+    shard's result, or an Index.group_* result with its counts (rows of count 0 included).  result() compacts and returns
+    (g, seconds, group_keys, *columns) exactly as group_by_agg does; with no batch g = 0.  close() drops the buffers; a context manager."""
+
+    def __init__(self, signed=None, float64: bool = False, max_groups: Optional[int] = None, compact_at: int = 65536):
+        if float64 and signed is not None:
+            raise TypeError(f"GroupByAccumulator: signed must be None with float64=True (a float64 carries its own sign), got {signed!r}")
+        if signed is not None and not isinstance(signed, (bool, np.bool_)):
+            raise TypeError(f"GroupByAccumulator: signed must be None, True or False, got {type(signed).__name__}")
+        if isinstance(compact_at, (bool, np.bool_)) or not isinstance(compact_at, (int, np.integer)) or compact_at < 1:
+            raise ValueError(f"GroupByAccumulator: compact_at must be an integer >= 1, got {compact_at!r}")
+        self._signed_arg, self._float64 = signed, bool(float64)
+        self._max_groups = _check_max_groups("GroupByAccumulator", max_groups)
+        self._compact_at = int(compact_at)
+        self._container = None                               # of the first batch; with it the resolved signedness
+        self._signed = self._unsigned_out = False
+        self._state = None                                   # (keys, (4, g) planes) of distinct keys, as words
+        self._pending: list = []                             # (keys, counts, sums, mins, maxs) partials not merged yet, as words
+        self._pending_rows = self._rows_seen = self._merges = 0
+        self._closed = False
+
+    # -- bookkeeping ---------------------------------------------------------------------------------------------------------------
+    @property
+    def num_groups(self) -> int:
+        """the groups of the merged state (after the last compaction; the pending partials are not counted)"""
+        return 0 if self._state is None else int(self._state[0].shape[0])
+
+    @property
+    def pending_rows(self) -> int:
+        return self._pending_rows
+
+    @property
+    def rows_seen(self) -> int:
+        """the input rows behind everything taken so far: the rows of every batch, the counts of every merged partial"""
+        return self._rows_seen
+
+    @property
+    def merges(self) -> int:
+        """the library merge calls so far"""
+        return self._merges
+
+    def close(self) -> None:
+        self._state, self._pending, self._pending_rows, self._closed = None, [], 0, True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _open(self, who: str) -> None:
+        if self._closed:
+            raise ValueError(f"{who}: the accumulator is closed")
+
+    def _agree(self, who: str, container, signed: bool) -> None:
+        """a later input must have the container and the signedness the first one fixed (checked before anything is kept)"""
+        if self._container is None:
+            return
+        if container != self._container:
+            raise TypeError(f"{who}: this accumulator holds {self._container} data, got {container} (one container kind and one device)")
+        elif signed != self._signed:
+            raise TypeError(f"{who}: this accumulator compares {'signed' if self._signed else 'unsigned'}, the input resolves to "
+                            f"{'signed' if signed else 'unsigned'} (pass signed= to the constructor)")
+
+    def _take(self, parts, rows: int, container, signed: bool, unsigned_out: bool) -> float:
+        if self._container is None:
+            self._container, self._signed, self._unsigned_out = container, signed, unsigned_out
+        self._pending.extend(parts)
+        self._pending_rows += sum(int(p[0].shape[0]) for p in parts)
+        self._rows_seen += rows
+        return self._compact() if self._pending_rows >= max(self.num_groups, self._compact_at) else 0.0
+
+    def _compact(self) -> float:
+        """state + pending -> state with one group_by_merge; seconds of that call (nothing pending: no call)"""
+        if not self._pending:
+            return 0.0
+        k, planes = _pack_partials("GroupByAccumulator", self._partials(), self._container)
+        sec = 0.0
+        if k.shape[0]:
+            flags = ALGO_AGG_FLOAT if self._float64 else (ALGO_AGG_SIGNED if self._signed else 0)
+            g, sec, k, planes = _group_by_merge(k, planes, flags, self._max_groups)
+            self._merges += 1
+        self._state = (k, planes)
+        self._pending, self._pending_rows = [], 0
+        return sec
+
+    def _partials(self) -> list:
+        """the merged state and the pending partials as (keys, counts, sums, mins, maxs) rows"""
+        return ([(self._state[0], *self._state[1])] if self._state is not None else []) + self._pending
+
+    # -- input ---------------------------------------------------------------------------------------------------------------------
+    def update(self, keys, values):
+        """One batch: (g_batch, seconds) - the batch's distinct keys, and the device time of its group_by_agg plus that of the merge
+        it set off, if any."""
+        self._open("GroupByAccumulator.update")
+        keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
+        if values is None:
+            raise ValueError("GroupByAccumulator.update: values is required")
+        container = _same_container("GroupByAccumulator.update", [a for a in (keys, values) if _is_array(a)])
+        _, signed, unsigned_in = _word_column("GroupByAccumulator.update", "values", values, self._signed_arg, self._float64)
+        self._agree("GroupByAccumulator.update", container, signed)
+        g, sec, gk, c, s, mn, mx = group_by_agg(keys, values, signed=self._signed_arg, float64=self._float64, max_groups=self._max_groups)
+        words = _as_float64_words if self._float64 else (lambda a: a)
+        rows = int(np.prod(keys.shape)) if _is_array(keys) else len(keys)
+        return g, sec + self._take([(gk, c, words(s), words(mn), words(mx))], rows, container, signed, unsigned_in and not signed)
+
+    def merge(self, other):
+        """Another accumulator's groups (it stays as it is), or a (keys, counts, sums, mins, maxs) tuple of partial rows - every item
+        one array or a sequence of arrays, as for group_by_merge: seconds of the merge this set off, 0.0 if none."""
+        self._open("GroupByAccumulator.merge")
+        if isinstance(other, GroupByAccumulator):
+            other._open("GroupByAccumulator.merge")
+            if other._float64 != self._float64:
+                raise TypeError("GroupByAccumulator.merge: one accumulator is float64, the other is not")
+            if other._container is None:
+                return 0.0
+            self._agree("GroupByAccumulator.merge", other._container, other._signed)
+            return self._take(other._partials(), other._rows_seen, other._container, other._signed, other._unsigned_out)
+        if not isinstance(other, (tuple, list)) or len(other) != 5:
+            raise TypeError("GroupByAccumulator.merge: another GroupByAccumulator, or a (keys, counts, sums, mins, maxs) tuple")
+        parts, container, signed, unsigned_out = _partial_words("GroupByAccumulator.merge", *other, self._signed_arg, self._float64)
+        self._agree("GroupByAccumulator.merge", container, signed)
+        return self._take(parts, sum(int(p[1].sum()) for p in parts), container, signed, unsigned_out)
+
+    # -- output --------------------------------------------------------------------------------------------------------------------
+    def result(self, aggs=("count", "sum", "min", "max")):
+        """(g, seconds, group_keys, *columns) as group_by_agg returns them, one column per name in aggs ("mean" only with float64=True);
+        seconds: the merge this call made, 0.0 when everything was merged already.  The accumulator goes on taking batches."""
+        self._open("GroupByAccumulator.result")
+        aggs = _check_aggs("GroupByAccumulator.result", aggs, self._float64)
+        sec = self._compact()
+        k, planes = self._state if self._state is not None else (np.empty(0, np.uint64), np.empty((4, 0), np.int64))
+        if isinstance(planes, np.ndarray):
+            planes = planes.view(np.int64)
+        return (int(k.shape[0]), sec, k, *_agg_columns(planes, aggs, self._float64, self._unsigned_out))
+
+
+def group_by_accumulator(signed=None, float64: bool = False, max_groups: Optional[int] = None, compact_at: int = 65536) -> GroupByAccumulator:
+    """GroupByAccumulator(...), under the naming of build_index"""
+    return GroupByAccumulator(signed=signed, float64=float64, max_groups=max_groups, compact_at=compact_at)
+
+
 # ---- extension: gather maps (row positions instead of keys and values) ------------------------------------------------------
-_HOW = {"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
+_HOW ={"inner": 0, "left": ALGO_LEFT_OUTER, "anti": ALGO_ANTI, "full": ALGO_FULL_OUTER, "semi": 0}
 
 
 def join_indices(build_keys, probe_keys, how: str = "inner", many_to_many: bool = False, duplicates: str = "first"):
@@ -1720,5 +2083,6 @@ ALIASES = ["flash_join", "flash_join_radix", "flash_join_bloom", "flash_join_rad
 EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_join_count", "join_indices",
               "full_join", "semi_join", "semi_join_count", "lookup", "isin", "lookup_indices", "group_join_count", "group_join_sum",
               "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
-              "group_by_agg", "group_by_argmin", "group_by_argmax", "factorize", "build_index"]
+              "group_by_agg", "group_by_argmin", "group_by_argmax", "group_by_merge", "GroupByAccumulator", "group_by_accumulator", "factorize",
+              "build_index"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

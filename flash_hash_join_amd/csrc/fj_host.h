@@ -368,6 +368,10 @@ int group_by_all(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t
 // minimum (is_max: the maximum) of bv over the key's rows, and that extreme; kind as above
 int group_by_arg(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
                  u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind, bool is_max);
+// ... with FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_MERGE (fj_groupby_merge.hip): bk holds nb PARTIAL rows and bv their four planes of nb words -
+// count, sum, min, max; d_ov is four planes of cap_out words, the rows of one key combined; kind and cap_out as for group_by_all
+int group_by_merge(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+                   u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

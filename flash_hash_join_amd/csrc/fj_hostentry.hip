@@ -185,10 +185,24 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;
+    const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;            // partial rows in: build_vals is FOUR planes of nb words
+    if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
+        return set_err("fj_join_host: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo);
     const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
-                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG : 0);                                  // modifiers of FJ_ALGO_GROUP_BY: unknown without it
+                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
+        if (amerge) {                                          // FJ_ALGO_AGG_ALL's refusals under this flag's name, ahead of them
+            if (many_host || left || anti || full || allc || po || bo)
+                return set_err("fj_join_host: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (it merges partial group-by rows: there is no join in it)",
+                               many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+            if (pk || np) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE takes no probe side (probe_keys must be NULL and np 0: the partial rows are the build side)");
+            if (amin || amax) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_AGG_%s (it merges both the minima and the maxima)", amin ? "MIN" : "MAX");
+            if (rid || inv || aarg) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (a partial row is no row of a relation)", rid ? "ROW_IDS" : inv ? "INVERSE" : "AGG_ARG");
+            if (asigned && (algo & FJ_ALGO_AGG_FLOAT)) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE needs materialize = 1 (the merged rows are the result)");
+            if (!out_keys || !out_vals || (nb && !bv)) return set_err("fj_join_host: FJ_ALGO_AGG_MERGE needs build_vals, out_keys and out_vals (four planes of nb words - count, sum, min, max -, the g distinct keys and four planes of g words)");
+        }
         if (many_host || left || anti || full || allc || po || bo)
             return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
@@ -296,7 +310,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     // internal context, so drop it here
     if (stream_abort(c) || begin_step(c, "fj_join_host")) return 1;
     void *dbk, *dbv, *dpk;
-    if (get_buf(c, W_H_BK, nb * 8, &dbk) || get_buf(c, W_H_BV, (bo ? np : nb) * 8, &dbv) || get_buf(c, W_H_PK, np * 8, &dpk)) return 1;
+    if (get_buf(c, W_H_BK, nb * 8, &dbk) || get_buf(c, W_H_BV, (bo ? np : amerge ? 4 * nb : nb) * 8, &dbv) || get_buf(c, W_H_PK, np * 8, &dpk)) return 1;
     // pieces: >= 16 MiB (the ring's DMA and memcpy run at full rate), at most 48 of them for the probe side (the streamed
     // join takes <= 64 appends), a multiple of 4 KiB
     size_t piece = std::max<size_t>(16u << 20, (np * 8 + 47) / 48);
@@ -325,7 +339,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
         else if (gb) {                                                          // the relation's value column: only the sum / min / max forms that return it read it
             if (!bv || inv) dbv = nullptr;
-            else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1;
+            else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, (amerge ? 4 * nb : nb) * 8, piece, &cursor, nullptr)) return 1;   // (FJ_ALGO_AGG_MERGE: four planes)
         }
         else if (bo) {                                                          // the probe side's value column, read for the sums only
             if (!out_vals || !np) dbv = nullptr;

@@ -462,6 +462,14 @@ hipError_t fj_launch_group_by_arg(const FjGroupByArgs& a, const u64* vals, u64 n
 hipError_t fj_launch_gt_group_by_arg_resolve(const FjGtArgs& a, int kind, const u64* vals, const u64* ext, u64* pos, hipStream_t s);
 hipError_t fj_launch_gt_group_by_arg_sweep(const FjGtArgs& a, const u64* ext, const u64* pos, u64* out_keys, u64* out_vals, u64 out_capacity,
                                            unsigned long long* cursor, u32* err, hipStream_t s);
+// the merge of partial group-bys (csrc/fj_groupby_merge.hip; FJ_ALGO_AGG_MERGE): as fj_launch_group_by_all, but a.rel.vals holds the
+// partial rows' POSITIONS (the first pass made them; flat arrays: the index), the kernel gathers planes[q * nrows + position] for the four
+// planes q - count, sum, min, max of every partial row - itself, the counts ADD in 64 bits, and the table takes 1920 distinct keys per
+// partition.  kind: the words of the sum, min and max planes as 0 uint64, 1 int64, 2 binary64
+hipError_t fj_launch_group_by_merge(const FjGroupByArgs& a, const u64* planes, u64 nrows, int kind, hipStream_t s);
+// ... on the global table of fj_launch_gt_build_first (vals = false) over a.bk: acc as for fj_launch_gt_group_by_all_combine; one thread
+// per partial row combines planes[q * a.nb + i] into all four.  fj_launch_gt_group_by_all_sweep compacts
+hipError_t fj_launch_gt_group_by_merge_combine(const FjGtArgs& a, int kind, const u64* planes, u64* acc, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

@@ -689,6 +689,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
+    const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;   // a modifier of that PAIR: the build side is partial rows with four planes (csrc/fj_groupby_merge.hip)
     const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
     const bool bo_reuse = bo && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // the aggregate join onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD stays unknown)
     const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
@@ -697,6 +698,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0, afloat = (bo || gb) && (algo & FJ_ALGO_AGG_FLOAT) != 0;
     int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
     const int algo_word = algo;
+    if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
+        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo_word);
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
     const uint64_t* d_gv = nullptr;                         // FJ_ALGO_GROUP_BY: d_build_vals is the relation's value column (null: the count form)
@@ -705,6 +708,19 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
         algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG);
+        if (amerge) {                                       // partial rows in, FJ_ALGO_AGG_ALL's outputs out: its refusals under this flag's name, ahead of them
+            algo &= ~FJ_ALGO_AGG_MERGE;
+            if (many || left || anti || full || allc || po || bo)
+                return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (it merges partial group-by rows: there is no join in it)",
+                               many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+            if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE takes no probe side (d_probe_keys must be NULL and np 0: the partial rows are the build side)");
+            if (amin || amax) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_AGG_%s (it merges both the minima and the maxima)", amin ? "MIN" : "MAX");
+            if (rid || inv || aarg) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (a partial row is no row of a relation)", rid ? "ROW_IDS" : inv ? "INVERSE" : "AGG_ARG");
+            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs materialize = 1 (the merged rows are the result)");
+            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs d_build_vals, d_out_keys and d_out_vals (four planes of nb words - count, sum, min, max -, the g distinct keys and four planes of out_capacity words)");
+            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs an output capacity of at least 1 row (any bound on the number of groups will do)");
+        }
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
@@ -879,6 +895,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (timings) *timings = t;
         last_timings() = t;
         return 0;
+    }
+    if (amerge) {                                           // ... of partial rows: the four planes of the rows of one key combined; g beyond the capacity as below
+        const int rc = group_by_merge(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
+                                      afloat ? 2 : asigned ? 1 : 0);
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return rc;
     }
     if (aall) {                                             // ... and four aggregates beside it; g beyond the capacity fails with *out_count = g
         const int rc = group_by_all(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,

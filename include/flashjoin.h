@@ -345,6 +345,33 @@ extern "C" {
  * or with both; combined with FJ_ALGO_ROW_IDS, FJ_ALGO_INVERSE or FJ_ALGO_AGG_ALL, with FJ_ALGO_AGG_SIGNED and FJ_ALGO_AGG_FLOAT
  * together; materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity < nb; a misaligned output. */
 #define FJ_ALGO_AGG_ARG    0x8000000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL (in every other combination an unknown algo; csrc/fj_groupby_merge.hip):
+ * MERGE partial group-by results.  The build side is not a relation but nb PARTIAL rows - a key and beside it a row count, a sum, a
+ * minimum and a maximum, what FJ_ALGO_AGG_ALL returned for one batch, one shard or one slice of a relation - and the rows that share a
+ * key are combined into one.  OR it into `algo` together with FJ_ALGO_GROUP_BY, FJ_ALGO_AGG_ALL and a base value (ADAPTIVE, SCALAR or
+ * RADIX), optionally with FJ_ALGO_AGG_SIGNED or with FJ_ALGO_AGG_FLOAT, materialize = 1:
+ *   d_build_keys                  nb keys, one per partial row.
+ *   d_build_vals                  FOUR planes of nb words at stride nb - count, sum, min, max: the layout FJ_ALGO_AGG_ALL writes, with
+ *                                 stride nb in place of out_capacity.  Required (nb > 0).
+ *   d_out_keys, d_out_vals        exactly as for FJ_ALGO_AGG_ALL: the g distinct keys and four planes of out_capacity words -
+ *                                   plane 0  the sum of the rows' counts modulo 2^64
+ *                                   plane 1  the sum of the rows' sums: modulo 2^64, or binary64 atomic adds in an unspecified order
+ *                                            with FJ_ALGO_AGG_FLOAT
+ *                                   plane 2  the minimum of the rows' minima
+ *                                   plane 3  the maximum of the rows' maxima
+ *                                 in the kind's order (uint64, int64 with FJ_ALGO_AGG_SIGNED, numbers with FJ_ALGO_AGG_FLOAT; NaN and
+ *                                 -0.0 / +0.0 as for FJ_ALGO_AGG_ALL).
+ * A partial row with count 0 whose other planes hold the aggregates' identities (sum 0 / +0.0; min all ones, INT64_MAX or +inf; max 0,
+ * INT64_MIN or -inf) is legal: it is what FJ_ALGO_BUILD_ORDER leaves for a build row without a partner.  Its key becomes a group of the
+ * result, with count 0 unless another row of that key says otherwise.
+ * *out_count = g.  out_capacity may be ANY value >= 1; g > out_capacity fails AFTER the device work with an error that states g, with
+ * *out_count = g, and the context stays usable.  nb == 0: g = 0, no buffer is needed.  bloom is ignored.  Never a pending result.
+ * fj_timings as for FJ_ALGO_AGG_ALL; fell_back = 1 when a final partition held more distinct keys than this form's LDS table takes
+ * (1920) and the call ran again on the HBM table.  fj_join_host: build_vals is 4 * nb words; the outputs as for FJ_ALGO_AGG_ALL.
+ * Refused up front, before any device work: everything FJ_ALGO_AGG_ALL refuses (FJ_ALGO_AGG_MIN, FJ_ALGO_AGG_MAX, FJ_ALGO_ROW_IDS,
+ * FJ_ALGO_INVERSE, FJ_ALGO_AGG_SIGNED with FJ_ALGO_AGG_FLOAT, materialize = 0, a NULL d_build_vals, d_out_keys or d_out_vals with
+ * nb > 0, out_capacity == 0 with nb > 0, a misaligned buffer), FJ_ALGO_AGG_ARG beside it, and whatever FJ_ALGO_GROUP_BY refuses. */
+#define FJ_ALGO_AGG_MERGE  0x10000000
 
 typedef struct fj_ctx fj_ctx;
 
