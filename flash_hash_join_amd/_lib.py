@@ -46,7 +46,7 @@ LAB_SYMBOLS = [
     "fj_bcast_region_bytes", "fj_bcast_piece_span", "fj_bcast_pack", "fj_bcast_pack_bounds", "fj_bcast_probe", "fj_bcast_join", "fj_bcast_finish", "fj_bcast_abort",
     "fj_bloom_filter_words", "fj_bloom_export", "fj_bloom_prefilter",
     "fj_stream_open", "fj_stream_append_build", "fj_stream_advance_probe", "fj_stream_begin", "fj_stream_append_probe", "fj_stream_finish",
-    "fj_ctx_reserve_cus", "fj_debug_partition",
+    "fj_ctx_reserve_cus", "fj_key_pair64", "fj_debug_partition",
 ]
 
 
@@ -245,6 +245,8 @@ def load() -> ctypes.CDLL:
         L.fj_bcast_join.restype = i32; L.fj_bcast_join.argtypes = [vp, vp, i32, pu64, pu64, ctypes.c_uint32, ctypes.c_uint32, vp]
         L.fj_bcast_finish.restype = i32; L.fj_bcast_finish.argtypes = [vp, vp, pu64, ctypes.POINTER(FjTimings)]
         L.fj_bcast_abort.restype = None; L.fj_bcast_abort.argtypes = [vp]
+        if hasattr(L, "fj_key_pair64"):                     # (an A/B variant built from an older tree lacks it)
+            L.fj_key_pair64.restype = u64; L.fj_key_pair64.argtypes = [u64, u64]
         L.fj_debug_partition.restype = i32
         L.fj_debug_partition.argtypes = [vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, pu64]
     _lib = L

@@ -51,6 +51,7 @@ ALGO_ACCUMULATE = 0x1000000       # FJ_ALGO_ACCUMULATE: modifier of ALGO_BUILD_O
 ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_ORDER / ALGO_GROUP_BY - the value column and the values output hold IEEE-754 float64 words: float sum, or float min / max with AGG_MIN / AGG_MAX (extension)
 ALGO_AGG_ALL = 0x4000000          # FJ_ALGO_AGG_ALL: modifier of ALGO_GROUP_BY - the values output holds FOUR planes: row count, sum, minimum and maximum of the value column (extension)
 ALGO_AGG_MERGE = 0x10000000       # FJ_ALGO_AGG_MERGE: modifier of ALGO_GROUP_BY | ALGO_AGG_ALL - the input rows are PARTIAL aggregates (a key and four planes: count, sum, min, max) and the rows of one key are combined (extension)
+ALGO_KEY_PAIR = 0x20000000        # FJ_ALGO_KEY_PAIR: modifier of ALGO_GROUP_BY | ALGO_INVERSE - the key is the PAIR (keys, values): the values output holds every row's group id, the keys output the row index of each group's first occurrence (extension)
 ALGO_AGG_ARG = 0x8000000          # FJ_ALGO_AGG_ARG: modifier of ALGO_GROUP_BY with AGG_MIN or AGG_MAX - the values output holds TWO planes: the row index of each group's extreme (smallest index on ties) and the extreme (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
@@ -1298,6 +1299,89 @@ def factorize(keys):
     return g, sec, codes, uniques
 
 
+def _key_columns(name: str, what: str, columns: Any):
+    """(columns, torch_in): a key of one or more columns as a list of word columns - a single array is one column, a list / tuple of
+    arrays (or of nested sequences) is one column each.  Every column is converted as `factorize` converts its keys; all are of one
+    kind - NumPy-like (torch_in False), or torch tensors on one device - and of one length."""
+    if isinstance(columns, (list, tuple)) and len(columns) and all(_is_array(c) or isinstance(c, (list, tuple)) for c in columns):
+        cols = [_from_dlpack_if_device(c) for c in columns]
+    elif isinstance(columns, (list, tuple)) and not len(columns):
+        cols = []
+    else:
+        cols = [_from_dlpack_if_device(columns)]
+    if not cols:
+        return cols, False
+    torch_in = [_is_torch_tensor(c) for c in cols]
+    if any(torch_in) and not all(torch_in):
+        raise TypeError(f"{name}: {what} must be of one kind, got NumPy and torch columns side by side")
+    if all(torch_in):
+        _same_container(name, cols)
+        if cols[0].is_cuda:
+            cols = [_dev_tensor(c, f"{what}[{i}]") for i, c in enumerate(cols)]
+        else:
+            cols = [_as_u64_host(c.numpy(), f"{what}[{i}]") for i, c in enumerate(cols)]
+    else:
+        cols = [_as_u64_host(c, f"{what}[{i}]") for i, c in enumerate(cols)]
+    for i, c in enumerate(cols[1:], 1):
+        if c.shape[0] != cols[0].shape[0]:
+            raise ValueError(f"{name}: {what}[{i}] has {c.shape[0]} rows, {what}[0] has {cols[0].shape[0]}")
+    return cols, all(torch_in)
+
+
+def _first_rows(idx):
+    """the row indices the pair form returns where the keys go, as int64 in their container"""
+    return idx if _is_torch_tensor(idx) else idx.view(np.int64)
+
+
+def factorize_columns(columns):
+    """The dense group id of every row under a MULTI-COLUMN key - (customer, day), (src, dst), (tenant, user):
+    (g, seconds, codes, first_index).  columns is a sequence of two or more key columns of equal length and one kind, each converted
+    as `factorize` converts its keys.  codes holds one int64 in [0, g) per row, and two rows share a code iff they agree in EVERY
+    column; first_index holds, per group, the int64 row index of its first occurrence, so the distinct tuples are
+    tuple(c[first_index] for c in columns) and c[first_index][codes] == c for every column.  The order of the groups is unspecified.
+    Two columns are ONE library call (C ABI: algo | FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE | FJ_ALGO_KEY_PAIR), exact for every input; a
+    third and fourth column fold on left to right - (codes so far, next column) through the same call - and `seconds` is the sum.  The
+    codes are ordinary dense keys: group_by_agg(codes, v), inner_join(build_codes, bv, probe_codes) and build_index(codes) take them
+    unchanged.  NumPy in, NumPy out; torch ROCm tensors / DLPack are grouped in place on the current stream, both outputs torch.int64
+    on their device.  A single column is `factorize`'s: here it is a ValueError."""
+    if _is_array(columns):
+        raise ValueError("factorize_columns: got a single array; columns is a sequence of two or more key columns (one column: factorize)")
+    cols, _ = _key_columns("factorize_columns", "columns", columns)
+    if len(cols) < 2:
+        raise ValueError(f"factorize_columns: got {len(cols)} column{'s' if len(cols) != 1 else ''}; columns is a sequence of two or more key columns (one column: factorize)")
+    g, sec, first, codes = _group_by(cols[0], cols[1], ALGO_INVERSE | ALGO_KEY_PAIR)
+    for c in cols[2:]:
+        g, sec2, first, codes = _group_by(codes, c, ALGO_INVERSE | ALGO_KEY_PAIR)    # (the first rows of (codes, c) are rows of the relation already)
+        sec += sec2
+    return g, sec, codes, _first_rows(first)
+
+
+def encode_keys(build_columns, probe_columns):
+    """ONE shared dictionary over the keys of two relations: (g, seconds, build_codes, probe_codes).  Each argument is a sequence of
+    key columns as for `factorize_columns` - or a single array, a one-column key - and both name the same number of columns.  The
+    columns are concatenated, build rows first, factorized in one `factorize_columns` call (`factorize` for one column) and the
+    codes split again: equal tuples get equal int64 codes in [0, g) across the two relations, so every join, `build_index` and every
+    `group_join_*` takes the codes as its keys.  NumPy in, NumPy out; torch ROCm tensors stay on their device and stream."""
+    b, b_torch = _key_columns("encode_keys", "build_columns", build_columns)
+    p, p_torch = _key_columns("encode_keys", "probe_columns", probe_columns)
+    if len(b) != len(p) or not b:
+        raise ValueError(f"encode_keys: build_columns names {len(b)} key columns, probe_columns {len(p)}; both sides need the same number, at least one")
+    if b_torch != p_torch:
+        raise TypeError("encode_keys: build_columns and probe_columns must be of one kind, got NumPy and torch columns side by side")
+    if _is_torch_tensor(b[0]):
+        import torch
+        _same_container("encode_keys", b + p)
+        cat = [torch.cat((x.view(torch.int64), y.view(torch.int64))) for x, y in zip(b, p)]
+    else:
+        cat = [np.concatenate((x, y)) for x, y in zip(b, p)]
+    nb = b[0].shape[0]
+    if len(cat) == 1:
+        g, sec, codes, _ = factorize(cat[0])
+    else:
+        g, sec, codes, _ = factorize_columns(cat)
+    return g, sec, codes[:nb], codes[nb:]
+
+
 def unique(keys, return_index: bool = False, return_counts: bool = False, return_inverse: bool = False):
     """The distinct keys of one relation (DISTINCT; torch.unique / np.unique without the sort): (g, seconds, unique_keys) followed by
     first_index if return_index (the 0-based position of every key's FIRST occurrence, int64), by inverse if return_inverse (int64,
@@ -2085,4 +2169,7 @@ EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_
               "group_join_min", "group_join_max", "unique", "distinct_count", "group_by_count", "group_by_sum", "group_by_min", "group_by_max",
               "group_by_agg", "group_by_argmin", "group_by_argmax", "group_by_merge", "GroupByAccumulator", "group_by_accumulator", "factorize",
               "build_index"]
-__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]
+# multi-column keys: compositions over the entries above (`_group_by`, `factorize`), whose caller-context rows
+# (tests/test_caller_context_cpu.py walks EXTENSIONS) cover the path they take; their own suite is tests/test_factorize_columns.py
+KEY_EXTENSIONS = ["factorize_columns", "encode_keys"]
+__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + KEY_EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

@@ -112,6 +112,11 @@ __host__ __device__ __forceinline__ u32 fj_hash_w1(u64 k) {
     return fj_fmix32(a ^ b);
 }
 __host__ __device__ __forceinline__ u64 fj_hash64(u64 k) { return fj_key_mix(k); }
+// a two-column key (a, b) as ONE word the partition passes and the tables treat as a key (FJ_ALGO_KEY_PAIR, csrc/fj_groupby_pair.hip).
+// For a fixed b it is a bijection of a - any word w is reached by a = w ^ fj_key_mix(b ^ C) - but over pairs it is NOT injective:
+// every user verifies the pair itself behind an equal word
+#define FJ_PAIR_SALT 0x9E3779B97F4A7C15ull
+__host__ __device__ __forceinline__ u64 fj_key_pair(u64 a, u64 b) { return a ^ fj_key_mix(b ^ FJ_PAIR_SALT); }
 
 // splitmix64-style counter hash used by the synthetic generators; identical in
 // NumPy (flash_hash_join_amd/datagen.py), C and HIP.

@@ -92,6 +92,7 @@ enum Slot {
                                                                                     // probe items, both sets' counts and both sets' offsets (mm_tile_join)
     W_MM_PBITS,                                                                     // ... option "mm_heavy_outer": "found a partner in some tile" bits of the probe rows (one per row of the probe side's final chunk pool)
     W_FULL_BITS,                                                                    // full outer join: matched bits of the build rows / of the global table's slots
+    W_PAIR_WORDS,                                                                   // FJ_ALGO_KEY_PAIR: the nb combined words of the two key columns, the input of the relation's passes (fj_groupby_pair.hip)
     W_NSLOTS
 };
 
@@ -372,6 +373,11 @@ int group_by_arg(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t
 // count, sum, min, max; d_ov is four planes of cap_out words, the rows of one key combined; kind and cap_out as for group_by_all
 int group_by_merge(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
                    u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind);
+
+// ... with FJ_ALGO_INVERSE | FJ_ALGO_KEY_PAIR (fj_groupby_pair.hip): the key is the PAIR (ka[i], kb[i]); d_ov receives nb words, every row's
+// group id at the row's position, and d_ok the g row indices of the groups' first occurrences; nb <= 2^40, cap_out >= nb
+int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+                  u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

@@ -183,13 +183,16 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
+    const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;                     // a two-column key: build_vals is the second KEY column, *out_keys g first-occurrence row indices
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;
     const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;            // partial rows in: build_vals is FOUR planes of nb words
     if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
         return set_err("fj_join_host: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo);
+    if (algo >= 0 && (algo & FJ_ALGO_KEY_PAIR) && !gb)
+        return set_err("fj_join_host: unknown algo %d (FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE)", algo);
     const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
-                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
+                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (amerge) {                                          // FJ_ALGO_AGG_ALL's refusals under this flag's name, ahead of them
@@ -233,6 +236,11 @@ int fj_join_host(int algo, int bloom, int materialize,
                                amin ? "MIN" : amax ? "MAX" : "SIGNED");
             if (rid) return set_err("fj_join_host: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_ROW_IDS (out_vals is taken: one per-call output)");
             if (!materialize) return set_err("fj_join_host: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+        }
+        if (kpair) {                                           // the ids as above; *out_keys: the row index of every group's first occurrence
+            if (!inv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing)");
+            if (nb && !bv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR needs build_vals (the second key column, nb words)");
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
         }
         if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax && !aall) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
@@ -338,7 +346,8 @@ int fj_join_host(int algo, int bloom, int materialize,
     if (!streamed) {
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
         else if (gb) {                                                          // the relation's value column: only the sum / min / max forms that return it read it
-            if (!bv || inv) dbv = nullptr;
+            if (kpair) { if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1; }      // (the second key column)
+            else if (!bv || inv) dbv = nullptr;
             else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, (amerge ? 4 * nb : nb) * 8, piece, &cursor, nullptr)) return 1;   // (FJ_ALGO_AGG_MERGE: four planes)
         }
         else if (bo) {                                                          // the probe side's value column, read for the sums only
@@ -477,9 +486,9 @@ int fj_join_host(int algo, int bloom, int materialize,
     }
     if (gb && !aall && !aarg) {                                                        // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
         void *dok = nullptr, *dov = nullptr;
-        const bool ids = inv && out_vals;                                       // (nobody takes the ids: the plain distinct form)
+        const bool ids = inv && (out_vals || kpair);                            // (nobody takes the ids: the plain distinct form - which a two-column key does not have)
         if (inv && !ids) algo &= ~FJ_ALGO_INVERSE;
-        if (materialize && (get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dok) || (out_vals && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dov)))) return 1;
+        if (materialize && (get_buf(c, W_H_OK, std::max<size_t>(nb, 1) * 8, &dok) || ((out_vals || ids) && get_buf(c, W_H_OV, std::max<size_t>(nb, 1) * 8, &dov)))) return 1;
         if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
                            &count, (u64*)dok, (u64*)dov, nb, &t)) return 1;
         if (materialize) {

@@ -12,6 +12,7 @@
 #define FJ_BLOOM_HDR_MAGIC 0xB100F000u   // exported filter sets end with 4 header words: [0] = magic | variant
 #define FJ_STAT_TOOBIG 64u   // (status) some items' partitions hold more distinct build keys than even the tagged LDS table takes: part_count[item] == FJ_ITEM_TOOBIG marks them; the host re-partitions just those
 #define FJ_ERR_OUTCAP 128u   // single-pass materialising join: more pairs than the caller's output buffers hold
+#define FJ_ERR_PAIR_COLLISION 256u // FJ_ALGO_KEY_PAIR: two distinct pairs share a combined word (fj_key_pair) -> global-table fallback, which compares pairs
 #define FJ_ITEM_RETRY 0xFFFFFFFFu
 #define FJ_ITEM_TOOBIG 0xFFFFFFFEu
 

@@ -687,6 +687,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
+    const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;   // a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE: d_build_vals is a second KEY column (csrc/fj_groupby_pair.hip)
+    const uint64_t* d_kb = nullptr;                         // ... that column
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
     const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;   // a modifier of that PAIR: the build side is partial rows with four planes (csrc/fj_groupby_merge.hip)
@@ -700,6 +702,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const int algo_word = algo;
     if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
         return set_err("fj_join_device: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo_word);
+    if (algo >= 0 && (algo & FJ_ALGO_KEY_PAIR) && !gb)
+        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE)", algo_word);
     if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
     const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
     const uint64_t* d_gv = nullptr;                         // FJ_ALGO_GROUP_BY: d_build_vals is the relation's value column (null: the count form)
@@ -707,7 +711,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR);
         if (amerge) {                                       // partial rows in, FJ_ALGO_AGG_ALL's outputs out: its refusals under this flag's name, ahead of them
             algo &= ~FJ_ALGO_AGG_MERGE;
             if (many || left || anti || full || allc || po || bo)
@@ -753,6 +757,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
             if (rid) return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_ROW_IDS (d_out_vals is taken: one per-call output)");
             if (!materialize) return set_err("fj_join_device: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
             if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_INVERSE needs d_out_keys and d_out_vals (the g distinct keys and the nb group ids that index them)");
+        }
+        if (kpair) {                                        // a two-column key: the group ids as above, d_out_keys the row index of every group's first occurrence
+            if (!inv) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing)");
+            if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR needs d_build_vals (the second key column, nb words)");
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
+            if ((uintptr_t)d_bv & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
+            d_kb = d_bv;
         }
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax && !aall) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
@@ -915,6 +926,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     if (aarg) {                                             // ... or the row index and the extreme beside it (out_capacity >= nb was checked)
         if (group_by_arg(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
                          afloat ? 2 : asigned ? 1 : 0, amax)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (kpair) {                                            // ... under a two-column key: nb ids and g first rows, never a pending result
+        if (group_by_pair(c, use_radix, d_bk, d_kb, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

@@ -372,6 +372,29 @@ extern "C" {
  * FJ_ALGO_INVERSE, FJ_ALGO_AGG_SIGNED with FJ_ALGO_AGG_FLOAT, materialize = 0, a NULL d_build_vals, d_out_keys or d_out_vals with
  * nb > 0, out_capacity == 0 with nb > 0, a misaligned buffer), FJ_ALGO_AGG_ARG beside it, and whatever FJ_ALGO_GROUP_BY refuses. */
 #define FJ_ALGO_AGG_MERGE  0x10000000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (in every other combination refused; csrc/fj_groupby_pair.hip): the key of
+ * the group-by is a PAIR of columns - (customer, day), (src, dst), (tenant, user).  OR it into `algo` together with FJ_ALGO_GROUP_BY,
+ * FJ_ALGO_INVERSE and a base value (ADAPTIVE, SCALAR or RADIX), materialize = 1:
+ *   d_build_keys       column A, nb words.
+ *   d_build_vals       column B, nb words: a KEY column here.  Required (nb > 0), 16-byte aligned.
+ * Rows i and j belong to one group iff A[i] == A[j] && B[i] == B[j], compared as 64-bit words.
+ *   d_out_vals[i]      for every i < nb: the group id of row i, AT row i's position - a uint64 in [0, g), as for FJ_ALGO_INVERSE.
+ *   d_out_keys[r]      for r < g: NOT a key but the ROW INDEX of group r's first occurrence - the smallest i whose pair is the group's.
+ *                      The caller gathers A[idx], B[idx] and any other column with it; rows [g, nb) may hold anything.
+ * *out_count = g.  out_capacity >= nb covers both arrays; both are required (nb > 0) and 8-byte aligned; nothing at or beyond word
+ * out_capacity of either is touched.  nb == 0: g = 0, nothing is written.  nb <= 2^40.  bloom is ignored.  Never a pending result.
+ * The ids are ordinary dense keys: every function of this header takes them as its one key column, and a third column folds onto them
+ * with another call (ids, C).  The result is deterministic up to the order of the groups, which is the cursor's.
+ * The partition passes run over ONE combined word per row, a ^ fj_key_mix64(b ^ 0x9E3779B97F4A7C15).  That map is not injective: every
+ * row's pair is compared with its group's first row, and where two distinct pairs share a word the call runs again on an HBM table
+ * that compares pairs.  The result is exact for every input.
+ * fj_timings as for FJ_ALGO_INVERSE; fell_back = 1 when the call ran again on the HBM table (a final partition of more than 7680
+ * distinct combined words, or two pairs on one word).
+ * fj_join_host: build_vals is column B; *out_keys is a malloc'ed array of exactly g row indices, *out_vals one of exactly nb ids; a
+ * NULL pointer drops that output.
+ * Refused up front, before any device work: the flag without FJ_ALGO_GROUP_BY (an unknown algo); with it but without FJ_ALGO_INVERSE;
+ * everything FJ_ALGO_INVERSE and FJ_ALGO_GROUP_BY refuse; a NULL d_build_vals with nb > 0; nb > 2^40. */
+#define FJ_ALGO_KEY_PAIR   0x20000000
 
 typedef struct fj_ctx fj_ctx;
 

@@ -159,6 +159,10 @@ int fj_stream_finish(fj_ctx* ctx, void* stream, uint64_t* out_count, fj_timings*
  * restores the full grid. */
 void fj_ctx_reserve_cus(fj_ctx* ctx, unsigned n);
 
+/* The combined word of a two-column key (FJ_ALGO_KEY_PAIR): a ^ fj_key_mix64(b ^ 0x9E3779B97F4A7C15), what the partition passes see in
+ * place of the pair.  For any word w and any b, a = w ^ fj_key_mix64(b ^ 0x9E3779B97F4A7C15) lands on w: tests craft collisions with it. */
+uint64_t fj_key_pair64(uint64_t a, uint64_t b);
+
 /*
  * Diagnostic for the test-suite: runs total_bits (2..24) of radix partitioning over a flat
  * device relation and writes the final per-bucket chunk lists, linearised bucket by bucket, into

@@ -15,7 +15,9 @@ form, appended to --out:
                                    [--out profiles/group_by_probe.jsonl]
 
 Workloads: u1m = 100M rows over 1M distinct keys, uniform; distinct = 100M rows, all distinct; b1g = 1B rows over 100M distinct keys;
-hot = 100M rows over 1M keys of which one owns every tenth row.  Times of (a) are device times (core_duration_sec, HIP events); (b) is
+hot = 100M rows over 1M keys of which one owns every tenth row.  Two-column keys (not in the default list): p1k = 100M rows over
+1000 x 1000 values, p10k = 100M rows over 10 000 x 10 000 values - the lines factorize_columns and "factorize x3 + multiply-add", its
+composition from the single-key entry (_pair_workload).  Times of (a) are device times (core_duration_sec, HIP events); (b) is
 torch kernels, so its figure is wall time around a synchronised region, and (a) is reported that way too ("wall_median_ms") so that
 the two compare like with like.  "timings" of (a) carry the split: build_phase_ms = the relation's passes, join_ms = the kernel - for
 the hot workload the kernel's time is the one long work item's (the hot key's partition)."""
@@ -28,6 +30,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+PAIR_WORKLOADS = {"p1k": (100_000_000, 1000, 1000), "p10k": (100_000_000, 10_000, 10_000)}     # rows, values of column a, values of column b
 WORKLOADS = {"u1m": (100_000_000, 1_000_000), "distinct": (100_000_000, 100_000_000), "b1g": (1_000_000_000, 100_000_000), "hot": (100_000_000, 1_000_000)}
 KEEP = ("total_ms", "build_phase_ms", "probe_phase_ms", "join_ms", "emit_ms", "path", "passes", "radix_bits", "fell_back")
 SPREAD = 0x9E3779B97F4A7C15 - 2**64          # an odd multiplier: i -> i * SPREAD is one-to-one modulo 2^64 (int64 storage)
@@ -52,6 +55,36 @@ def _timed(fn, want, steps, warmup):
     return (statistics.median(dev) if dev else None), (min(dev) if dev else None), statistics.median(wall)
 
 
+def _pair_workload(flash_join, torch, wl, args, out):
+    """two-column keys (FJ_ALGO_KEY_PAIR): factorize_columns next to its composition from the single-key entry - factorize(a),
+    factorize(b), a multiply-add of the two code columns, a third factorize.  Both report device times (the composition: the sum of
+    its three calls); the composition's last call runs factorize's kernel over the very groups factorize_columns finds, so its
+    join_ms beside factorize_columns' join_ms is what the pair kernel's position atomics and verification gathers cost."""
+    n, na, nb = PAIR_WORKLOADS[wl]
+    a = torch.randint(0, na, (n,), dtype=torch.int64, device="cuda:0") * SPREAD
+    b = torch.randint(0, nb, (n,), dtype=torch.int64, device="cuda:0") * SPREAD
+
+    def composed():
+        ga, s1, ca, _ = flash_join.factorize(a)
+        gb, s2, cb, _ = flash_join.factorize(b)
+        g, s3, codes, _ = flash_join.factorize(ca * gb + cb)
+        return g, s1 + s2 + s3, codes
+
+    g = composed()[0]                                                         # the two forms check each other's group count
+    runs = [("a", "factorize_columns", lambda: flash_join.factorize_columns((a, b))), ("a", "factorize x3 + multiply-add", composed)]
+    if args.names:
+        runs = [r for r in runs if r[1] in args.names.split(",")]
+    for form, name, fn in runs:
+        d_med, d_min, w_med = _timed(fn, g, args.steps, args.warmup)
+        lt = flash_join.last_timings()                                        # (the composition: its third call's)
+        line = json.dumps({"workload": wl, "rows": n, "distinct": g, "form": form, "name": name, "device_median_ms": round(d_med, 3),
+                           "device_min_ms": round(d_min, 3), "wall_median_ms": round(w_med, 3), "timings": {k: lt[k] for k in KEEP}})
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="u1m,distinct,hot")
@@ -67,6 +100,9 @@ def main():
     forms = args.forms.split(",")
     out = open(args.out, "a")
     for wl in args.workloads.split(","):
+        if wl in PAIR_WORKLOADS:
+            _pair_workload(flash_join, torch, wl, args, out)
+            continue
         n, g = WORKLOADS[wl]
         if g == n:
             keys = torch.arange(n, dtype=torch.int64, device="cuda:0")[torch.randperm(n, device="cuda:0")] * SPREAD
