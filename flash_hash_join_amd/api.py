@@ -52,6 +52,7 @@ ALGO_AGG_FLOAT = 0x2000000        # FJ_ALGO_AGG_FLOAT: modifier of ALGO_BUILD_OR
 ALGO_AGG_ALL = 0x4000000          # FJ_ALGO_AGG_ALL: modifier of ALGO_GROUP_BY - the values output holds FOUR planes: row count, sum, minimum and maximum of the value column (extension)
 ALGO_AGG_MERGE = 0x10000000       # FJ_ALGO_AGG_MERGE: modifier of ALGO_GROUP_BY | ALGO_AGG_ALL - the input rows are PARTIAL aggregates (a key and four planes: count, sum, min, max) and the rows of one key are combined (extension)
 ALGO_KEY_PAIR = 0x20000000        # FJ_ALGO_KEY_PAIR: modifier of ALGO_GROUP_BY | ALGO_INVERSE - the key is the PAIR (keys, values): the values output holds every row's group id, the keys output the row index of each group's first occurrence (extension)
+ALGO_GROUP_ROWS = 0x40000000       # FJ_ALGO_GROUP_ROWS: modifier of ALGO_GROUP_BY alone - the values output holds TWO planes: the row indices in group-contiguous order and the first of them that belongs to each group, a CSR of row indices (extension)
 ALGO_AGG_ARG = 0x8000000          # FJ_ALGO_AGG_ARG: modifier of ALGO_GROUP_BY with AGG_MIN or AGG_MAX - the values output holds TWO planes: the row index of each group's extreme (smallest index on ties) and the extreme (extension)
 _OUTER = ALGO_LEFT_OUTER | ALGO_ANTI
 
@@ -1299,6 +1300,96 @@ def factorize(keys):
     return g, sec, codes, uniques
 
 
+def _group_rows(keys):
+    """(g, seconds, group_keys, offsets, row_index) of ALGO_GROUP_BY | ALGO_GROUP_ROWS, where the keys live: the two planes of the
+    values output come back as row_index (the first len(keys) words of plane 0) and offsets (the g starts of plane 1 and len(keys))"""
+    global _last
+    keys = _from_dlpack_if_device(keys)
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_GROUP_ROWS
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    if _is_torch_tensor(keys) and keys.is_cuda:
+        import torch
+        k = _dev_tensor(keys, "keys")
+        n = k.numel()
+        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(n, dtype=torch.int64, device=k.device)
+        ov = torch.empty(2 * n, dtype=torch.int64, device=k.device)           # two planes of n words: the rows, the starts
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            check(L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), None, n, None, 0, stream, 64,
+                                   ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(), n, ctypes.byref(t)))
+        _last = t
+        g = int(cnt.value)
+        offsets = torch.empty(g + 1, dtype=torch.int64, device=k.device)
+        offsets[:g] = ov[n:n + g]
+        offsets[g] = n
+        return g, t.total_ms * 1e-3, _trim(ok, g), offsets, ov[:n]
+    if _is_torch_tensor(keys):
+        keys = keys.numpy()
+    k = _as_u64_host(keys, "keys")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, None, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        gk = take(ok, g)
+        words = take(ov, k.size + g).view(np.int64)                           # the nb row indices, then the g starts
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    offsets = np.empty(g + 1, np.int64)
+    offsets[:g] = words[k.size:]
+    offsets[g] = k.size
+    return g, float(sec.value), gk, offsets, words[:k.size].copy()
+
+
+def group_rows(keys):
+    """The ROWS of every group (pandas groupby().indices, cuDF groupby.groups, SQL array_agg over the row number, the CSR of an edge
+    list by source): (g, seconds, group_keys, offsets, row_index).  group_keys holds the g distinct keys in unspecified order; offsets
+    is int64 of g + 1 with offsets[0] == 0 and offsets[g] == len(keys); row_index is int64 of len(keys), a permutation of the row
+    numbers, and keys[row_index[offsets[i]:offsets[i + 1]]] are all group_keys[i].  offsets is what torch.segment_reduce(...,
+    offsets=) and np.add.reduceat(values[row_index], offsets[:-1]) take as it is: a median, a quantile, a top-k, a list per group -
+    every aggregate the library has no kernel for - is one gather and one segmented pass of the caller's.  The order of the rows
+    INSIDE a group is unspecified and may differ from run to run.  One library call and no sort (C ABI: algo | FJ_ALGO_GROUP_BY |
+    FJ_ALGO_GROUP_ROWS).  Keys are converted as `factorize` converts them: NumPy in, group_keys is uint64 and the rest int64 NumPy;
+    torch ROCm tensors / DLPack are grouped in place on the current stream, every output is torch.int64 on their device."""
+    return _group_rows(keys)
+
+
+def group_by_collect(keys, values):
+    """The values of every group, gathered (SQL array_agg, pandas groupby().agg(list) as one flat array with offsets):
+    (g, seconds, group_keys, offsets, values[row_index]) with group_keys, offsets and row_index as `group_rows(keys)` returns them.
+    values has one row per key along its first dimension and keeps its dtype and any trailing dimensions; the rows of group i are
+    collected[offsets[i]:offsets[i + 1]], in unspecified order.  The gather is ONE indexing operation where the inputs live: NumPy
+    (or CPU torch) values with NumPy keys, a torch tensor on the keys' device with device keys."""
+    keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
+    dev_keys = _is_torch_tensor(keys) and keys.is_cuda
+    if dev_keys:
+        if not (_is_torch_tensor(values) and values.device == keys.device):
+            raise TypeError("group_by_collect: keys is a device tensor, values must be a torch tensor on the same device")
+        n = keys.numel()
+    else:
+        if _is_torch_tensor(values) and values.is_cuda:
+            raise TypeError("group_by_collect: values is a device tensor, keys must be a torch tensor on the same device")
+        if not _is_torch_tensor(values):
+            values = np.asarray(values)
+        n = keys.numel() if _is_torch_tensor(keys) else np.asarray(keys).size
+    if values.ndim < 1 or values.shape[0] != n:
+        raise ValueError(f"group_by_collect: values has {values.shape[0] if values.ndim else 'no'} rows along its first dimension, keys has {n}")
+    g, sec, gk, offsets, rows = _group_rows(keys)
+    if _is_torch_tensor(values) and not _is_torch_tensor(rows):
+        import torch
+        rows = torch.from_numpy(rows)
+    return g, sec, gk, offsets, values[rows]
+
+
 def _key_columns(name: str, what: str, columns: Any):
     """(columns, torch_in): a key of one or more columns as a list of word columns - a single array is one column, a list / tuple of
     arrays (or of nested sequences) is one column each.  Every column is converted as `factorize` converts its keys; all are of one
@@ -2172,4 +2263,6 @@ EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_
 # multi-column keys: compositions over the entries above (`_group_by`, `factorize`), whose caller-context rows
 # (tests/test_caller_context_cpu.py walks EXTENSIONS) cover the path they take; their own suite is tests/test_factorize_columns.py
 KEY_EXTENSIONS = ["factorize_columns", "encode_keys"]
-__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + KEY_EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]
+# the rows of every group: one entry of their own (ALGO_GROUP_ROWS) and a gather over it; their suite is tests/test_group_rows.py
+ROW_EXTENSIONS = ["group_rows", "group_by_collect"]
+__all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + KEY_EXTENSIONS + ROW_EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

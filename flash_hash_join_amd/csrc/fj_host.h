@@ -93,6 +93,7 @@ enum Slot {
     W_MM_PBITS,                                                                     // ... option "mm_heavy_outer": "found a partner in some tile" bits of the probe rows (one per row of the probe side's final chunk pool)
     W_FULL_BITS,                                                                    // full outer join: matched bits of the build rows / of the global table's slots
     W_PAIR_WORDS,                                                                   // FJ_ALGO_KEY_PAIR: the nb combined words of the two key columns, the input of the relation's passes (fj_groupby_pair.hip)
+    W_GR_PART, W_GR_BASE,                                                           // FJ_ALGO_GROUP_ROWS: groups and rows per final partition; their exclusive scans (the HBM form: per tile of table slots) (fj_groupby_rows.hip)
     W_NSLOTS
 };
 
@@ -378,6 +379,11 @@ int group_by_merge(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size
 // group id at the row's position, and d_ok the g row indices of the groups' first occurrences; nb <= 2^40, cap_out >= nb
 int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
                   u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out);
+
+// ... with FJ_ALGO_GROUP_ROWS (fj_groupby_rows.hip): d_ov is two planes of cap_out >= nb words - the nb row indices in group order, and
+// the first word of them that belongs to each of the g groups; nb <= 2^40
+int group_rows(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
+               u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out);
 
 // ---- streamed joins (fj_stream.hip) ----
 int stream_open(fj_ctx* c, size_t nb_bound, int build_appends, size_t np_bound, int probe_appends, hipStream_t s, int top_bits,

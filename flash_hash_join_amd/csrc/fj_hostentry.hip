@@ -184,15 +184,23 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;
     const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;                     // a two-column key: build_vals is the second KEY column, *out_keys g first-occurrence row indices
+    const bool grows = gb && (algo & FJ_ALGO_GROUP_ROWS) != 0;                   // the rows of every group: *out_vals nb row indices, then g starts
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;
     const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;            // partial rows in: build_vals is FOUR planes of nb words
+    if (algo >= 0 && (algo & FJ_ALGO_GROUP_ROWS) && !gb)
+        return set_err("fj_join_host: unknown algo %d (FJ_ALGO_GROUP_ROWS modifies FJ_ALGO_GROUP_BY)", algo);
+    if (grows && (algo & (FJ_ALGO_INVERSE | FJ_ALGO_ROW_IDS | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_AGG_MERGE | FJ_ALGO_KEY_PAIR)))
+        return set_err("fj_join_host: FJ_ALGO_GROUP_ROWS cannot be combined with FJ_ALGO_%s (out_vals is taken by the row indices and the groups' starts, and no value column is read)",
+                       (algo & FJ_ALGO_INVERSE) ? "INVERSE" : (algo & FJ_ALGO_ROW_IDS) ? "ROW_IDS" : (algo & FJ_ALGO_AGG_MIN) ? "AGG_MIN" : (algo & FJ_ALGO_AGG_MAX) ? "AGG_MAX" :
+                       (algo & FJ_ALGO_AGG_SIGNED) ? "AGG_SIGNED" : (algo & FJ_ALGO_AGG_FLOAT) ? "AGG_FLOAT" : (algo & FJ_ALGO_AGG_ALL) ? "AGG_ALL" : (algo & FJ_ALGO_AGG_ARG) ? "AGG_ARG" :
+                       (algo & FJ_ALGO_AGG_MERGE) ? "AGG_MERGE" : "KEY_PAIR");
     if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
         return set_err("fj_join_host: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo);
     if (algo >= 0 && (algo & FJ_ALGO_KEY_PAIR) && !gb)
         return set_err("fj_join_host: unknown algo %d (FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE)", algo);
     const int agg_flags = ((bo || gb) ? (FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT) : 0) |  // modifiers of FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: unknown without either
-                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
+                          (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR | FJ_ALGO_GROUP_ROWS : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
         if (amerge) {                                          // FJ_ALGO_AGG_ALL's refusals under this flag's name, ahead of them
@@ -241,6 +249,10 @@ int fj_join_host(int algo, int bloom, int materialize,
             if (!inv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing)");
             if (nb && !bv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR needs build_vals (the second key column, nb words)");
             if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
+        }
+        if (grows) {                                           // the rows of every group: *out_keys g keys, *out_vals nb row indices then g starts
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_GROUP_ROWS needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_host: FJ_ALGO_GROUP_ROWS takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
         }
         if (amin && amax) return set_err("fj_join_host: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax && !aall) return set_err("fj_join_host: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
@@ -347,7 +359,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if ((anti && !bv) || rid || (po && !out_vals)) dbv = dbk;               // (an anti join reads no value, a row-id join none either, nor does a probe-order join's mask)
         else if (gb) {                                                          // the relation's value column: only the sum / min / max forms that return it read it
             if (kpair) { if (h2d_pipelined(c, dbv, bv, nb * 8, piece, &cursor, nullptr)) return 1; }      // (the second key column)
-            else if (!bv || inv) dbv = nullptr;
+            else if (!bv || inv || grows) dbv = nullptr;
             else if (materialize && out_vals && h2d_pipelined(c, dbv, bv, (amerge ? 4 * nb : nb) * 8, piece, &cursor, nullptr)) return 1;   // (FJ_ALGO_AGG_MERGE: four planes)
         }
         else if (bo) {                                                          // the probe side's value column, read for the sums only
@@ -484,7 +496,28 @@ int fj_join_host(int algo, int bloom, int materialize,
         *out_keys = hk; *out_vals = hv;
         joined = true;
     }
-    if (gb && !aall && !aarg) {                                                        // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
+    if (grows) {                                                               // g keys; nb row indices and, behind them, g starts (the device planes have stride nb)
+        void *dok = nullptr, *dov = nullptr;
+        const size_t cap = std::max<size_t>(nb, 1);
+        if (get_buf(c, W_H_OK, cap * 8, &dok) || get_buf(c, W_H_OV, 2 * cap * 8, &dov)) return 1;
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, nullptr, nb, nullptr, 0, js, 64,
+                           &count, (u64*)dok, (u64*)dov, cap, &t)) return 1;
+        const size_t g = (size_t)count;
+        u64* hk = out_keys ? (u64*)malloc(std::max<size_t>(g, 1) * 8) : nullptr;
+        u64* hv = out_vals ? (u64*)malloc(std::max<size_t>(nb + g, 1) * 8) : nullptr;
+        if ((out_keys && !hk) || (out_vals && !hv)) { free(hk); free(hv); return set_err("fj_join_host: out of host memory for %zu rows", nb + g); }
+        auto t1 = std::chrono::steady_clock::now();
+        if (g && hk) HIPCHK(hipMemcpy(hk, dok, g * 8, hipMemcpyDeviceToHost));
+        if (nb && hv) {
+            HIPCHK(hipMemcpy(hv, dov, nb * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hv + nb, (const u64*)dov + cap, g * 8, hipMemcpyDeviceToHost));
+        }
+        d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (out_keys) *out_keys = hk;
+        if (out_vals) *out_vals = hv;
+        joined = true;
+    }
+    if (gb && !aall && !aarg && !grows) {                                                        // g <= nb keys and aggregates; exactly g rows go back (FJ_ALGO_INVERSE: g keys, nb ids)
         void *dok = nullptr, *dov = nullptr;
         const bool ids = inv && (out_vals || kpair);                            // (nobody takes the ids: the plain distinct form - which a two-column key does not have)
         if (inv && !ids) algo &= ~FJ_ALGO_INVERSE;

@@ -689,6 +689,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;   // a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE: d_build_vals is a second KEY column (csrc/fj_groupby_pair.hip)
     const uint64_t* d_kb = nullptr;                         // ... that column
+    const bool grows = gb && (algo & FJ_ALGO_GROUP_ROWS) != 0;   // another modifier of FJ_ALGO_GROUP_BY alone: the rows of every group, two planes of d_out_vals (csrc/fj_groupby_rows.hip)
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
     const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;   // a modifier of that PAIR: the build side is partial rows with four planes (csrc/fj_groupby_merge.hip)
@@ -700,6 +701,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0, afloat = (bo || gb) && (algo & FJ_ALGO_AGG_FLOAT) != 0;
     int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
     const int algo_word = algo;
+    if (algo >= 0 && (algo & FJ_ALGO_GROUP_ROWS) && !gb)
+        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_GROUP_ROWS modifies FJ_ALGO_GROUP_BY)", algo_word);
+    if (grows && (algo & (FJ_ALGO_INVERSE | FJ_ALGO_ROW_IDS | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_AGG_MERGE | FJ_ALGO_KEY_PAIR)))
+        return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the row indices and the groups' starts, and no value column is read)",
+                       (algo & FJ_ALGO_INVERSE) ? "INVERSE" : (algo & FJ_ALGO_ROW_IDS) ? "ROW_IDS" : (algo & FJ_ALGO_AGG_MIN) ? "AGG_MIN" : (algo & FJ_ALGO_AGG_MAX) ? "AGG_MAX" :
+                       (algo & FJ_ALGO_AGG_SIGNED) ? "AGG_SIGNED" : (algo & FJ_ALGO_AGG_FLOAT) ? "AGG_FLOAT" : (algo & FJ_ALGO_AGG_ALL) ? "AGG_ALL" : (algo & FJ_ALGO_AGG_ARG) ? "AGG_ARG" :
+                       (algo & FJ_ALGO_AGG_MERGE) ? "AGG_MERGE" : "KEY_PAIR");
     if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
         return set_err("fj_join_device: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo_word);
     if (algo >= 0 && (algo & FJ_ALGO_KEY_PAIR) && !gb)
@@ -711,7 +719,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR);
+        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR | FJ_ALGO_GROUP_ROWS);
         if (amerge) {                                       // partial rows in, FJ_ALGO_AGG_ALL's outputs out: its refusals under this flag's name, ahead of them
             algo &= ~FJ_ALGO_AGG_MERGE;
             if (many || left || anti || full || allc || po || bo)
@@ -765,6 +773,11 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
             if ((uintptr_t)d_bv & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
             d_kb = d_bv;
         }
+        if (grows) {                                        // the rows of every group: d_out_vals is two planes, the nb row indices and the g starts (no other modifier: refused above)
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
+            if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS needs d_out_keys and d_out_vals (the g distinct keys and two planes of out_capacity words: the nb row indices and the g starts)");
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
+        }
         if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
         if (asigned && !amin && !amax && !aall) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
         if ((amin || amax) && nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs d_build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
@@ -779,8 +792,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
         if (afloat) agg = amin ? FJ_GJ_MIN_F : amax ? FJ_GJ_MAX_F : FJ_GJ_SUM_F;
         if (!amin && !amax && !d_bv) agg = FJ_GJ_COUNT;
-        d_gv = (rid || inv) ? nullptr : d_bv;
-        if (!d_bv || rid || inv) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
+        d_gv = (rid || inv || grows) ? nullptr : d_bv;
+        if (!d_bv || rid || inv || grows) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
     }
     if (bo) {
         // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
@@ -926,6 +939,13 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     if (aarg) {                                             // ... or the row index and the extreme beside it (out_capacity >= nb was checked)
         if (group_by_arg(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
                          afloat ? 2 : asigned ? 1 : 0, amax)) return 1;
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return 0;
+    }
+    if (grows) {                                            // ... or the rows of every group: nb row indices and g starts, never a pending result
+        if (group_rows(c, use_radix, d_bk, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity)) return 1;
         if (out_count) *out_count = count;
         if (timings) *timings = t;
         last_timings() = t;

@@ -1,5 +1,5 @@
 // fj_lds_table_dev.h -- what the extension kernels that keep a linear-probing LDS table share (csrc/fj_group.hip, fj_groupby.hip,
-// fj_groupby_multi.hip, fj_groupby_arg.hip, fj_groupby_merge.hip, fj_groupby_pair.hip, fj_aligned.hip, fj_prepared.hip, fj_outer.hip, fj_many.hip; csrc/fj_join.hip takes fj_chunk_entry): the decoding of chunk lists and
+// fj_groupby_multi.hip, fj_groupby_arg.hip, fj_groupby_merge.hip, fj_groupby_pair.hip, fj_groupby_rows.hip, fj_aligned.hip, fj_prepared.hip, fj_outer.hip, fj_many.hip; csrc/fj_join.hip takes fj_chunk_entry): the decoding of chunk lists and
 // work items every one of them starts with, and, stated once, the table they all build.
 //
 // THE TABLE: TS slots (a power of two) of 64-bit MIXED keys in LDS, all FJ_EMPTY_KEY at rest.  A key's home slot is

@@ -395,6 +395,36 @@ extern "C" {
  * Refused up front, before any device work: the flag without FJ_ALGO_GROUP_BY (an unknown algo); with it but without FJ_ALGO_INVERSE;
  * everything FJ_ALGO_INVERSE and FJ_ALGO_GROUP_BY refuse; a NULL d_build_vals with nb > 0; nb > 2^40. */
 #define FJ_ALGO_KEY_PAIR   0x20000000
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY alone (without it an unknown algo; csrc/fj_groupby_rows.hip): the ROWS of every group - the
+ * relation's row indices in group-contiguous order and the offset at which every group starts, a CSR of row indices.  What pandas
+ * groupby().indices, SQL array_agg and the CSR of an edge list by source are, and what a median, a top-k or any segment reduction per
+ * group starts from - without the stable sort of the group ids that FJ_ALGO_INVERSE would need for it.  OR it into `algo` together
+ * with FJ_ALGO_GROUP_BY and a base value (ADAPTIVE, SCALAR or RADIX), materialize = 1:
+ *   d_build_keys       the relation, nb words.  d_build_vals is never read and may be NULL.
+ *   d_out_keys[r]      for r < g: the distinct raw keys; rows [g, nb) may hold anything.
+ *   d_out_vals         TWO planes of out_capacity words each, plane-major:
+ *     plane 0, words [0, nb): the row indices in group order; every i < nb appears exactly once.
+ *     plane 1, words [0, g):  start[r], the first word of plane 0 that belongs to group r.  The starts are strictly increasing,
+ *                        start[0] = 0, and group r owns the words [start[r], start[r + 1]) with start[g] = nb implied:
+ *                        d_build_keys[plane0[j]] == d_out_keys[r] for every j in that range.
+ * *out_count = g.  out_capacity >= nb; d_out_keys and d_out_vals are required (nb > 0) and 8-byte aligned.  The words [nb, out_capacity)
+ * of plane 0 are not written, the words [g, out_capacity) of plane 1 may hold anything, nothing at or beyond word out_capacity of
+ * d_out_keys or word 2 * out_capacity of d_out_vals is touched.  nb == 0: g = 0, nothing is written.  nb <= 2^40.  bloom is ignored.
+ * Never a pending result for fj_emit_pairs.
+ * The order of the groups is unspecified, but keys and starts share it.  The order of the rows INSIDE a group is unspecified too and
+ * may differ from run to run: an atomic counter per group hands out the places.  A caller that needs the rows of a group ascending
+ * sorts inside the groups.
+ * fj_timings as for FJ_ALGO_INVERSE: the relation's passes in build_phase_ms, everything behind them - three launches: count, scan,
+ * place - in join_ms = probe_phase_ms, emit_ms = 0, fell_back = 1 when a final partition held more than 7680 distinct keys and the
+ * call ran again on the HBM table (which defines all nb + g words itself).  A key that owns a large share of the rows is streamed by
+ * ONE workgroup, three times; exact at any distribution, the time is not flat.
+ * fj_join_host: *out_keys is a malloc'ed array of exactly g keys, *out_vals one of exactly nb + g words - the nb row indices, then the
+ * g starts; a NULL pointer drops that output.
+ * Refused up front, before any device work: the flag without FJ_ALGO_GROUP_BY (an unknown algo); combined with FJ_ALGO_INVERSE,
+ * FJ_ALGO_ROW_IDS, FJ_ALGO_AGG_MIN, FJ_ALGO_AGG_MAX, FJ_ALGO_AGG_SIGNED, FJ_ALGO_AGG_FLOAT, FJ_ALGO_AGG_ALL, FJ_ALGO_AGG_ARG,
+ * FJ_ALGO_AGG_MERGE or FJ_ALGO_KEY_PAIR; materialize = 0; fj_join_device with d_out_keys == NULL or d_out_vals == NULL (and nb > 0),
+ * out_capacity < nb or a misaligned output; nb > 2^40; and whatever FJ_ALGO_GROUP_BY refuses (a probe side, the join flags). */
+#define FJ_ALGO_GROUP_ROWS 0x40000000
 
 typedef struct fj_ctx fj_ctx;
 

@@ -6,10 +6,13 @@ form, appended to --out:
       factorize followed by zeros(g).index_add_(0, codes, values) (the sums from the ids: one grouping, then any aggregate);
       the float64 aggregates (float64=True) beside their integer forms: group_by_sum_f64 / group_by_min_f64, group_join_sum and
       group_join_sum_f64 (the g distinct keys as the build side), Index.group_sum and Index.group_sum_f64 (an index on them, built
-      outside the timed region), and factorize+index_add_f64, the torch composition on a float64 column
+      outside the timed region), and factorize+index_add_f64, the torch composition on a float64 column;
+      group_rows (FJ_ALGO_GROUP_ROWS): the rows of every group as a CSR of row indices - group keys, offsets, row_index
   (b) the composition: torch.unique(keys, return_counts=True) (counts), torch.unique(keys, return_inverse=True) alone (the ids), or
       followed by zeros(g).index_add_(0, inverse, values) (sums) / full(g, INT64_MAX).scatter_reduce_(0, inverse, values, "amin")
-      (minima) - the wall time of the steps between two device synchronisations
+      (minima) - the wall time of the steps between two device synchronisations;
+      the two ways to the CSR of group_rows without it: "factorize+sort+bincount+cumsum" (factorize, a stable torch.sort of the
+      codes, bincount and cumsum) and "torch.unique(return_inverse+return_counts)+argsort" (a stable argsort of the inverse, cumsum)
 
     python tools/group_by_probe.py [--workloads u1m,distinct,hot,b1g] [--forms a,b] [--names factorize,...] [--steps 8] [--warmup 2]
                                    [--out profiles/group_by_probe.jsonl]
@@ -130,6 +133,20 @@ def main():
             uk, inv = torch.unique(keys, return_inverse=True)
             return uk.numel(), None, uk, inv
 
+        def composed_rows_factorize():
+            n_g, _, codes, uk = flash_join.factorize(keys)
+            _, row_index = torch.sort(codes, stable=True)
+            offsets = torch.zeros(n_g + 1, dtype=torch.int64, device=keys.device)
+            torch.cumsum(torch.bincount(codes, minlength=n_g), 0, out=offsets[1:])
+            return n_g, None, uk, offsets, row_index
+
+        def composed_rows_unique():
+            uk, inv, cnt = torch.unique(keys, return_inverse=True, return_counts=True)
+            row_index = torch.argsort(inv, stable=True)
+            offsets = torch.zeros(uk.numel() + 1, dtype=torch.int64, device=keys.device)
+            torch.cumsum(cnt, 0, out=offsets[1:])
+            return uk.numel(), None, uk, offsets, row_index
+
         def factorize_sum(v=vals):
             n_g, sec, codes, uk = flash_join.factorize(keys)
             return n_g, sec, uk, torch.zeros(n_g, dtype=v.dtype, device=keys.device).index_add_(0, codes, v)
@@ -165,11 +182,14 @@ def main():
                      ("a", "group_join_sum_f64", joined(lambda: flash_join.group_join_sum(dkeys, keys, fvals, float64=True))),
                      ("a", "Index.group_sum", joined(lambda ix: ix.group_sum(keys, vals))),
                      ("a", "Index.group_sum_f64", joined(lambda ix: ix.group_sum(keys, fvals, float64=True))),
-                     ("a", "factorize+index_add_f64", lambda: factorize_sum(fvals))]
+                     ("a", "factorize+index_add_f64", lambda: factorize_sum(fvals)),
+                     ("a", "group_rows", lambda: flash_join.group_rows(keys))]
         if "b" in forms:
             runs += [("b", "torch.unique(return_counts)", composed_count), ("b", "torch.unique(return_inverse)", composed_inverse),
                      ("b", "torch.unique(return_inverse)+index_add", composed_sum),
-                     ("b", "torch.unique(return_inverse)+scatter_reduce_amin", composed_min)]
+                     ("b", "torch.unique(return_inverse)+scatter_reduce_amin", composed_min),
+                     ("b", "factorize+sort+bincount+cumsum", composed_rows_factorize),
+                     ("b", "torch.unique(return_inverse+return_counts)+argsort", composed_rows_unique)]
         if args.names:
             runs = [r for r in runs if r[1] in args.names.split(",")]
         for form, name, fn in runs:
