@@ -180,40 +180,25 @@ hipError_t fj_launch_probe_order_join(const FjLdsJoinArgs& a, bool first, u64 np
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The table holds first-occurrence row indices (d_ov != nullptr) or
-// keys only (the mask form)
+// the global-table form (fj_host.h).  The table holds first-occurrence row indices (d_ov != nullptr) or keys only (the mask form)
 static int join_probe_order_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, hipStream_t s,
                                    fj_timings* t, u64* out_count, unsigned char* d_mask, u64* d_ov, bool rid) {
     const bool vals = d_ov != nullptr;
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (vals) { if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1; a.tvals = (u64*)p; }
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.bv = (vals && !rid) ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    if (gt_open(c, nb, vals ? cap : 0, s, &a, &a.tvals)) return 1;
+    a.bk = bk; a.bv = (vals && !rid) ? bv : nullptr; a.pk = pk; a.np = np;
     a.out_vals = d_ov; a.row_ids = rid ? 1u : 0u;
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
     HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));           // (row index minimum)
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
     if (vals) HIPCHK(hipMemsetAsync(a.tvals, 0xFF, cap * 8, s));
     HIPCHK(fj_launch_gt_build_first(a, vals, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_probe_order(a, &c->d_sc->expected, d_mask, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
+    if (gt_close(c, s, t)) return 1;
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (hits + misses != np) return set_err("internal error: probe-order join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
     *out_count = hits;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -267,7 +252,7 @@ int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, si
     HIPCHK(fj_launch_probe_order_join(ja, rid, np, &c->d_sc->expected, d_mask, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     if (vals && !rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and every row stored again
@@ -286,15 +271,11 @@ int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, si
         HIPCHK(fj_launch_probe_order_join(ja, true, np, &c->d_sc->expected, d_mask, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     }
     plan_timings(c, plan, ja.nparts, evc, t);
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_probe_order_global(c, bk, bv, nb, pk, np, s, &t2, out_count, d_mask, d_ov, rid)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return join_probe_order_global(c, bk, bv, nb, pk, np, s, g, out_count, d_mask, d_ov, rid); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a probe row's position lies beyond the probe side");
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (hits + misses != np) return set_err("internal error: probe-order join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);

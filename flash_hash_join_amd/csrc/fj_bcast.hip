@@ -645,7 +645,7 @@ int fj_bcast_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* ti
         pd.lds = bc.ja; pd.toff = bc.pit.toff; pd.src = bc.src; pd.nb_total = bc.nb_total;
     }
     bc = BcastState();
-    if (err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     // a final partition beyond the LDS table (> ~8000 build keys in all: build-side skew): the caller takes another form
     if (err & (FJ_STAT_RETRY | FJ_ERR_LDS_FULL)) return set_err("build broadcast: a final partition does not fit the LDS table (skewed build keys)");

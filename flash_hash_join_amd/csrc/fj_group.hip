@@ -28,8 +28,7 @@
 // flushed row (HBM), min / max one integer atomic on the raw bits chosen by the value's sign bit (gj_combine, csrc/fj_group_dev.h);
 // identities +0.0, +inf, -inf.  Every word they touch is LDS or device memory of the call (DESIGN.md "Float aggregates").
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole join on the global HBM table (the kernels at
-// the end of this file), timings.fell_back = 1.
+// Fallback: FJ_ERR_LDS_FULL; the HBM-table kernels end this file.
 #include "fj_host.h"
 #include "fj_group_dev.h"
 
@@ -267,43 +266,32 @@ hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigne
     if (!a.total || !cnt || (!out_cnt && !out_sum) || (out_sum && (!sum || !pv))) return hipErrorInvalidValue;
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_sum && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     if (a.np) {
-        const u64 rounds = (a.np + 1023) / 1024;
         void (*probe)(FjGtArgs, const u64*, unsigned long long*, unsigned long long*) =
             agg == FJ_GJ_MIN_U ? fj_gt_group_probe_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_probe_kernel<FJ_GJ_MIN_S> :
             agg == FJ_GJ_MAX_U ? fj_gt_group_probe_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_probe_kernel<FJ_GJ_MAX_S> :
             agg == FJ_GJ_SUM_F ? fj_gt_group_probe_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_probe_kernel<FJ_GJ_MIN_F> :
             agg == FJ_GJ_MAX_F ? fj_gt_group_probe_kernel<FJ_GJ_MAX_F> :
             fj_gt_group_probe_kernel<FJ_GJ_SUM>;                                  // (the count form: sum == nullptr)
-        hipLaunchKernelGGL(probe, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
+        hipLaunchKernelGGL(probe, dim3(fjh::gt_grid(a.np)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
     }
-    if (a.nb) {
-        const u64 rounds = (a.nb + 1023) / 1024;
-        hipLaunchKernelGGL(fj_gt_group_flush_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, cnt, sum, out_cnt, out_sum);
-    }
+    if (a.nb) hipLaunchKernelGGL(fj_gt_group_flush_kernel, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, cnt, sum, out_cnt, out_sum);
     return hipGetLastError();
 }
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  Counts are always kept (P is their sum over the build rows)
+// the global-table form (fj_host.h).  Counts are always kept (P is their sum over the build rows)
 // agg: what d_sum receives (FJ_GJ_SUM or a min / max form); its accumulators start at the aggregate's identity, the empty key's too
 static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk, const u64* pv, size_t np, hipStream_t s,
                              fj_timings* t, u64* out_count, u64* d_cnt, u64* d_sum, int agg) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
-    FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
+    const u64 cap = gt_capacity(nb);
     const size_t acc_words = (d_sum ? 2 : 1) * (cap + 1);
-    if (get_buf(c, W_GT_VALS, acc_words * 8, &p)) return 1;
-    unsigned long long* cnt = (unsigned long long*)p;
+    FjGtArgs a{};
+    u64* acc = nullptr;
+    if (gt_open(c, nb, acc_words, s, &a, &acc)) return 1;
+    unsigned long long* cnt = (unsigned long long*)acc;
     unsigned long long* sum = d_sum ? cnt + cap + 1 : nullptr;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    a.bk = bk; a.pk = pk; a.np = np;
     const bool own_fill = sum && fj_group_identity(agg) != 0;                    // (sum, unsigned max: one memset serves both arrays)
     HIPCHK(hipMemsetAsync(cnt, 0, (own_fill ? cap + 1 : acc_words) * 8, s));
     if (own_fill) HIPCHK(fj_launch_group_fill((u64*)sum, cap + 1, agg, s));
@@ -311,14 +299,8 @@ static int join_group_global(fj_ctx* c, const u64* bk, size_t nb, const u64* pk,
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_group(a, d_sum ? agg : FJ_GJ_COUNT, pv, cnt, sum, d_cnt, d_sum, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
+    if (gt_close(c, s, t)) return 1;
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -377,7 +359,7 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
     }
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     if (!d_cnt && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // sums (minima, maxima) alone over duplicated build keys: the hits are not P.  The count form once, without an output, for P
@@ -388,12 +370,8 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
         if (read_scalars(c, s)) return 1;
     }
     plan_timings(c, plan, ja.nparts, evc, t);
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_group_global(c, bk, nb, pk, pv, np, s, &t2, out_count, d_cnt, d_sum, agg)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return join_group_global(c, bk, nb, pk, pv, np, s, g, out_count, d_cnt, d_sum, agg); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a build row's position lies beyond the build side");
     *out_count = c->h_sc->total;
     return 0;

@@ -24,8 +24,7 @@
 // Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition, and its LDS atomics hit
 // one address; fewer than ~256 distinct keys leave CUs idle.  Correct at any distribution (DESIGN.md "Group-by on one relation").
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than GJ_LIMIT distinct keys) -> the
-// whole call on the global HBM table (the kernels at the end of this file) from cursor 0, timings.fell_back = 1.
+// Fallback: FJ_ERR_LDS_FULL, a partition of more than GJ_LIMIT distinct keys; the HBM-table kernels end this file.
 #include "fj_host.h"
 #include "fj_group_dev.h"
 
@@ -358,22 +357,20 @@ hipError_t fj_launch_group_by_inverse(const FjGroupByArgs& a, hipStream_t s) {
 hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s) {
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    const u64 rounds = (a.nb + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*) =
         agg == FJ_GJ_COUNT ? fj_gt_group_by_combine_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM> :
         agg == FJ_GJ_MIN_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_S> :
         agg == FJ_GJ_MAX_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_S> :
         agg == FJ_GJ_SUM_F ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_F> :
         fj_gt_group_by_combine_kernel<FJ_GJ_MAX_F>;
-    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, vals, acc);
+    hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, acc);
     return hipGetLastError();
 }
 
 hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
                                        unsigned long long* cursor, u32* err, hipStream_t s, u64* ids) {
     if (!cursor || !err || (out_vals && (!acc || !out_keys)) || (ids && (!out_keys || out_vals))) return hipErrorInvalidValue;
-    const u64 rounds = (a.cap_mask + 2 + 1023) / 1024;
-    hipLaunchKernelGGL(ids ? fj_gt_group_by_sweep_kernel<true> : fj_gt_group_by_sweep_kernel<false>, dim3((u32)(rounds < 4096 ? rounds : 4096)),
+    hipLaunchKernelGGL(ids ? fj_gt_group_by_sweep_kernel<true> : fj_gt_group_by_sweep_kernel<false>, dim3(fjh::gt_grid(a.cap_mask + 2)),
                        dim3(1024), 0, s, a, acc, out_keys, out_vals, out_capacity, cursor, err, ids);
     return hipGetLastError();
 }
@@ -381,33 +378,23 @@ hipError_t fj_launch_gt_group_by_sweep(const FjGtArgs& a, const u64* acc, u64* o
 hipError_t fj_launch_gt_group_by_inverse(const FjGtArgs& a, const u64* ids, u64* out_vals, u64 out_capacity, hipStream_t s) {
     if (!ids || !out_vals) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    const u64 rounds = (a.nb + 1023) / 1024;
-    hipLaunchKernelGGL(fj_gt_group_by_inverse_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, ids, out_vals, out_capacity);
+    hipLaunchKernelGGL(fj_gt_group_by_inverse_kernel, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, ids, out_vals, out_capacity);
     return hipGetLastError();
 }
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts at 0: whatever an
-// abandoned partitioned attempt wrote is overwritten.  rid: the table build itself keeps every key's first row index
-// (fj_gt_build_first_kernel with values), so the accumulators are its value plane and no combine pass runs.  inv: the value plane
-// receives the row the sweep hands to every slot instead, and one more kernel, behind the sweep on the same stream, stores every row's
-// id at the row's position: all nb words of d_ov, whatever an abandoned partitioned attempt left there.
+// the global-table form (fj_host.h).  rid: the table build itself keeps every key's first row index (fj_gt_build_first_kernel with
+// values), so the accumulators are its value plane and no combine pass runs.  inv: the value plane receives the row the sweep hands to
+// every slot instead, and one more kernel, behind the sweep on the same stream, stores every row's id at the row's position: all nb
+// words of d_ov, whatever an abandoned partitioned attempt left there.
 static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                            u64* d_ok, u64* d_ov, size_t cap_out, int agg, bool rid, bool inv) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
     u64* acc = nullptr;
-    if (d_ov) { if (get_buf(c, W_GT_VALS, (cap + 1) * 8, &p)) return 1; acc = (u64*)p; }
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    if (gt_open(c, nb, d_ov ? cap + 1 : 0, s, &a, &acc)) return 1;
+    a.bk = bk;
     if (inv) HIPCHK(fj_launch_gt_build_first(a, false, s));  // (the id plane needs no fill: the sweep writes every word that is read)
     else if (acc && rid) {                                   // (row index minimum: all ones at rest; the empty key's word is the table's last)
         a.tvals = acc; a.empty_val = acc + cap;
@@ -426,15 +413,9 @@ static int group_by_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, h
         HIPCHK(fj_launch_gt_group_by_sweep(a, nullptr, d_ok, nullptr, cap_out, &c->d_sc->total, &c->d_sc->err, s, acc));
         HIPCHK(fj_launch_gt_group_by_inverse(a, acc, d_ov, cap_out, s));
     } else HIPCHK(fj_launch_gt_group_by_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
+    if (gt_close(c, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return distinct_error();
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -453,35 +434,19 @@ int group_by(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb,
     if (rid) agg = FJ_GJ_MIN_U;
     if (!use_radix) return group_by_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, agg, rid, inv);
 
-    const Plan plan = make_plan(nb, top_bits, false);
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    RelAttempt r;
+    const RelBeside beside = (rid || inv) ? REL_POSITIONS : agg != FJ_GJ_COUNT ? REL_VALUES : REL_KEYS_ONLY;
+    if (rel_open(c, bk, beside, bv, nb, top_bits, 0, s, &r)) return 1;
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, agg != FJ_GJ_COUNT || inv, nb, plan, top_bits);
-    it.vals_pos = rid || inv;                                // the rows' positions travel through the passes
-    if (run_passes(c, it, bk, (agg != FJ_GJ_COUNT && !rid && !inv) ? bv : nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     if (inv) HIPCHK(fj_launch_group_by_inverse(ga, s));
     else HIPCHK(fj_launch_group_by(ga, agg, d_ok != nullptr, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (group_by_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, agg, rid, inv)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
-    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_by_global(c, bk, bv, nb, s, g, out_count, d_ok, d_ov, cap_out, agg, rid, inv); });
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return distinct_error();
     *out_count = c->h_sc->total;
     return 0;
 }

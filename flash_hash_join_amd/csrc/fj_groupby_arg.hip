@@ -31,8 +31,8 @@
 // Every group has a row, so every position is a row index - also where the extreme equals the aggregate's identity: the rows that
 // hold it compare equal to the untouched plane.  Only a group whose extreme is a NaN keeps all ones (-1 as int64).
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than 3840 distinct keys) -> nothing
-// written, the whole call on the global HBM table (the kernels at the end of this file) from cursor 0, timings.fell_back = 1.
+// Fallback: FJ_ERR_LDS_FULL, a partition of more than 3840 distinct keys, which writes nothing; the HBM-table
+// kernels end this file.
 //
 // Weak spot: a key that owns a large share of the rows is streamed by the one workgroup of its partition - here TWICE, since such a
 // partition is longer than one round - and where its values tie, the position atomics hit one address too.  Correct at any
@@ -285,47 +285,34 @@ hipError_t fj_launch_group_by_arg(const FjGroupByArgs& a, const u64* vals, u64 n
 hipError_t fj_launch_gt_group_by_arg_resolve(const FjGtArgs& a, int kind, const u64* vals, const u64* ext, u64* pos, hipStream_t s) {
     if (kind < GR_UNSIGNED || kind > GR_FLOAT || !vals || !ext || !pos) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    const u64 rounds = (a.nb + 1023) / 1024;
     hipLaunchKernelGGL(kind == GR_FLOAT ? fj_gt_group_by_arg_resolve_kernel<GR_FLOAT> : fj_gt_group_by_arg_resolve_kernel<GR_UNSIGNED>,
-                       dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, vals, ext, pos);      // (signed words compare equal by bits too)
+                       dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, ext, pos);      // (signed words compare equal by bits too)
     return hipGetLastError();
 }
 
 hipError_t fj_launch_gt_group_by_arg_sweep(const FjGtArgs& a, const u64* ext, const u64* pos, u64* out_keys, u64* out_vals, u64 out_capacity,
                                            unsigned long long* cursor, u32* err, hipStream_t s) {
     if (!cursor || !err || !ext || !pos || !out_keys || !out_vals || !out_capacity) return hipErrorInvalidValue;
-    const u64 rounds = (a.cap_mask + 2 + 1023) / 1024;
-    hipLaunchKernelGGL(fj_gt_group_by_arg_sweep_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, ext, pos, out_keys, out_vals,
+    hipLaunchKernelGGL(fj_gt_group_by_arg_sweep_kernel, dim3(fjh::gt_grid(a.cap_mask + 2)), dim3(1024), 0, s, a, ext, pos, out_keys, out_vals,
                        out_capacity, cursor, err);
     return hipGetLastError();
 }
 
 namespace fjh {
 
-static int gr_agg(int kind, bool is_max) {
-    return kind == GR_FLOAT ? (is_max ? FJ_GJ_MAX_F : FJ_GJ_MIN_F) : kind == GR_SIGNED ? (is_max ? FJ_GJ_MAX_S : FJ_GJ_MIN_S) : (is_max ? FJ_GJ_MAX_U : FJ_GJ_MIN_U);
-}
+static_assert(GR_UNSIGNED == KIND_UNSIGNED && GR_SIGNED == KIND_SIGNED && GR_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts at 0: whatever an
-// abandoned partitioned attempt wrote is overwritten.  Every kernel on the one stream
+// the global-table form (fj_host.h): a plane of extremes and a plane of positions, capacity + 1 words each.  Every kernel on the one
+// stream
 static int group_by_arg_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                                u64* d_ok, u64* d_ov, size_t cap_out, int kind, bool is_max) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
-    const u64 plane = cap + 1;
+    const u64 plane = gt_capacity(nb) + 1;
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (get_buf(c, W_GT_VALS, 2 * plane * 8, &p)) return 1;
-    u64* ext = (u64*)p;
+    u64* ext = nullptr;
+    if (gt_open(c, nb, 2 * plane, s, &a, &ext)) return 1;
     u64* pos = ext + plane;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
-    const int agg = gr_agg(kind, is_max);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    a.bk = bk;
+    const int agg = kind_agg(kind, is_max ? PLANE_MAX : PLANE_MIN);
     HIPCHK(fj_launch_gt_build_first(a, false, s));
     HIPCHK(fj_launch_group_fill(ext, plane, agg, s));
     HIPCHK(hipMemsetAsync(pos, 0xFF, plane * 8, s));
@@ -334,15 +321,9 @@ static int group_by_arg_global(fj_ctx* c, const u64* bk, const u64* bv, size_t n
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_group_by_arg_resolve(a, kind, bv, ext, pos, s));
     HIPCHK(fj_launch_gt_group_by_arg_sweep(a, ext, pos, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct keys than the relation has rows");
+    if (gt_close(c, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return distinct_error();
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -356,33 +337,16 @@ int group_by_arg(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t
     if (nb == 0) return 0;
     if (!use_radix) return group_by_arg_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, kind, is_max);
 
-    const Plan plan = make_plan(nb, top_bits, false, GR_TS / 2);     // aim at half of the table's 4096 slots per partition
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    RelAttempt r;      // aim at half of the table's 4096 slots per partition; the rows' positions travel, the kernel gathers the values
+    if (rel_open(c, bk, REL_POSITIONS, nullptr, nb, top_bits, GR_TS / 2, s, &r)) return 1;
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    it.vals_pos = true;                                      // the rows' positions travel through the passes; the kernel gathers the values
-    if (run_passes(c, it, bk, nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(fj_launch_group_by_arg(ga, bv, nb, kind, is_max, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (group_by_arg_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, kind, is_max)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_by_arg_global(c, bk, bv, nb, s, g, out_count, d_ok, d_ov, cap_out, kind, is_max); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by met a row position beyond the relation, or more distinct keys than rows");
     *out_count = c->h_sc->total;
     return 0;

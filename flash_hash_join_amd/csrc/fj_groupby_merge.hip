@@ -22,8 +22,8 @@
 // its gathers behind them.  The emit is fj_group_by_all_kernel's: one global atomic reserves the partition's rows on the call's cursor,
 // ballot + popcount ranks the occupied slots, a slot writes its key and its four aggregates at stride out_capacity.
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than 1920 distinct keys) -> nothing
-// written, the whole call on the global HBM table (the kernels at the end of this file) from cursor 0, timings.fell_back = 1.
+// Fallback: FJ_ERR_LDS_FULL, a partition of more than 1920 distinct keys, which writes nothing; the HBM-table
+// kernels end this file.
 //
 // Weak spot: a hot key's partial rows are still one workgroup's and its four LDS atomics per row hit four addresses - but a hot key now
 // has one row per batch (shard, slice), not one per input row.  Correct at any distribution.
@@ -227,10 +227,9 @@ hipError_t fj_launch_group_by_merge(const FjGroupByArgs& a, const u64* planes, u
 hipError_t fj_launch_gt_group_by_merge_combine(const FjGtArgs& a, int kind, const u64* planes, u64* acc, hipStream_t s) {
     if (kind < GM_UNSIGNED || kind > GM_FLOAT || !acc || !planes) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    const u64 rounds = (a.nb + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*) = kind == GM_UNSIGNED ? fj_gt_group_by_merge_combine_kernel<GM_UNSIGNED> :
                                                kind == GM_SIGNED ? fj_gt_group_by_merge_combine_kernel<GM_SIGNED> : fj_gt_group_by_merge_combine_kernel<GM_FLOAT>;
-    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, planes, acc);
+    hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, planes, acc);
     return hipGetLastError();
 }
 
@@ -241,40 +240,23 @@ static int merge_outcap_error(u64 g, size_t cap_out) {
                    (unsigned long long)g, cap_out);
 }
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts at 0: whatever an
-// abandoned partitioned attempt wrote is overwritten
+static_assert(GM_UNSIGNED == KIND_UNSIGNED && GM_SIGNED == KIND_SIGNED && GM_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
+
+// the global-table form (fj_host.h): group_by_all's accumulator planes and sweep behind this file's combine kernel
 static int group_by_merge_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                                  u64* d_ok, u64* d_ov, size_t cap_out, int kind) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
-    const u64 plane = cap + 1;
+    const u64 plane = gt_capacity(nb) + 1;
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (get_buf(c, W_GT_VALS, 4 * plane * 8, &p)) return 1;
-    u64* acc = (u64*)p;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
-    const int aggs[4] = {FJ_GJ_COUNT, kind == GM_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM,
-                         kind == GM_FLOAT ? FJ_GJ_MIN_F : kind == GM_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U,
-                         kind == GM_FLOAT ? FJ_GJ_MAX_F : kind == GM_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U};
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    u64* acc = nullptr;
+    if (gt_open(c, nb, 4 * plane, s, &a, &acc)) return 1;
+    a.bk = bk;
     HIPCHK(fj_launch_gt_build_first(a, false, s));
-    for (int j = 0; j < 4; ++j) HIPCHK(fj_launch_group_fill(acc + j * plane, plane, aggs[j], s));
+    for (int j = PLANE_COUNT; j <= PLANE_MAX; ++j) HIPCHK(fj_launch_group_fill(acc + j * plane, plane, kind_agg(kind, j), s));
     HIPCHK(fj_launch_gt_group_by_merge_combine(a, kind, bv, acc, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_group_by_all_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    if (gt_close(c, s, t)) return 1;
     *out_count = c->h_sc->total;
     if (c->h_sc->err & FJ_ERR_OUTCAP) return merge_outcap_error(c->h_sc->total, cap_out);      // (g goes back with the error)
     return 0;
@@ -290,33 +272,16 @@ int group_by_merge(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size
     if (nb == 0) return 0;
     if (!use_radix) return group_by_merge_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, kind);
 
-    const Plan plan = make_plan(nb, top_bits, false, GM_TS / 2);     // aim at half of the table's 2048 slots per partition
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    RelAttempt r;      // aim at half of the table's 2048 slots per partition; the rows' positions travel, the kernel gathers the planes
+    if (rel_open(c, bk, REL_POSITIONS, nullptr, nb, top_bits, GM_TS / 2, s, &r)) return 1;
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    it.vals_pos = true;                                      // the rows' positions travel through the passes; the kernel gathers the planes
-    if (run_passes(c, it, bk, nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(fj_launch_group_by_merge(ga, bv, nb, kind, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        const int rc = group_by_merge_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, kind);
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return rc;
-    }
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_by_merge_global(c, bk, bv, nb, s, g, out_count, d_ok, d_ov, cap_out, kind); });
     *out_count = c->h_sc->total;
     if (c->h_sc->err & FJ_ERR_OUTCAP) return merge_outcap_error(c->h_sc->total, cap_out);      // (g goes back with the error)
     return 0;

@@ -25,8 +25,7 @@
 // aggregates at stride out_capacity.  out_capacity may be smaller than nb here: a row at or past it is not written and raises
 // FJ_ERR_OUTCAP, the cursor still counts it, and the host reports g against the capacity.
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than 3840 distinct keys) -> the
-// whole call on the global HBM table (the kernels at the end of this file) from cursor 0, timings.fell_back = 1.
+// Fallback: FJ_ERR_LDS_FULL, a partition of more than 3840 distinct keys; the HBM-table kernels end this file.
 //
 // Weak spot, as in fj_groupby.hip and four times over: a key that owns a large share of the rows is streamed by one workgroup and
 // its four LDS atomics per row hit four addresses.  Correct at any distribution (DESIGN.md "Group-by with four aggregates").
@@ -214,18 +213,16 @@ hipError_t fj_launch_group_by_all(const FjGroupByArgs& a, int kind, hipStream_t 
 hipError_t fj_launch_gt_group_by_all_combine(const FjGtArgs& a, int kind, const u64* vals, u64* acc, hipStream_t s) {
     if (kind < GA_UNSIGNED || kind > GA_FLOAT || !acc || !vals) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    const u64 rounds = (a.nb + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*) = kind == GA_UNSIGNED ? fj_gt_group_by_all_combine_kernel<GA_UNSIGNED> :
                                                kind == GA_SIGNED ? fj_gt_group_by_all_combine_kernel<GA_SIGNED> : fj_gt_group_by_all_combine_kernel<GA_FLOAT>;
-    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, vals, acc);
+    hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, acc);
     return hipGetLastError();
 }
 
 hipError_t fj_launch_gt_group_by_all_sweep(const FjGtArgs& a, const u64* acc, u64* out_keys, u64* out_vals, u64 out_capacity,
                                            unsigned long long* cursor, u32* err, hipStream_t s) {
     if (!cursor || !err || !acc || !out_keys || !out_vals || !out_capacity) return hipErrorInvalidValue;
-    const u64 rounds = (a.cap_mask + 2 + 1023) / 1024;
-    hipLaunchKernelGGL(fj_gt_group_by_all_sweep_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, acc, out_keys, out_vals,
+    hipLaunchKernelGGL(fj_gt_group_by_all_sweep_kernel, dim3(fjh::gt_grid(a.cap_mask + 2)), dim3(1024), 0, s, a, acc, out_keys, out_vals,
                        out_capacity, cursor, err);
     return hipGetLastError();
 }
@@ -237,42 +234,25 @@ static int outcap_error(u64 g, size_t cap_out) {
                    (unsigned long long)g, cap_out);
 }
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold", and a relation of 2^32 rows or more.  The cursor (the plan's `total`
-// word) starts at 0: whatever an abandoned partitioned attempt wrote is overwritten
+static_assert(GA_UNSIGNED == KIND_UNSIGNED && GA_SIGNED == KIND_SIGNED && GA_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
+
+// the global-table form (fj_host.h); also what a relation of 2^32 rows or more takes.  Four accumulator planes of capacity + 1 words
 static int group_by_all_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                                u64* d_ok, u64* d_ov, size_t cap_out, int kind) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
-    const u64 plane = cap + 1;
+    const u64 plane = gt_capacity(nb) + 1;
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (get_buf(c, W_GT_VALS, 4 * plane * 8, &p)) return 1;
-    u64* acc = (u64*)p;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
-    const int aggs[4] = {FJ_GJ_COUNT, kind == GA_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM,
-                         kind == GA_FLOAT ? FJ_GJ_MIN_F : kind == GA_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U,
-                         kind == GA_FLOAT ? FJ_GJ_MAX_F : kind == GA_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U};
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    u64* acc = nullptr;
+    if (gt_open(c, nb, 4 * plane, s, &a, &acc)) return 1;
+    a.bk = bk;
     HIPCHK(fj_launch_gt_build_first(a, false, s));
-    for (int j = 0; j < 4; ++j) HIPCHK(fj_launch_group_fill(acc + j * plane, plane, aggs[j], s));
+    for (int j = PLANE_COUNT; j <= PLANE_MAX; ++j) HIPCHK(fj_launch_group_fill(acc + j * plane, plane, kind_agg(kind, j), s));
     HIPCHK(fj_launch_gt_group_by_all_combine(a, kind, bv, acc, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     HIPCHK(fj_launch_gt_group_by_all_sweep(a, acc, d_ok, d_ov, cap_out, &c->d_sc->total, &c->d_sc->err, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
-    if (c->h_sc->err & FJ_ERR_OUTCAP) { *out_count = c->h_sc->total; return outcap_error(c->h_sc->total, cap_out); }      // (g goes back with the error)
+    if (gt_close(c, s, t)) return 1;
     *out_count = c->h_sc->total;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return outcap_error(c->h_sc->total, cap_out);      // (g goes back with the error)
     return 0;
 }
 
@@ -287,34 +267,18 @@ int group_by_all(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t
     if ((u64)nb >> 32) use_radix = false;                    // (the LDS table counts in u32)
     if (!use_radix) return group_by_all_global(c, bk, bv, nb, s, t, out_count, d_ok, d_ov, cap_out, kind);
 
-    const Plan plan = make_plan(nb, top_bits, false, GA_TS / 2);     // aim at half of the table's 4096 slots per partition
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    RelAttempt r;
+    if (rel_open(c, bk, REL_VALUES, bv, nb, top_bits, GA_TS / 2, s, &r)) return 1;      // aim at half of the table's 4096 slots per partition
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    if (run_passes(c, it, bk, bv, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(fj_launch_group_by_all(ga, kind, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        const int rc = group_by_all_global(c, bk, bv, nb, s, &t2, out_count, d_ok, d_ov, cap_out, kind);
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return rc;
-    }
-    if (c->h_sc->err & FJ_ERR_OUTCAP) { *out_count = c->h_sc->total; return outcap_error(c->h_sc->total, cap_out); }      // (g goes back with the error)
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_by_all_global(c, bk, bv, nb, s, g, out_count, d_ok, d_ov, cap_out, kind); });
     *out_count = c->h_sc->total;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return outcap_error(c->h_sc->total, cap_out);      // (g goes back with the error)
     return 0;
 }
 

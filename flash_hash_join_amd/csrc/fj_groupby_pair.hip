@@ -30,9 +30,8 @@
 // word and position plus the round's slot words and own pairs in 118 of the 128 VGPRs, no scratch; at four rows it is 66
 // (profiles/group_by_pair_kernel_resources.txt).  Eight keep twice as many gathers in flight per thread.
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL (a partition of more than 7680 distinct words) or
-// FJ_ERR_PAIR_COLLISION -> the whole call on the global HBM table of ROW INDICES (the kernels at the end of this file) from cursor 0,
-// timings.fell_back = 1.  That form compares pairs, never words, and defines all nb ids and all g first rows by itself.
+// Fallback: FJ_ERR_LDS_FULL (a partition of more than 7680 distinct words) or FJ_ERR_PAIR_COLLISION; the HBM
+// table holds ROW INDICES (the kernels at the end of this file) and compares pairs, never words.
 //
 // Weak spot: a pair that owns a large share of the rows is streamed TWICE by the one workgroup of its partition, its position atomics
 // hit one address, and its rows' representative reads hit one line.  Correct at any distribution (DESIGN.md "Two-column keys").
@@ -259,8 +258,6 @@ __global__ __launch_bounds__(1024) void fj_gt_pair_inverse_kernel(const u64* __r
     }
 }
 
-u32 gp_grid(u64 n) { const u64 rounds = (n + 1023) / 1024; return (u32)(rounds < 4096 ? (rounds ? rounds : 1) : 4096); }
-
 hipError_t launch_pair_lds(const FjGroupByArgs& a, const u64* A, const u64* B, u64 nrows, hipStream_t s) {
     if (!a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !A || !B) return hipErrorInvalidValue;
     if (a.out_capacity < nrows || nrows > (1ull << GP_POS_BITS)) return hipErrorInvalidValue;      // (every row may be a group of its own; a position takes 40 bits)
@@ -277,39 +274,26 @@ extern "C" uint64_t fj_key_pair64(uint64_t a, uint64_t b) { return fj_key_pair(a
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table or of two pairs on one combined word,
-// and FJ_ALGO_SCALAR under "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  The cursor (the plan's `total` word) starts
-// at 0; the three kernels run in order on the one stream and define every one of the nb ids and all g first rows, whatever an
-// abandoned partitioned attempt wrote
+// the global-table form (fj_host.h), also the fallback of two pairs on one combined word.  The key plane holds row indices, the value
+// plane the slots' ids; the three kernels run in order on the one stream and define every one of the nb ids and all g first rows
 static int group_by_pair_global(fj_ctx* c, const u64* ka, const u64* kb, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                                 u64* d_ok, u64* d_ov, size_t cap_out) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1;
-    u64* tab = (u64*)p;
-    if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1;
-    u64* ids = (u64*)p;                                      // (no fill: the sweep writes every word the inverse kernel reads)
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(tab, 0xFF, cap * 8, s));
-    hipLaunchKernelGGL(fj_gt_pair_build_kernel, dim3(gp_grid(nb)), dim3(1024), 0, s, ka, kb, (u64)nb, tab, cap - 1);
+    const u64 cap = gt_capacity(nb);
+    FjGtArgs a{};
+    u64* ids = nullptr;                                      // (no fill: the sweep writes every word the inverse kernel reads)
+    if (gt_open(c, nb, cap, s, &a, &ids)) return 1;
+    u64* tab = a.tkeys;
+    hipLaunchKernelGGL(fj_gt_pair_build_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, ka, kb, (u64)nb, tab, cap - 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    hipLaunchKernelGGL(fj_gt_pair_sweep_kernel, dim3(gp_grid(cap)), dim3(1024), 0, s, tab, cap - 1, ids, d_ok, (u64)cap_out, &c->d_sc->total, &c->d_sc->err);
+    hipLaunchKernelGGL(fj_gt_pair_sweep_kernel, dim3(gt_grid(cap)), dim3(1024), 0, s, tab, cap - 1, ids, d_ok, (u64)cap_out, &c->d_sc->total, &c->d_sc->err);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(fj_gt_pair_inverse_kernel, dim3(gp_grid(nb)), dim3(1024), 0, s, ka, kb, (u64)nb, tab, cap - 1, ids, d_ov, (u64)cap_out);
+    hipLaunchKernelGGL(fj_gt_pair_inverse_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, ka, kb, (u64)nb, tab, cap - 1, ids, d_ov, (u64)cap_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
+    if (gt_close(c, s, t)) return 1;
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by found more distinct pairs than the relation has rows");
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -329,7 +313,7 @@ int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_
     begin_plan(c);
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     if (clear_plan_scalars(c, s)) return 1;
-    hipLaunchKernelGGL(fj_pair_combine_kernel, dim3(gp_grid(nb)), dim3(1024), 0, s, ka, kb, words, (u64)nb);
+    hipLaunchKernelGGL(fj_pair_combine_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, ka, kb, words, (u64)nb);
     HIPCHK(hipGetLastError());
     FjGroupByArgs ga{};
     PassIter it;
@@ -342,18 +326,9 @@ int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(launch_pair_lds(ga, ka, kb, nb, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the kernel alone)
-    if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_PAIR_COLLISION)) {      // a partition beyond the LDS table, or two pairs on one word: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (group_by_pair_global(c, ka, kb, nb, s, &t2, out_count, d_ok, d_ov, cap_out)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (rel_close(c, plan, ga.nparts, s, t)) return 1;
+    if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_PAIR_COLLISION))        // a partition beyond the LDS table, or two pairs on one word: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_by_pair_global(c, ka, kb, nb, s, g, out_count, d_ok, d_ov, cap_out); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by met a row position beyond the relation, or more distinct pairs than rows");
     *out_count = c->h_sc->total;
     return 0;

@@ -24,8 +24,8 @@
 // Weak spot, as in fj_groupby.hip: a key that owns a large share of the rows is streamed by the one workgroup of its partition -
 // three times here - and in stream 2 all its rows bump one LDS word.  Correct at any distribution (DESIGN.md "The rows of every group").
 //
-// Fallback, decided by the host from the device error word: FJ_ERR_LDS_FULL -> the whole call on the global HBM table (the kernels
-// at the end of this file), timings.fell_back = 1.  The count kernel sees the overflow, so the abandoned attempt wrote no output.
+// Fallback: FJ_ERR_LDS_FULL; the HBM-table kernels end this file.  The count kernel sees the overflow, so the
+// abandoned attempt wrote no output.
 // No kernel here waits on another workgroup.
 #include "fj_host.h"
 #include "fj_group_dev.h"
@@ -344,27 +344,25 @@ hipError_t launch_rows_lds(const FjGroupRowsArgs& a, hipStream_t s, u64* group_b
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  It defines all nb row words, all g keys and all g starts itself
+static int rows_outcap_error() {
+    return set_err("internal error: FJ_ALGO_GROUP_ROWS met a place beyond the relation's rows, or more distinct keys than rows");
+}
+
+// the global-table form (fj_host.h): a count per slot, scanned per tile of GJ_TS slots.  It defines all nb row words, all g keys and
+// all g starts itself
 static int group_rows_global(fj_ctx* c, const u64* bk, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,
                              u64* d_ok, u64* d_rows, u64* d_starts, size_t cap_out) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     const u64 ntiles64 = (cap + 1 + GJ_TS - 1) / GJ_TS;
     if (ntiles64 > 0x7FFFFFFFull) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS on the HBM table takes fewer than 2^43 rows, got %zu", nb);
     const u32 ntiles = (u32)ntiles64;
-    FjGtArgs a{};
     void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (get_buf(c, W_GT_VALS, ntiles64 * GJ_TS * 8, &p)) return 1;              // (whole tiles: the slots behind capacity + 1 are never read)
-    u64* cnt = (u64*)p;
     if (get_buf(c, W_GR_BASE, 2 * ((size_t)ntiles + 1) * 8, &p)) return 1;
     u64* tile_occ = (u64*)p; u64* tile_rows = tile_occ + ntiles + 1;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.nb = nb; a.total = &c->d_sc->total;
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
+    FjGtArgs a{};
+    u64* cnt = nullptr;
+    if (gt_open(c, nb, ntiles64 * GJ_TS, s, &a, &cnt)) return 1;                 // (whole tiles: the slots behind capacity + 1 are never read)
+    a.bk = bk;
     HIPCHK(fj_launch_gt_build_first(a, false, s));
     HIPCHK(fj_launch_group_fill(cnt, cap + 1, FJ_GJ_COUNT, s));
     HIPCHK(fj_launch_gt_group_by_combine(a, FJ_GJ_COUNT, nullptr, cnt, s));
@@ -378,18 +376,11 @@ static int group_rows_global(fj_ctx* c, const u64* bk, size_t nb, hipStream_t s,
     hipLaunchKernelGGL(fj_gt_group_rows_tile_kernel<true>, dim3(ntiles), dim3(GJ_NT), 0, s, a, cnt, tile_occ, tile_rows, ntiles,
                        d_ok, d_starts, (u64)cap_out, &c->d_sc->total, &c->d_sc->err);
     HIPCHK(hipGetLastError());
-    const u64 rounds = ((u64)nb + 1023) / 1024;
-    hipLaunchKernelGGL(fj_gt_group_rows_place_kernel, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, cnt, d_rows, (u64)nb, &c->d_sc->err);
+    hipLaunchKernelGGL(fj_gt_group_rows_place_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, a, cnt, d_rows, (u64)nb, &c->d_sc->err);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: FJ_ALGO_GROUP_ROWS met a place beyond the relation's rows, or more distinct keys than rows");
+    if (gt_close(c, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return rows_outcap_error();
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
 }
 
@@ -403,18 +394,10 @@ int group_rows(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, int top_bits
     u64* d_rows = d_ov; u64* d_starts = d_ov + cap_out;
     if (!use_radix) return group_rows_global(c, bk, nb, s, t, out_count, d_ok, d_rows, d_starts, cap_out);
 
-    const Plan plan = make_plan(nb, top_bits, false);        // factorize's plan: the table is its 8192 slots
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    RelAttempt r;                                            // factorize's plan: the table is its 8192 slots; the rows' positions travel
+    if (rel_open(c, bk, REL_POSITIONS, nullptr, nb, top_bits, 0, s, &r)) return 1;
     FjGroupRowsArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    it.vals_pos = true;                                      // the rows' positions travel through the passes
-    if (run_passes(c, it, bk, nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     void* p;
     if (get_buf(c, W_GR_PART, 2 * (size_t)ga.nparts * 4, &p)) return 1;
     ga.part_groups = (u32*)p; ga.part_rows = ga.part_groups + ga.nparts;
@@ -424,19 +407,10 @@ int group_rows(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, int top_bits
     ga.out_keys = d_ok; ga.out_rows = d_rows; ga.out_starts = d_starts; ga.out_capacity = cap_out; ga.nrows = nb;
     ga.total = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(launch_rows_lds(ga, s, group_base, row_base));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
-    end_plan(c);
-    plan_timings(c, plan, ga.nparts, 0, t);
-    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the three launches alone)
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole call on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (group_rows_global(c, bk, nb, s, &t2, out_count, d_ok, d_rows, d_starts, cap_out)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
-    if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: FJ_ALGO_GROUP_ROWS met a place beyond the relation's rows, or more distinct keys than rows");
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole call on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return group_rows_global(c, bk, nb, s, g, out_count, d_ok, d_rows, d_starts, cap_out); });
+    if (c->h_sc->err & FJ_ERR_OUTCAP) return rows_outcap_error();
     *out_count = c->h_sc->total;
     return 0;
 }

@@ -1,5 +1,5 @@
 // fj_host.h -- host-side state shared by the translation units behind the C ABI (include/flashjoin.h):
-//   fj_plan.hip   workspace, plans, the partition-pass state machine, contexts, options, diagnostics
+//   fj_plan.hip   workspace, plans, the partition-pass state machine, the HBM-table form's scaffold, contexts, options, diagnostics
 //   fj_joins.hip  one-shot joins (the reference's drivers, hash_join.cpp:315-594), emit, owner split, bloom export / prefilter
 //   fj_prepared.hip  a build side prepared once and probed many times (FJ_ALGO_RETAIN_BUILD / FJ_ALGO_REUSE_BUILD)
 //   fj_stream.hip joins whose relations arrive in pieces, the owner shuffle's pack / append side
@@ -316,6 +316,42 @@ int begin_step(fj_ctx* c, const char* who);
 int read_scalars(fj_ctx* c, hipStream_t s);
 float ev_ms(fj_ctx* c, int a, int b);
 void plan_timings(fj_ctx* c, const Plan& plan, u64 partitions, int evc, fj_timings* t);
+int pool_error();                         // the one set_err of FJ_ERR_POOL behind a partition pass
+int distinct_error();                     // ... and of a group-by that found more distinct keys than the relation has rows
+
+// ---- the global-table form (one table in HBM for the whole build side, no partition passes) and the fallback onto it (fj_plan.hip;
+// DESIGN.md section 5).  gt_capacity: the smallest power of two >= max(64, 2 * nb).  gt_grid: workgroups of 1024 threads over n rows or
+// slots, 4096 at most, never 0.  gt_open takes W_GT_KEYS (and W_GT_VALS, val_words != 0), wires `a` to the context's scalars and nb,
+// records E_START, clears the scalars up to `alloc` (the cursor starts at 0) and fills the key plane with 0xFF.  gt_close records E_JOIN,
+// then gt_read: the scalars read back, gt_facts (path 1, no passes, one partition) and the intervals between E_START, E_BUILD, E_PPART
+// and E_JOIN, which the form records.  gt_fallback runs `global_form` into fresh timings, adds the abandoned attempt's total_ms, sets
+// fell_back, stores them in *t - also when the form fails; a failed call publishes no timings - and returns the form's code.
+// kind_agg: the FJ_GJ_* form of an accumulator plane over a value column of that kind; -1 outside either range ----
+enum ValueKind { KIND_UNSIGNED = 0, KIND_SIGNED = 1, KIND_FLOAT = 2 };          // uint64 / int64 / binary64 words: the `kind` of group_by_all, _arg, _merge
+enum AggPlane { PLANE_COUNT = 0, PLANE_SUM = 1, PLANE_MIN = 2, PLANE_MAX = 3 };  // the order of the four output planes of FJ_ALGO_AGG_ALL
+u64 gt_capacity(size_t nb);
+inline u32 gt_grid(u64 n) { const u64 rounds = (n + 1023) / 1024; return (u32)(rounds < 4096 ? (rounds ? rounds : 1) : 4096); }
+int gt_open(fj_ctx* c, size_t nb, size_t val_words, hipStream_t s, FjGtArgs* a, u64** vals);
+void gt_facts(fj_timings* t);
+int gt_read(fj_ctx* c, hipStream_t s, fj_timings* t);
+int gt_close(fj_ctx* c, hipStream_t s, fj_timings* t);
+template <class F> int gt_fallback(fj_timings* t, F&& global_form) {
+    fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
+    const int rc = global_form(&t2);
+    t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
+    return rc;
+}
+int kind_agg(int kind, int plane);
+
+// ---- the partitioned attempt on ONE relation (fj_groupby*.hip).  rel_open: make_plan (target: make_plan's override, 0 = none) ..
+// E_PPART - the relation's passes, with `beside` travelling beside the keys (vals is read for REL_VALUES only).  rel_close: E_JOIN ..
+// plan_timings behind the form's kernel, the pool check included; probe_phase_ms = join_ms (there is no second relation) ----
+enum RelBeside { REL_KEYS_ONLY, REL_VALUES, REL_POSITIONS };      // nothing / the value column / the rows' positions, made by the first pass
+struct RelAttempt { Plan plan; FjChunkSet rel{}; u32 nparts = 0; };
+int rel_open(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, u64 target, hipStream_t s,
+             RelAttempt* r);
+int rel_close(fj_ctx* c, const Plan& plan, u32 nparts, hipStream_t s, fj_timings* t);
+
 int stamps_begin(unsigned long long** dbg, hipStream_t s);
 int stamps_report(const char* label, const unsigned long long* dbg, u32 nitems, hipStream_t s);
 

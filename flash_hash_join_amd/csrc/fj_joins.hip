@@ -158,24 +158,17 @@ int emit_pending(fj_ctx* c, u64* d_ok, u64* d_ov, size_t cap, hipStream_t s, fj_
 int join_global(fj_ctx* c, int bloom, int materialize, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np,
                 hipStream_t s, fj_timings* t, u64* out_count, bool rid = false) {
     if (rid) bloom = 0;
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     FjGtArgs a{};
     void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1; a.tvals = (u64*)p;
     a.bloom = nullptr;
     if (bloom) { if (get_buf(c, W_GT_BLOOM, cap / 8 * 4, &p)) return 1; a.bloom = (u32*)p; }
     const u64 npairs = (np + 1) / 2;
     const u32 grid = (u32)std::min<u64>(2048, std::max<u64>(1, npairs / 256));
     if (get_buf(c, W_WG_COUNT, (size_t)grid * 4, &p)) return 1; a.wg_count = (u32*)p;
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.bv = rid ? nullptr : bv; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
+    if (gt_open(c, nb, cap, s, &a, &a.tvals)) return 1;
+    a.bk = bk; a.bv = rid ? nullptr : bv; a.pk = pk; a.np = np;
     a.row_ids = rid ? 1u : 0u;
-
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
     if (a.bloom) HIPCHK(hipMemsetAsync(a.bloom, 0, cap / 8 * 4, s));
     if (rid) {                                       // (row index minimum: all ones at rest)
         HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));
@@ -187,14 +180,8 @@ int join_global(fj_ctx* c, int bloom, int materialize, const u64* bk, const u64*
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     if (np > 0) HIPCHK(fj_launch_gt_probe(a, false, grid, s));
     else HIPCHK(hipMemsetAsync(a.wg_count, 0, (size_t)grid * 4, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
+    if (gt_close(c, s, t)) return 1;
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     if (materialize) { c->pend.valid = true; c->pend.kind = Pending::HBM_TABLE; c->pend.gt = a; c->pend.gt_grid = grid; c->pend.count = *out_count; }
     return 0;
 }
@@ -358,7 +345,7 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
         HIPCHK(fj_launch_emit_single(js, s, &c->d_sc->next_emit_item));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
         if (!(c->h_sc->err & (FJ_STAT_DUPS | FJ_STAT_EMIT_RETRY | FJ_ERR_LDS_FULL | FJ_ERR_OUTCAP))) {
             end_plan(c);
             plan_timings(c, plan, ja.nparts, evc, t);
@@ -433,7 +420,7 @@ int radix_join_tail(fj_ctx* c, int materialize, FjLdsJoinArgs& ja, const Plan& p
             else c->h_sc->err |= FJ_ERR_LDS_FULL;                // not recoverable this way: the caller's whole-join fallback
         }
     }
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);                              // every prepared pass ran its bookkeeping: the self-cleaning buffers are clean
     plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL) { *lds_full = true; return 0; }
@@ -650,7 +637,7 @@ int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t n
         if (mm_tile_join(c, ja, nitems, materialize, s, &c->pend, outer, &oa)) return 1;
         tiled = true;
     }
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)
         return set_err("many-to-many join: a final partition holds more than 4096 build rows (a build key with thousands of duplicates?); not supported");
@@ -1147,7 +1134,7 @@ int fj_bloom_export(fj_ctx* c, const uint64_t* d_build_keys, size_t nb, int hash
     if (run_passes(c, bit, (const u64*)d_build_keys, nullptr, s, &cs, nullptr)) return 1;
     HIPCHK(fj_launch_bloom_export(cs, d_filters, c->num_cus, options().bloom_variant, s));
     if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     return 0;
 }
@@ -1184,7 +1171,7 @@ int fj_bloom_prefilter(fj_ctx* c, const uint64_t* d_probe_keys, size_t n, int ha
     if (read_scalars(c, s)) return 1;
     HIPCHK(hipMemcpyAsync(&c->h_sc->expected, &bbase[nbuckets], sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // (pinned scratch word)
     HIPCHK(hipStreamSynchronize(s));
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     if (c->h_sc->err & FJ_ERR_VARIANT)
         return set_err("fj_bloom_prefilter: these filters were not exported with bloom_variant %d (every rank must use the same FJ_BLOOM_VARIANT)", options().bloom_variant);

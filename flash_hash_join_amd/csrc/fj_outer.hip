@@ -318,34 +318,27 @@ hipError_t fj_launch_full_sweep(const FjChunkSet& build, const u64* bits, const 
 
 namespace fjh {
 
-// the global-table form (no partition passes): the fallback of a partition beyond the LDS table, and FJ_ALGO_SCALAR under
-// "scalar_hbm_table" / FJ_ALGO_ADAPTIVE below "radix_threshold".  LEFT builds with row indices (the smallest wins, first occurrence)
+// the global-table form (fj_host.h).  LEFT builds with row indices (the smallest wins, first occurrence)
 // full_r != nullptr (LEFT only): the full outer join - the probe marks the slots it hits, a sweep over the flat build rows looks every
 // key up again and appends the rows of unmarked slots behind row np; *full_r = their number
 static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, hipStream_t s,
                              fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, bool rid, u64* full_r = nullptr) {
     const bool left = mode != FJ_OJ_ANTI;
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     FjGtArgs a{};
-    void* p;
-    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
-    if (left) { if (get_buf(c, W_GT_VALS, cap * 8, &p)) return 1; a.tvals = (u64*)p; }
-    a.cap_mask = cap - 1; a.flags = &c->d_sc->flags; a.empty_val = &c->d_sc->empty_val;
-    a.bk = bk; a.bv = (left && !rid) ? bv : nullptr; a.nb = nb; a.pk = pk; a.np = np; a.total = &c->d_sc->total;
-    a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr; a.row_ids = rid ? 1u : 0u;
     if (full_r) {
+        void* p;
         if (get_buf(c, W_FULL_BITS, (cap / 32 + 1) * 4, &p)) return 1;
         a.matched = (u32*)p;
     }
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    if (gt_open(c, nb, left ? cap : 0, s, &a, &a.tvals)) return 1;
+    a.bk = bk; a.bv = (left && !rid) ? bv : nullptr; a.pk = pk; a.np = np;
+    a.out_keys = d_ok; a.out_vals = left ? d_ov : nullptr; a.row_ids = rid ? 1u : 0u;
     if (full_r) {
         HIPCHK(hipMemsetAsync(a.matched, 0, (cap / 32 + 1) * 4, s));
         HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));      // (the sweep's row cursor)
     }
     HIPCHK(hipMemsetAsync(&c->d_sc->empty_val, 0xFF, sizeof(u64), s));           // (row index minimum)
-    HIPCHK(hipMemsetAsync(a.tkeys, 0xFF, cap * 8, s));
     if (left) HIPCHK(hipMemsetAsync(a.tvals, 0xFF, cap * 8, s));
     HIPCHK(fj_launch_gt_build_first(a, left, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
@@ -357,16 +350,11 @@ static int join_outer_global(fj_ctx* c, int mode, const u64* bk, const u64* bv, 
         HIPCHK(fj_launch_gt_full_sweep(a, np, (u64)np + nb, &c->d_sc->sample_hits, &c->d_sc->err, s));
         HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
     }
-    if (read_scalars(c, s)) return 1;
+    if (gt_read(c, s, t)) return 1;                          // (E_JOIN stands before the sweep: gt_close's second half)
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join's global-table probe wrote out of its rows");
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (left ? hits + misses != np : misses > np) return set_err("internal error: outer join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
     *out_count = left ? hits : misses;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
-    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
-    t->probe_phase_ms = t->join_ms;
-    t->total_ms = ev_ms(c, E_START, E_JOIN);
     if (full_r) {
         *full_r = c->h_sc->sample_hits;
         if (*full_r > nb) return set_err("internal error: full outer join kept %llu of %zu build rows", (unsigned long long)*full_r, nb);
@@ -427,7 +415,7 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     HIPCHK(fj_launch_outer_join(ja, (rid && left) ? FJ_OJ_LEFT_FIRST : mode, np, &c->d_sc->expected, s));
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     end_plan(c);
     if (left && !rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
@@ -446,15 +434,11 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
         HIPCHK(fj_launch_outer_join(ja, FJ_OJ_LEFT_FIRST, np, &c->d_sc->expected, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
     }
     plan_timings(c, plan, ja.nparts, evc, t);
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_outer_global(c, mode, bk, bv, nb, pk, np, s, &t2, out_count, d_ok, d_ov, rid)) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return join_outer_global(c, mode, bk, bv, nb, pk, np, s, g, out_count, d_ok, d_ov, rid); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join kernel wrote out of its rows");
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected;
     if (left ? hits + misses != np : misses > np) return set_err("internal error: outer join placed %llu + %llu of %zu probe rows", (unsigned long long)hits, (unsigned long long)misses, np);
@@ -527,7 +511,7 @@ int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb
         HIPCHK(fj_launch_full_sweep(ja.build, bits, ja.orig_vals, ja.row_ids, d_ok, d_ov, np, out_cap, &c->d_sc->sample_hits, &c->d_sc->err, s));
         HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
         return 0;
     };
     if (join_and_sweep(rid ? FJ_OJ_LEFT_FIRST : FJ_OJ_LEFT)) return 1;
@@ -550,12 +534,8 @@ int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb
         if (join_and_sweep(FJ_OJ_LEFT_FIRST)) return 1;
     }
     plan_timings(c, plan, ja.nparts, evc, t);
-    if (c->h_sc->err & FJ_ERR_LDS_FULL) {                    // a partition beyond the LDS table: the whole join on the HBM table
-        fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-        if (join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, &t2, &out_counts[0], d_ok, d_ov, rid, &out_counts[1])) return 1;
-        t2.total_ms += t->total_ms; t2.fell_back = 1; *t = t2;
-        return 0;
-    }
+    if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
+        return gt_fallback(t, [&](fj_timings* g) { return join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, g, &out_counts[0], d_ok, d_ov, rid, &out_counts[1]); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the full outer join wrote out of its rows");
     const u64 hits = c->h_sc->total, misses = c->h_sc->expected, rest = c->h_sc->sample_hits;
     if (hits + misses != np || rest > nb) return set_err("internal error: full outer join placed %llu + %llu of %zu probe rows and %llu of %zu build rows",

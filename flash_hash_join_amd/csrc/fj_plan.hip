@@ -391,6 +391,81 @@ void plan_timings(fj_ctx* c, const Plan& plan, u64 partitions, int evc, fj_timin
     if (plan.bloom_level > 0) { t->filter_ms = ev_ms(c, E_BF0, E_BF1); t->filter_survivors = c->h_sc->bloom_survivors; }
 }
 
+int pool_error() { return set_err("internal error: chunk pool exhausted during a partition pass"); }
+int distinct_error() { return set_err("internal error: group-by found more distinct keys than the relation has rows"); }
+
+// ---- the global-table form: no partition passes; FJ_ALGO_SCALAR under "scalar_hbm_table", FJ_ALGO_ADAPTIVE
+// below "radix_threshold", and the fallback of a partitioned attempt that met a partition beyond its LDS table.  Load factor <= 1/2 ----
+u64 gt_capacity(size_t nb) {
+    u64 cap = 64;
+    while (cap < 2 * (u64)nb) cap <<= 1;
+    return cap;
+}
+
+int gt_open(fj_ctx* c, size_t nb, size_t val_words, hipStream_t s, FjGtArgs* a, u64** vals) {
+    const u64 cap = gt_capacity(nb);
+    void* p;
+    if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a->tkeys = (u64*)p;
+    if (val_words) { if (get_buf(c, W_GT_VALS, val_words * 8, &p)) return 1; *vals = (u64*)p; }
+    a->cap_mask = cap - 1; a->flags = &c->d_sc->flags; a->empty_val = &c->d_sc->empty_val;
+    a->nb = nb; a->total = &c->d_sc->total;
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    HIPCHK(hipMemsetAsync(c->d_sc, 0, offsetof(Scalars, alloc), s));
+    HIPCHK(hipMemsetAsync(a->tkeys, 0xFF, cap * 8, s));
+    return 0;
+}
+
+void gt_facts(fj_timings* t) { t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1; }
+
+int gt_read(fj_ctx* c, hipStream_t s, fj_timings* t) {
+    if (read_scalars(c, s)) return 1;
+    gt_facts(t);
+    t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
+    t->join_ms = ev_ms(c, E_PPART, E_JOIN);
+    t->probe_phase_ms = t->join_ms;
+    t->total_ms = ev_ms(c, E_START, E_JOIN);
+    return 0;
+}
+
+int gt_close(fj_ctx* c, hipStream_t s, fj_timings* t) {
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    return gt_read(c, s, t);
+}
+
+int kind_agg(int kind, int plane) {
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || plane < PLANE_COUNT || plane > PLANE_MAX) return -1;
+    static const int forms[3][4] = {{FJ_GJ_COUNT, FJ_GJ_SUM, FJ_GJ_MIN_U, FJ_GJ_MAX_U},
+                                    {FJ_GJ_COUNT, FJ_GJ_SUM, FJ_GJ_MIN_S, FJ_GJ_MAX_S},
+                                    {FJ_GJ_COUNT, FJ_GJ_SUM_F, FJ_GJ_MIN_F, FJ_GJ_MAX_F}};
+    return forms[kind][plane];
+}
+
+int rel_open(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, u64 target, hipStream_t s,
+             RelAttempt* r) {
+    r->plan = make_plan(n, top_bits, false, target);
+    begin_plan(c);
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (clear_plan_scalars(c, s)) return 1;
+    PassIter it;
+    pass_init(it, 0, beside != REL_KEYS_ONLY, n, r->plan, top_bits);
+    it.vals_pos = beside == REL_POSITIONS;
+    if (run_passes(c, it, keys, beside == REL_VALUES ? vals : nullptr, s, &r->rel, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    r->nparts = r->rel.list ? r->rel.nb : 1u;
+    return 0;
+}
+
+int rel_close(fj_ctx* c, const Plan& plan, u32 nparts, hipStream_t s, fj_timings* t) {
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
+    end_plan(c);
+    plan_timings(c, plan, nparts, 0, t);
+    t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the form's kernels alone)
+    return 0;
+}
+
 // diagnostic: per-item phase stamps (s_memrealtime, 100 MHz) written by thread 0 of the first 4096 workgroups of a join kernel
 int stamps_begin(unsigned long long** dbg, hipStream_t s) {
     static unsigned long long* dbg_buf = nullptr;

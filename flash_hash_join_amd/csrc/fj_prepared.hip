@@ -514,14 +514,13 @@ hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u6
     if (!a.total || !miss_total || !err || !a.tkeys || !a.tvals || !a.flags || !a.empty_val || !a.pk) return hipErrorInvalidValue;
     if ((!out_cnt && !out_val) || (out_val && !pv)) return hipErrorInvalidValue;
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_val && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
-    const u64 rounds = (a.np + 1023) / 1024;
     void (*kern)(FjGtArgs, const u64*, u64*, u64*, u64, unsigned long long*, u32*) =
         agg == FJ_GJ_MIN_U ? fj_prep_gt_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_gt_group_kernel<FJ_GJ_MIN_S> :
         agg == FJ_GJ_MAX_U ? fj_prep_gt_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_gt_group_kernel<FJ_GJ_MAX_S> :
         agg == FJ_GJ_SUM_F ? fj_prep_gt_group_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_prep_gt_group_kernel<FJ_GJ_MIN_F> :
         agg == FJ_GJ_MAX_F ? fj_prep_gt_group_kernel<FJ_GJ_MAX_F> :
         fj_prep_gt_group_kernel<FJ_GJ_SUM>;                                       // (the counts alone: out_val == nullptr)
-    hipLaunchKernelGGL(kern, dim3((u32)(rounds < 4096 ? rounds : 4096)), dim3(1024), 0, s, a, pv, out_cnt, out_val, nb, miss_total, err);
+    hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.np)), dim3(1024), 0, s, a, pv, out_cnt, out_val, nb, miss_total, err);
     return hipGetLastError();
 }
 
@@ -547,8 +546,7 @@ static int prep_alloc(Prepared& P, void** out, size_t bytes) {
 // P.aux), an owned copy of the values beside it, g counted by the group-by's sweep of the table (cursor alone)
 static int prepared_retain_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s) {
     Prepared& P = c->prep;
-    u64 cap = 64;
-    while (cap < 2 * (u64)nb) cap <<= 1;
+    const u64 cap = gt_capacity(nb);
     P.form = Prepared::HBM; P.cap_mask = cap - 1;
     if (prep_alloc(P, (void**)&P.keys, cap * 8) || prep_alloc(P, (void**)&P.rows, cap * 8) || prep_alloc(P, &P.aux, 16)) return 1;
     if (bv && prep_alloc(P, (void**)&P.vals, nb * 8)) return 1;
@@ -601,7 +599,7 @@ int prepared_retain(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, siz
         HIPCHK(fj_launch_prep_build(ba, s));
         HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
         end_plan(c);
         t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
         if (!(c->h_sc->err & FJ_ERR_LDS_FULL)) {
@@ -620,7 +618,7 @@ int prepared_retain(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, siz
         t->fell_back = 1;
     }
     if (prepared_retain_global(c, bk, bv, nb, s)) return 1;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
+    gt_facts(t);
     t->build_phase_ms += ev_ms(c, E_START, E_BUILD);
     t->total_ms = t->build_phase_ms;
     P.path = 1; P.valid = true;
@@ -689,7 +687,7 @@ int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timing
         HIPCHK(fj_launch_prep_probe(pa, s));
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
         end_plan(c);
         plan_timings(c, P.plan, P.nparts, evc, t);
         t->build_phase_ms = 0;                               // (nothing touched the build relation: its passes ran when it was prepared)
@@ -777,7 +775,7 @@ int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream
         }
         HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
         if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return set_err("internal error: chunk pool exhausted during a partition pass");
+        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
         end_plan(c);
         plan_timings(c, P.plan, P.nparts, evc, t);
         t->build_phase_ms = 0;                               // (nothing touched the build relation: its passes ran when it was prepared)

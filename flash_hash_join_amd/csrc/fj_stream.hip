@@ -24,8 +24,7 @@ int stream_flat_join(fj_ctx* c, StreamState& st, const u64* d_pk, size_t n, hipS
 
 // counting join of the appended pieces over one table in HBM (fj_gt_*): the fallback of a streamed join
 int stream_global_count(fj_ctx* c, StreamState& st, hipStream_t s, fj_timings* t, u64* out_count) {
-    u64 cap = 64;
-    while (cap < 2 * (u64)st.nb_seen) cap <<= 1;
+    const u64 cap = gt_capacity(st.nb_seen);
     FjGtArgs a{};
     void* p;
     if (get_buf(c, W_GT_KEYS, cap * 8, &p)) return 1; a.tkeys = (u64*)p;
@@ -49,9 +48,9 @@ int stream_global_count(fj_ctx* c, StreamState& st, hipStream_t s, fj_timings* t
     HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
     if (read_scalars(c, s)) return 1;
     *out_count = c->h_sc->total;
-    t->path = 1; t->passes = 0; t->radix_bits = 0; t->partitions = 1;
+    gt_facts(t);
     t->build_phase_ms = ev_ms(c, E_START, E_BUILD);
-    t->join_ms = ev_ms(c, E_BUILD, E_JOIN);
+    t->join_ms = ev_ms(c, E_BUILD, E_JOIN);                  // (the pieces' probes follow their builds: no E_PPART)
     t->probe_phase_ms = t->join_ms;
     t->total_ms = ev_ms(c, E_START, E_JOIN);
     return 0;
@@ -222,9 +221,7 @@ int fj_stream_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* t
         if (lds_full) {
             // a partition of more than 8128 distinct build keys: count over ONE table in HBM, piece by piece (the streamed
             // join's own fallback; the one-shot join has the same one)
-            fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-            if (stream_global_count(c, st, s, &t2, &count)) return 1;
-            t2.total_ms += t.total_ms; t2.fell_back = 1; t = t2;
+            if (gt_fallback(&t, [&](fj_timings* g) { return stream_global_count(c, st, s, g, &count); })) return 1;
         }
     } else {
         if (st.plan.npass == 0 && st.nb_seen > 0)
@@ -235,12 +232,10 @@ int fj_stream_finish(fj_ctx* c, void* stream, uint64_t* out_count, fj_timings* t
         if (st.plan.npass == 0) end_plan(c);          // (a partitioned plan with an empty side never ran its bookkeeping: stays "in flight")
         if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_STAT_RETRY)) {
             // the one table of a zero-pass plan overflowed (a build side of ~3900 rows at a bad moment): HBM-table fallback
-            fj_timings t2; memset(&t2, 0, sizeof t2); t2.sampled_hit_bp = -1;
-            if (stream_global_count(c, st, s, &t2, &count)) return 1;
-            t2.fell_back = 1;
+            if (gt_fallback(&t, [&](fj_timings* g) { return stream_global_count(c, st, s, g, &count); })) return 1;      // (t.total_ms is still 0)
             if (out_count) *out_count = count;
-            if (timings) *timings = t2;
-            last_timings() = t2;
+            if (timings) *timings = t;
+            last_timings() = t;
             return 0;
         }
         count = c->h_sc->total;

@@ -15,6 +15,7 @@ import threading
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -247,6 +248,8 @@ def check_ids(rel, what, g, uniques, codes, device=False, raw=False):
 def check_timings(lt, what, path, passes, fell_back):
     assert lt["emit_ms"] == 0.0 and lt["join_ms"] == lt["probe_phase_ms"], (what, lt)
     assert lt["path"] == path and lt["fell_back"] == fell_back, (what, lt)
+    if path == 1:
+        hbm_timings.check_hbm_form(lt, what)
     if passes is not None:
         assert lt["passes"] == passes, (what, lt)
 

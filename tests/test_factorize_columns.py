@@ -12,6 +12,7 @@ import threading
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from test_factorize_columns_cpu import GB, INV, PAIR, SALT, pair64
 
@@ -84,6 +85,8 @@ def check(rel, what, g, codes, first_index, device=False, raw=False):
 def check_timings(lt, what, path, passes, fell_back):
     assert lt["emit_ms"] == 0.0 and lt["join_ms"] == lt["probe_phase_ms"], (what, lt)
     assert lt["path"] == path and lt["fell_back"] == fell_back, (what, lt)
+    if path == 1:
+        hbm_timings.check_hbm_form(lt, what)
     if passes is not None:
         assert lt["passes"] == passes, (what, lt)
 

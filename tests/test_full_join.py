@@ -13,6 +13,7 @@ import zlib
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -269,6 +270,7 @@ def test_global_table_path(fj, how):
                 a = (t(bk), t(bv), t(pk)) if dev else (bk, bv, pk)
                 (m, r), _, k, v = api._join(api.ALGO_SCALAR | api.ALGO_FULL_OUTER, 0, 1, *a, True)
                 assert fj.last_timings()["path"] == 1
+                hbm_timings.check_hbm_form(fj.last_timings())
                 k, v = _host(k), _host(v)
                 assert (m, r) == (m_exp, rk_exp.size) and k.size == pk.size + r
                 assert _same_pairs(k[:m], v[:m], ek, ev)
@@ -276,6 +278,7 @@ def test_global_table_path(fj, how):
                 assert _same_pairs(k[pk.size:], v[pk.size:], rk_exp, rv_exp)
                 (m, r), _, pi, bi = api._join(api.ALGO_SCALAR | api.ALGO_FULL_OUTER | api.ALGO_ROW_IDS, 0, 1, a[0], None, a[2], True)
                 assert fj.last_timings()["path"] == 1
+                hbm_timings.check_hbm_form(fj.last_timings())
                 pi, bi = _host(pi).view(np.int64), _host(bi).view(np.int64)
                 assert (m, r) == (m_exp, rk_exp.size)
                 assert np.array_equal(np.sort(pi[:pk.size]), np.arange(pk.size)) and np.array_equal(pk[pi[:m]], bk[bi[:m]])
@@ -289,6 +292,7 @@ def test_global_table_path(fj, how):
             for dev in (False, True):
                 _check(fj, bk, bv, pk, dev, fill=5)
                 assert fj.last_timings()["path"] == 1
+                hbm_timings.check_hbm_form(fj.last_timings())
         finally:
             fj.set_option("radix_threshold", 0)
 
@@ -314,12 +318,14 @@ def test_a_partition_beyond_the_lds_table_falls_back_to_the_global_table(fj):
     assert rk_exp.size > 0
     m, r, _, k, v = fj.full_join(bk, bv, pk, return_arrays=True)
     assert fj.last_timings()["fell_back"] == 1
+    hbm_timings.check_hbm_form(fj.last_timings())
     assert (m, r) == (m_exp, rk_exp.size)
     assert _same_pairs(k[:m], v[:m], ek, ev)
     assert np.array_equal(_sorted(k[m:pk.size]), _sorted(anti_exp))
     assert _same_pairs(k[pk.size:], v[pk.size:], rk_exp, rv_exp)
     m, r, _, pi, bi = fj.join_indices(bk, pk, how="full")
     assert fj.last_timings()["fell_back"] == 1
+    hbm_timings.check_hbm_form(fj.last_timings())
     assert (m, r) == (m_exp, rk_exp.size) and np.array_equal(np.sort(bi[pk.size:]), np.flatnonzero(~np.isin(bk, pk)))
     assert np.array_equal(pk[pi[:m]], bk[bi[:m]]) and np.all(pi[pk.size:] == -1)
 

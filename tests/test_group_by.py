@@ -16,6 +16,7 @@ import re
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -432,6 +433,7 @@ def test_hbm_table_form(fj, option, base, cid):
 
     def after(fn, lt):
         assert lt["path"] == 1 and lt["fell_back"] == 0 and lt["passes"] == 0 and lt["emit_ms"] == 0.0, (fn, lt)
+        hbm_timings.check_hbm_form(lt, fn)
     fj.set_option(option, 1 if base else ref.keys.size + 1)
     try:
         for device in (False, True):
@@ -466,6 +468,7 @@ def test_a_partition_beyond_the_lds_table_falls_back_to_the_hbm_table(fj, device
 
     def after(fn, lt):
         assert lt["fell_back"] == 1 and lt["path"] == 1 and lt["emit_ms"] == 0.0, (fn, lt)
+        hbm_timings.check_hbm_form(lt, fn)
     check_all_forms(fj, ref, device, after=after)
 
 

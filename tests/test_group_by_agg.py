@@ -17,6 +17,7 @@ import threading
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from test_float_aggregates import exact_values, extreme_values, inexact_values
 from test_group_by import _dup_keys, _hot_keys, _special_keys, _values_for
@@ -140,6 +141,8 @@ def check(ref, kind, out, device, public=True, sums_exact=True):
 def planned(fj, passes, fell_back=0, path=0):
     lt = fj.last_timings()
     assert lt["path"] == path and lt["fell_back"] == fell_back and lt["emit_ms"] == 0.0, lt
+    if path == 1:
+        hbm_timings.check_hbm_form(lt)
     if passes is not None:
         assert lt["passes"] == passes, lt
     assert lt["join_ms"] == lt["probe_phase_ms"], lt
@@ -256,7 +259,9 @@ def test_the_edge_of_the_lds_table(fj, n, fell_back):
             out = call(fj, ref, kind, device)
             lt = fj.last_timings()
             assert lt["fell_back"] == fell_back and lt["path"] == fell_back and lt["emit_ms"] == 0.0, (kind, device, lt)
-            if not fell_back:
+            if fell_back:
+                hbm_timings.check_hbm_form(lt, (kind, device))
+            else:
                 assert lt["passes"] == 1 and lt["radix_bits"] == 5, lt
             check(ref, kind, out, device)
 

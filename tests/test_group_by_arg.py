@@ -13,6 +13,7 @@ import threading
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from test_float_aggregates import exact_values, extreme_values
 from test_group_by import _dup_keys, _hot_keys, _special_keys
@@ -127,6 +128,8 @@ def check(rel, kind, is_max, out, skip_keys=()):
 def planned(fj, passes, fell_back=0, path=0):
     lt = fj.last_timings()
     assert lt["path"] == path and lt["fell_back"] == fell_back and lt["emit_ms"] == 0.0, lt
+    if path == 1:
+        hbm_timings.check_hbm_form(lt)
     if passes is not None:
         assert lt["passes"] == passes, lt
     assert lt["join_ms"] == lt["probe_phase_ms"], lt
@@ -391,6 +394,7 @@ def test_a_partition_beyond_the_lds_table_falls_back_to_the_hbm_table(fj):
                 out = call(fj, rel, kind, is_max, device)
                 lt = fj.last_timings()
                 assert lt["fell_back"] == 1 and lt["path"] == 1 and lt["emit_ms"] == 0.0, (kind, is_max, device, lt)
+                hbm_timings.check_hbm_form(lt, (kind, is_max, device))
                 check(rel, kind, is_max, out)
 
 

@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from test_float_aggregates import exact_values
 from test_group_by import _dup_keys, _values_for
@@ -119,6 +120,8 @@ def check(p, out, device=None):
 def planned(fj, passes=None, fell_back=0, path=0):
     lt = fj.last_timings()
     assert lt["path"] == path and lt["fell_back"] == fell_back and lt["emit_ms"] == 0.0, lt
+    if path == 1:
+        hbm_timings.check_hbm_form(lt)
     if passes is not None:
         assert lt["passes"] == passes, lt
     assert lt["join_ms"] == lt["probe_phase_ms"], lt
@@ -275,7 +278,9 @@ def test_the_edge_of_the_lds_table(fj, n, fell_back):
             out = merge(fj, p, device)
             lt = fj.last_timings()
             assert lt["fell_back"] == fell_back and lt["path"] == fell_back and lt["emit_ms"] == 0.0, (kind, device, lt)
-            if not fell_back:
+            if fell_back:
+                hbm_timings.check_hbm_form(lt, (kind, device))
+            else:
                 assert lt["passes"] == 1 and lt["radix_bits"] == 5, lt
             check(p, out)
 

@@ -14,6 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -416,6 +417,7 @@ def test_partitions_beyond_the_lds_table_fall_back_to_the_hbm_table(fj, device):
     the HBM table (fell_back == 1), whatever the partitioned attempt left in the outputs"""
     def after(fn, lt):
         assert lt["fell_back"] == 1 and lt["path"] == 1, (fn, lt)
+        hbm_timings.check_hbm_form(lt, fn)
     check_all_forms(fj, _oversized_case(), device, after=after)
 
 
@@ -431,11 +433,13 @@ def test_scalar_hbm_table_path(fj):
         for want_counts, with_values in ((True, False), (False, True), (True, True)):
             P, _, counts, sums = api.join_device(S, 0, 1, bk, pv if with_values else None, pk, want_counts=want_counts)
             assert fj.last_timings()["path"] == 1 and fj.last_timings()["fell_back"] == 0
+            hbm_timings.check_hbm_form(fj.last_timings())
             assert P == r.P
             assert (counts is None) if not want_counts else np.array_equal(counts.cpu().numpy(), r.counts)
             assert (sums is None) if not with_values else np.array_equal(sums.cpu().numpy().view(np.uint64), r.sums)
         P, _, counts, sums = api._group_host(S, r.bk, r.pk, r.pv, True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         assert P == r.P and np.array_equal(counts, r.counts) and np.array_equal(sums.view(np.uint64), r.sums)
     finally:
         fj.set_option("scalar_hbm_table", 0)
@@ -448,6 +452,7 @@ def test_radix_threshold_sends_the_adaptive_base_to_the_hbm_table(fj, device):
 
     def after(fn, lt):
         assert lt["path"] == 1 and lt["fell_back"] == 0, (fn, lt)
+        hbm_timings.check_hbm_form(lt, fn)
     fj.set_option("radix_threshold", r.bk.size + 1)
     try:
         check_all_forms(fj, r, device, after=after)

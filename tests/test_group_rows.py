@@ -13,6 +13,7 @@ import threading
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 
 GB, ROWS = 0x40000, 0x40000000
@@ -75,6 +76,8 @@ def check_csr(rel, what, g, group_keys, offsets, row_index, device=False, raw=Fa
 def check_timings(lt, what, path, passes, fell_back):
     assert lt["emit_ms"] == 0.0 and lt["join_ms"] == lt["probe_phase_ms"], (what, lt)
     assert lt["path"] == path and lt["fell_back"] == fell_back, (what, lt)
+    if path == 1:
+        hbm_timings.check_hbm_form(lt, what)
     if passes is not None:
         assert lt["passes"] == passes, (what, lt)
 

@@ -12,6 +12,7 @@ import zlib
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -191,6 +192,7 @@ def test_global_table_path_keeps_first_occurrence(fj):
     try:
         m, _, k, v = api.join_device(api.ALGO_SCALAR | api.ALGO_LEFT_OUTER, 0, 1, t(bk), t(bv), t(pk), return_arrays=True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         k, v = k.cpu().numpy().view(np.uint64), v.cpu().numpy().view(np.uint64)
         assert m == m_exp
         a, b = canon_pairs(k[:m], v[:m]), canon_pairs(ek, ev)
@@ -198,6 +200,7 @@ def test_global_table_path_keeps_first_occurrence(fj):
         assert np.array_equal(_sorted(k[m:]), _sorted(anti_exp)) and np.all(v[m:] == 0)
         u, _, ak, _ = api.join_device(api.ALGO_SCALAR | api.ALGO_ANTI, 0, 1, t(bk), None, t(pk), return_arrays=True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         assert u == pk.size - m and np.array_equal(_sorted(ak.cpu().numpy()), _sorted(anti_exp))
         uc, _ = api.join_device(api.ALGO_SCALAR | api.ALGO_ANTI, 0, 0, t(bk), None, t(pk))
         assert uc == pk.size - m
@@ -207,6 +210,7 @@ def test_global_table_path_keeps_first_occurrence(fj):
     try:
         m, _, k, v = fj.left_join(bk, bv, pk, return_arrays=True, fill_value=5)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         a = canon_pairs(k[:m], v[:m])
         assert m == m_exp and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.all(v[m:] == 5)
     finally:
@@ -234,11 +238,13 @@ def test_a_partition_beyond_the_lds_table_falls_back_to_the_global_table(fj):
     from oracle.oracle import canon_pairs
     m, _, k, v = fj.left_join(bk, bv, pk, return_arrays=True)
     assert fj.last_timings()["fell_back"] == 1
+    hbm_timings.check_hbm_form(fj.last_timings())
     a, b = canon_pairs(k[:m], v[:m]), canon_pairs(ek, ev)
     assert m == m_exp and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     assert np.array_equal(_sorted(k[m:]), _sorted(anti_exp))
     u, _, ak = fj.anti_join(bk, pk, return_arrays=True)
     assert fj.last_timings()["fell_back"] == 1
+    hbm_timings.check_hbm_form(fj.last_timings())
     assert u == pk.size - m and np.array_equal(_sorted(ak), _sorted(anti_exp))
 
 

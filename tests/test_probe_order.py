@@ -15,6 +15,7 @@ import zlib
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -347,6 +348,7 @@ def test_partitions_beyond_the_lds_table_fall_back_to_the_hbm_table(fj, device):
     the HBM table (fell_back == 1), still with first-occurrence values and build rows, in every form (the mask form has the same table)."""
     def after(fn, lt):
         assert lt["fell_back"] == 1 and lt["path"] == 1, (fn, lt)
+        hbm_timings.check_hbm_form(lt, fn)
     check_all_forms(fj, _oversized_case(), device, after=after)
 
 
@@ -379,16 +381,20 @@ def test_scalar_hbm_table_path(fj):
         for want_mask in (False, True):
             m, _, vals, mask = api.join_device(S, 0, 1, bk, bv, pk, want_values=True, want_mask=want_mask)
             assert fj.last_timings()["path"] == 1 and fj.last_timings()["fell_back"] == 0
+            hbm_timings.check_hbm_form(fj.last_timings())
             assert m == r.m and np.array_equal(vals.cpu().numpy().view(np.uint64), np.where(r.hit, r.vals, np.uint64(0)))
             assert (mask is None) if not want_mask else np.array_equal(mask.cpu().numpy(), r.hit.astype(np.uint8))
         m, _, vals, mask = api.join_device(S, 0, 1, bk, None, pk, want_values=False, want_mask=True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         assert m == r.m and vals is None and np.array_equal(mask.cpu().numpy(), r.hit.astype(np.uint8))
         m, _, idx, mask = api.join_device(S | api.ALGO_ROW_IDS, 0, 1, bk, None, pk, want_values=True, want_mask=True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         assert m == r.m and np.array_equal(idx.cpu().numpy(), r.idx) and np.array_equal(mask.cpu().numpy(), r.hit.astype(np.uint8))
         m, _, vals, mask = api._probe_order_host(S, r.bk, r.bv, r.pk, True, True)
         assert fj.last_timings()["path"] == 1
+        hbm_timings.check_hbm_form(fj.last_timings())
         assert m == r.m and np.array_equal(vals, np.where(r.hit, r.vals, np.uint64(0))) and np.array_equal(mask, r.hit.astype(np.uint8))
     finally:
         fj.set_option("scalar_hbm_table", 0)

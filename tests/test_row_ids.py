@@ -13,6 +13,7 @@ import zlib
 import numpy as np
 import pytest
 
+import hbm_timings
 import keymix
 from conftest import ROOT
 
@@ -312,6 +313,7 @@ def test_partitions_beyond_the_lds_tables_fall_back_to_the_hbm_table(fj, device)
         _check_mode(fj, bk, pk, device, how)
         if how != "anti":                                              # (the anti join's keys-only table takes 15360 keys)
             assert fj.last_timings()["fell_back"] == 1, (how, fj.last_timings())
+            hbm_timings.check_hbm_form(fj.last_timings())
 
 
 @pytest.mark.gpu
@@ -325,6 +327,7 @@ def test_scalar_hbm_table_path(fj):
         for how, flag in (("inner", 0), ("left", api.ALGO_LEFT_OUTER), ("anti", api.ALGO_ANTI)):
             n, _, pi, bi = api.join_device(api.ALGO_SCALAR | api.ALGO_ROW_IDS | flag, 0, 1, t(bk), None, t(pk), return_arrays=True)
             assert fj.last_timings()["path"] == 1
+            hbm_timings.check_hbm_form(fj.last_timings())
             epi, ebi = ref_indices(bk, pk, how)
             pi = pi.cpu().numpy()
             if how == "anti":
