@@ -1715,6 +1715,131 @@ def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None,
     return (g, sec, gk, *_agg_columns(planes, aggs, float64, unsigned_out))
 
 
+# ---- extension: GROUP BY a, b with four aggregates in one call (csrc/fj_groupby_pair_agg.hip) ---------------------------------------------
+def _group_by_pair_all(a, b, values, flags: int, max_groups: Optional[int] = None):
+    """(g, seconds, group_a, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL | flags, over word columns
+    as `_key_columns` returns them.  planes is a (5, g) array of int64 words where the inputs live - column B of every group, then row
+    counts, sums, minima, maxima - each row aligned with group_a.  flags and max_groups as for `_group_by_all`."""
+    global _last
+    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_KEY_PAIR | ALGO_AGG_ALL | flags
+    L = _lib.load()
+    cnt = ctypes.c_uint64(0)
+    n = a.shape[0]
+    if _is_torch_tensor(a):
+        import torch
+        v = _dev_tensor(_from_dlpack_if_device(values), "values")
+        if v.numel() != n:
+            raise ValueError(f"values has {v.numel()} elements, the key columns have {n}")
+        if v.device != a.device:
+            raise ValueError(f"group_by_agg_columns: values lives on {v.device}, the key columns on {a.device}")
+        cap = max(1, n if max_groups is None else min(n, max_groups))
+        dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
+        ctx = context(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = torch.empty(cap, dtype=torch.int64, device=a.device)
+        ov = torch.empty((5, cap), dtype=torch.int64, device=a.device)
+        t = FjTimings()
+        with _ctx_locks.setdefault(dev, threading.RLock()):
+            rc = L.fj_join_device(ctx, algo, 0, 1, a.data_ptr(), b.data_ptr(), n, v.data_ptr(), n, stream, 64, ctypes.byref(cnt), ok.data_ptr(),
+                                  ov.data_ptr(), cap, ctypes.byref(t))
+            g = int(cnt.value)
+            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
+                raise ValueError(f"group_by_agg_columns: the relation has g = {g} distinct key tuples, max_groups = {max_groups}")
+            check(rc)
+        _last = t
+        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
+    if _is_torch_tensor(values):
+        values = values.numpy()
+    v = _as_u64_host(values, "values")
+    if v.size != n:
+        raise ValueError(f"values has {v.size} elements, the key columns have {n}")
+    sec = ctypes.c_double(0.0)
+    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, 0, 1, a.ctypes.data, b.ctypes.data, n, v.ctypes.data, n, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    g = int(cnt.value)
+    try:
+        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
+        ga, planes = take(ok, g), take(ov, 5 * g).view(np.int64).reshape(5, g)
+    finally:
+        L.fj_free_host(ok)
+        L.fj_free_host(ov)
+    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
+        raise ValueError(f"group_by_agg_columns: the relation has g = {g} distinct key tuples, max_groups = {max_groups}")
+    return g, float(sec.value), ga, planes
+
+
+def group_by_agg_columns(columns, values, aggs=("count", "sum", "min", "max"), signed=None, float64: bool = False, max_groups: Optional[int] = None):
+    """GROUP BY a MULTI-COLUMN key with several aggregates of one value column - SELECT a, b, COUNT(*), SUM(v), MIN(v), MAX(v), AVG(v)
+    ... GROUP BY a, b: (g, seconds, group_columns, *aggregate_columns).  group_columns is a tuple with one array per key column, the
+    distinct tuples, every aggregate column aligned with them; the order of the groups is unspecified.  columns is a sequence of key
+    columns of equal length and one kind, each converted as `factorize_columns` converts them (a single array is one column).
+    aggs, "mean", signed, float64, max_groups, the output dtypes and the containers are exactly `group_by_agg`'s.
+    Two columns are ONE library call (C ABI: algo | FJ_ALGO_GROUP_BY | FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL): the relation goes through
+    the partition passes once and no group ids are written, where factorize_columns + group_by_agg(codes, v) + two gathers take two
+    trips.  One column delegates to `group_by_agg`.  Three or more fold the leading columns with `factorize_columns`, make the one
+    fused call on (codes, last column, values) and recover the leading columns as c[first_index[codes of the groups]]; `seconds` is the
+    sum.  values=None is allowed with aggs == ("count",) alone."""
+    name = "group_by_agg_columns"
+    aggs = _check_aggs(name, aggs, float64)
+    max_groups = _check_max_groups(name, max_groups)
+    cols, _ = _key_columns(name, "columns", columns)
+    if not cols:
+        raise ValueError(f"{name}: columns is empty (name at least one key column)")
+    if values is None:
+        if aggs != ("count",):
+            raise ValueError(f"{name}: values is required unless aggs == ('count',) (got aggs = {aggs!r})")
+        if float64 or signed is not None:
+            raise ValueError(f"{name}: values=None counts rows: float64 and signed describe a value column")
+        values = cols[-1]                                    # (any column stands in: the counts read none)
+        signed = False
+    if len(cols) == 1:
+        g, sec, gk, *out = group_by_agg(cols[0], values, aggs, signed, float64, max_groups)
+        return (g, sec, (gk,), *out)
+    unsigned_out = False
+    if float64:
+        flags = ALGO_AGG_FLOAT
+        values = _float_words(name, "values", values, signed)
+    else:
+        if signed is not None and not isinstance(signed, (bool, np.bool_)):
+            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+        values = _from_dlpack_if_device(values)
+        if _is_torch_tensor(values):
+            if values.dtype.is_floating_point:
+                raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = str(values.dtype) == "torch.uint64"
+        else:
+            values = np.asarray(values)
+            if values.dtype.kind not in "iub":
+                raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
+            unsigned_in = values.dtype == np.uint64
+        signed = (not unsigned_in) if signed is None else bool(signed)
+        flags = ALGO_AGG_SIGNED if signed else 0
+        unsigned_out = unsigned_in and not signed
+    if _is_torch_tensor(values) and not values.is_cuda:
+        values = values.numpy()                              # (as _key_columns takes host tensors)
+    if _is_torch_tensor(cols[0]) != _is_torch_tensor(values):
+        raise TypeError(f"{name}: columns and values must be of one kind, got NumPy and torch side by side")
+    nv = values.numel() if _is_torch_tensor(values) else values.size
+    if nv != cols[0].shape[0]:
+        raise ValueError(f"{name}: values has {nv} elements, the key columns have {cols[0].shape[0]} rows")
+    sec0, lead_first = 0.0, None
+    a = cols[0]
+    if len(cols) > 2:                                        # the leading columns as one column of dense codes
+        _, sec0, codes, lead_first = factorize_columns(cols[:-1])
+        a = _dev_tensor(codes, "codes") if _is_torch_tensor(codes) else _as_u64_host(codes, "codes")
+    g, sec, ga, planes = _group_by_pair_all(a, cols[-1], values, flags, max_groups)
+    gb = planes[0] if _is_torch_tensor(planes) else planes[0].view(np.uint64)
+    if lead_first is None:
+        group_columns = (ga, gb)
+    else:                                                    # (ga holds the groups' codes: any row of a code carries its leading tuple)
+        rows = lead_first[ga if _is_torch_tensor(ga) else ga.view(np.int64)]
+        group_columns = tuple(c[rows] for c in cols[:-1]) + (gb,)
+    return (g, sec0 + sec, group_columns, *_agg_columns(planes[1:], aggs, float64, unsigned_out))
+
+
 # ---- extension: the row that holds each group's minimum / maximum (csrc/fj_groupby_arg.hip) ------------------------------------------------
 def _group_by_arg(keys, values, flags: int):
     """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ARG | flags.  planes is a (2, g) array of int64
@@ -2261,8 +2386,12 @@ EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_
               "group_by_agg", "group_by_argmin", "group_by_argmax", "group_by_merge", "GroupByAccumulator", "group_by_accumulator", "factorize",
               "build_index"]
 # multi-column keys: compositions over the entries above (`_group_by`, `factorize`), whose caller-context rows
-# (tests/test_caller_context_cpu.py walks EXTENSIONS) cover the path they take; their own suite is tests/test_factorize_columns.py
-KEY_EXTENSIONS = ["factorize_columns", "encode_keys"]
+# (tests/test_caller_context_cpu.py walks EXTENSIONS) cover the path they take; their own suite is tests/test_factorize_columns.py.
+# group_by_agg_columns is NOT such a composition: it has a library entry of its own (`_group_by_pair_all`: ALGO_KEY_PAIR | ALGO_AGG_ALL,
+# with its own context lookup, per-device lock and stream), as group_rows below has.  Like ROW_EXTENSIONS it is exempt from the
+# caller-context walk, which reads EXTENSIONS only; what covers its caller context is its own suite, tests/test_group_by_agg_columns.py
+# (device tensors in place, a side stream, a strided view, the inputs' device)
+KEY_EXTENSIONS = ["factorize_columns", "encode_keys", "group_by_agg_columns"]
 # the rows of every group: one entry of their own (ALGO_GROUP_ROWS) and a gather over it; their suite is tests/test_group_rows.py
 ROW_EXTENSIONS = ["group_rows", "group_by_collect"]
 __all__ = REFERENCE_EXPORTS + ALIASES + EXTENSIONS + KEY_EXTENSIONS + ROW_EXTENSIONS + ["last_timings", "join_device", "context", "set_option", "get_option", "sort_pairs", "workspace_bytes", "trim_workspace", "Index"]

@@ -270,6 +270,18 @@ hipError_t launch_pair_lds(const FjGroupByArgs& a, const u64* A, const u64* B, u
 
 }  // namespace
 
+// the two kernels FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL shares (csrc/fj_groupby_pair_agg.hip) have launchers, this one and
+// fj_launch_pair_combine at the end of the file: host code only - the kernels above are unchanged and compile to the same resources
+// as before (profiles/group_by_pair_agg_kernel_resources.txt).  They sit apart on purpose: tests/test_hbm_table_trips_cpu.py reads
+// this file's gt_grid launches IN ORDER - build (nb), sweep (cap), inverse (nb), combine (nb) - to derive its shapes, and each launch
+// stays at its old place in that order
+hipError_t fj_launch_gt_pair_build(const u64* A, const u64* B, u64 nb, u64* tab, u64 cap_mask, hipStream_t s) {
+    if (!A || !B || !tab || cap_mask + 1 < 2 * nb) return hipErrorInvalidValue;          // (capacity >= 2 nb: an empty slot is always met)
+    if (!nb) return hipSuccess;
+    hipLaunchKernelGGL(fj_gt_pair_build_kernel, dim3(fjh::gt_grid(nb)), dim3(1024), 0, s, A, B, nb, tab, cap_mask);
+    return hipGetLastError();
+}
+
 extern "C" uint64_t fj_key_pair64(uint64_t a, uint64_t b) { return fj_key_pair(a, b); }
 
 namespace fjh {
@@ -283,8 +295,7 @@ static int group_by_pair_global(fj_ctx* c, const u64* ka, const u64* kb, size_t 
     u64* ids = nullptr;                                      // (no fill: the sweep writes every word the inverse kernel reads)
     if (gt_open(c, nb, cap, s, &a, &ids)) return 1;
     u64* tab = a.tkeys;
-    hipLaunchKernelGGL(fj_gt_pair_build_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, ka, kb, (u64)nb, tab, cap - 1);
-    HIPCHK(hipGetLastError());
+    HIPCHK(fj_launch_gt_pair_build(ka, kb, (u64)nb, tab, cap - 1, s));
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     hipLaunchKernelGGL(fj_gt_pair_sweep_kernel, dim3(gt_grid(cap)), dim3(1024), 0, s, tab, cap - 1, ids, d_ok, (u64)cap_out, &c->d_sc->total, &c->d_sc->err);
@@ -313,8 +324,7 @@ int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_
     begin_plan(c);
     HIPCHK(hipEventRecord(c->ev[E_START], s));
     if (clear_plan_scalars(c, s)) return 1;
-    hipLaunchKernelGGL(fj_pair_combine_kernel, dim3(gt_grid(nb)), dim3(1024), 0, s, ka, kb, words, (u64)nb);
-    HIPCHK(hipGetLastError());
+    HIPCHK(fj_launch_pair_combine(ka, kb, words, (u64)nb, s));
     FjGroupByArgs ga{};
     PassIter it;
     pass_init(it, 0, true, nb, plan, top_bits);
@@ -335,3 +345,10 @@ int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_
 }
 
 }  // namespace fjh
+
+hipError_t fj_launch_pair_combine(const u64* A, const u64* B, u64* out, u64 nb, hipStream_t s) {
+    if (!A || !B || !out) return hipErrorInvalidValue;
+    if (!nb) return hipSuccess;
+    hipLaunchKernelGGL(fj_pair_combine_kernel, dim3(fjh::gt_grid(nb)), dim3(1024), 0, s, A, B, out, nb);
+    return hipGetLastError();
+}

@@ -415,6 +415,12 @@ int group_by_merge(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size
 // group id at the row's position, and d_ok the g row indices of the groups' first occurrences; nb <= 2^40, cap_out >= nb
 int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_t nb, int top_bits, hipStream_t s, fj_timings* t,
                   u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out);
+// ... with FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL (fj_groupby_pair_agg.hip): the key is the PAIR (ka[i], kb[i]) and kv the value column, nb
+// words each (fj_join_device takes kv as d_probe_keys: the one group-by form with a third column); d_ok receives column A of the g
+// groups and d_ov FIVE planes of cap_out words - column B, then count, sum, min, max of kv as group_by_all writes them; kind as above;
+// nb <= 2^40, cap_out >= 1; g > cap_out fails after the device work with *out_count = g
+int group_by_pair_agg(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, const u64* kv, size_t nb, int top_bits, hipStream_t s,
+                      fj_timings* t, u64* out_count, u64* d_ok, u64* d_ov, size_t cap_out, int kind);
 
 // ... with FJ_ALGO_GROUP_ROWS (fj_groupby_rows.hip): d_ov is two planes of cap_out >= nb words - the nb row indices in group order, and
 // the first word of them that belongs to each of the g groups; nb <= 2^40

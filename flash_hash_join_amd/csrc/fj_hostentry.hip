@@ -188,6 +188,7 @@ int fj_join_host(int algo, int bloom, int materialize,
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;
     const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;            // partial rows in: build_vals is FOUR planes of nb words
+    const bool pagg = kpair && aall && !inv;                                     // a two-column key with four aggregates: probe_keys is the VALUE column (np == nb), *out_keys g words of A, *out_vals 5 * g words - B, count, sum, min, max
     if (algo >= 0 && (algo & FJ_ALGO_GROUP_ROWS) && !gb)
         return set_err("fj_join_host: unknown algo %d (FJ_ALGO_GROUP_ROWS modifies FJ_ALGO_GROUP_BY)", algo);
     if (grows && (algo & (FJ_ALGO_INVERSE | FJ_ALGO_ROW_IDS | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_AGG_MERGE | FJ_ALGO_KEY_PAIR)))
@@ -203,6 +204,20 @@ int fj_join_host(int algo, int bloom, int materialize,
                           (gb ? FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR | FJ_ALGO_GROUP_ROWS : 0) | (amerge ? FJ_ALGO_AGG_MERGE : 0);                                 // modifiers of FJ_ALGO_GROUP_BY: unknown without it
     if (gb) {                                                  // group-by on one relation (the build side): *out_keys g keys, *out_vals g aggregates; no probe side
         const bool amin = (algo & FJ_ALGO_AGG_MIN) != 0, amax = (algo & FJ_ALGO_AGG_MAX) != 0, asigned = (algo & FJ_ALGO_AGG_SIGNED) != 0;
+        if (pagg) {                                            // (the checks of fj_join_device, before the context is created)
+            if (many_host || left || anti || full || allc || po || bo)
+                return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
+                               many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+            if (amin || amax || rid || aarg || amerge)
+                return set_err("fj_join_host: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (out_vals is taken by column B and the four aggregates of the value column)",
+                               amin ? "AGG_MIN" : amax ? "AGG_MAX" : rid ? "ROW_IDS" : aarg ? "AGG_ARG" : "AGG_MERGE");
+            if (asigned && (algo & FJ_ALGO_AGG_FLOAT)) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs materialize = 1 (the pairs and their aggregates are the result)");
+            if (!out_keys || !out_vals || (nb && (!bk || !bv || !pk)))
+                return set_err("fj_join_host: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs build_keys, build_vals, probe_keys, out_keys and out_vals (the key columns A and B, the value column V, column A of the g groups and five planes of g words)");
+            if (np != nb) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs np == nb, got np = %zu and nb = %zu (probe_keys is the value column of the one relation)", np, nb);
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
+        }
         if (amerge) {                                          // FJ_ALGO_AGG_ALL's refusals under this flag's name, ahead of them
             if (many_host || left || anti || full || allc || po || bo)
                 return set_err("fj_join_host: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (it merges partial group-by rows: there is no join in it)",
@@ -217,7 +232,7 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (many_host || left || anti || full || allc || po || bo)
             return set_err("fj_join_host: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many_host ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
-        if (pk || np) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (!pagg && (pk || np)) return set_err("fj_join_host: FJ_ALGO_GROUP_BY takes no probe side (probe_keys must be NULL and np 0: the relation to group is the build side)");
         if (aall) {                                            // four aggregates: *out_vals is 4 * g words, plane-major with stride g
             if (amin || amax) return set_err("fj_join_host: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_AGG_%s (it holds both the minimum and the maximum)", amin ? "MIN" : "MAX");
             if (rid || inv) return set_err("fj_join_host: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (out_vals is taken by the four aggregates)", rid ? "ROW_IDS" : "INVERSE");
@@ -246,7 +261,7 @@ int fj_join_host(int algo, int bloom, int materialize,
             if (!materialize) return set_err("fj_join_host: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
         }
         if (kpair) {                                           // the ids as above; *out_keys: the row index of every group's first occurrence
-            if (!inv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing)");
+            if (!inv && !pagg) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing) or FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL (the pairs with four aggregates of a third column)");
             if (nb && !bv) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR needs build_vals (the second key column, nb words)");
             if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_host: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
         }
@@ -477,11 +492,11 @@ int fj_join_host(int algo, int bloom, int materialize,
         if (out_vals) *out_vals = hs;
         joined = true;
     }
-    if (aall || aarg) {                                                        // g keys and four (FJ_ALGO_AGG_ARG: two) planes of g words; the device planes have stride nb
+    if (aall || aarg) {                                                        // g keys and four (FJ_ALGO_AGG_ARG: two; with FJ_ALGO_KEY_PAIR: five) planes of g words; the device planes have stride nb
         void *dok = nullptr, *dov = nullptr;
-        const size_t cap = std::max<size_t>(nb, 1), planes = aall ? 4 : 2;
+        const size_t cap = std::max<size_t>(nb, 1), planes = pagg ? 5 : aall ? 4 : 2;
         if (get_buf(c, W_H_OK, cap * 8, &dok) || get_buf(c, W_H_OV, planes * cap * 8, &dov)) return 1;
-        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, nullptr, 0, js, 64,
+        if (fj_join_device(c, algo, bloom, materialize, (const u64*)dbk, (const u64*)dbv, nb, pagg ? (const u64*)dpk : nullptr, pagg ? np : 0, js, 64,   // (the pair form's value column)
                            &count, (u64*)dok, (u64*)dov, cap, &t)) return 1;
         const size_t g = (size_t)count;
         u64* hk = (u64*)malloc(std::max<size_t>(g, 1) * 8);

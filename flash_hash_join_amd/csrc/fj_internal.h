@@ -471,6 +471,11 @@ hipError_t fj_launch_group_by_merge(const FjGroupByArgs& a, const u64* planes, u
 // ... on the global table of fj_launch_gt_build_first (vals = false) over a.bk: acc as for fj_launch_gt_group_by_all_combine; one thread
 // per partial row combines planes[q * a.nb + i] into all four.  fj_launch_gt_group_by_all_sweep compacts
 hipError_t fj_launch_gt_group_by_merge_combine(const FjGtArgs& a, int kind, const u64* planes, u64* acc, hipStream_t s);
+// two-column keys (csrc/fj_groupby_pair.hip; FJ_ALGO_KEY_PAIR), the pieces its forms share: out[i] = fj_key_pair(A[i], B[i]) for i < n;
+// and the global table of ROW INDICES over the pairs - tab: cap_mask + 1 >= 2 nb words, all ones before the launch; behind it every
+// pair's slot holds the pair's smallest row, and rows are found by comparing pairs from the home slot fj_hash64(fj_key_pair(a, b)) & cap_mask
+hipError_t fj_launch_pair_combine(const u64* A, const u64* B, u64* out, u64 n, hipStream_t s);
+hipError_t fj_launch_gt_pair_build(const u64* A, const u64* B, u64 nb, u64* tab, u64 cap_mask, hipStream_t s);
 
 // ---- full outer join (FJ_ALGO_FULL_OUTER): the left outer join above plus the build rows nobody asked for ------------------------
 // bits: one bit per build row, indexed by the row's place in the build side's final chunk pool (chunk id * FJ_CHUNK + offset; flat

@@ -676,6 +676,8 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
     const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
     const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;   // a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE: d_build_vals is a second KEY column (csrc/fj_groupby_pair.hip)
     const uint64_t* d_kb = nullptr;                         // ... that column
+    const bool pagg = kpair && !inv && (algo & FJ_ALGO_AGG_ALL) != 0;   // ... or of FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL: the pairs and four aggregates of a THIRD column, d_probe_keys (csrc/fj_groupby_pair_agg.hip)
+    const uint64_t* d_kv = nullptr;                         // ... that column
     const bool grows = gb && (algo & FJ_ALGO_GROUP_ROWS) != 0;   // another modifier of FJ_ALGO_GROUP_BY alone: the rows of every group, two planes of d_out_vals (csrc/fj_groupby_rows.hip)
     const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
     const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
@@ -707,6 +709,22 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
         // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
         algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR | FJ_ALGO_GROUP_ROWS);
+        if (pagg) {                                         // a two-column key with four aggregates: d_build_keys = A, d_build_vals = B, d_probe_keys = the value column V, np == nb
+            if (many || left || anti || full || allc || po || bo)
+                return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
+                               many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
+            if (amin || amax || rid || aarg || amerge)
+                return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (d_out_vals is taken by column B and the four aggregates of the value column)",
+                               amin ? "AGG_MIN" : amax ? "AGG_MAX" : rid ? "ROW_IDS" : aarg ? "AGG_ARG" : "AGG_MERGE");
+            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
+            if (!materialize) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs materialize = 1 (the pairs and their aggregates are the result)");
+            if (nb && (!d_bk || !d_bv || !d_pk || !d_out_keys || !d_out_vals))
+                return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs d_build_keys, d_build_vals, d_probe_keys, d_out_keys and d_out_vals (the key columns A and B, the value column V, column A of the g groups and five planes of out_capacity words)");
+            if (np != nb) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs np == nb, got np = %zu and nb = %zu (d_probe_keys is the value column of the one relation)", np, nb);
+            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs an output capacity of at least 1 row (any bound on the number of groups will do)");
+            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
+            d_kv = d_pk;
+        }
         if (amerge) {                                       // partial rows in, FJ_ALGO_AGG_ALL's outputs out: its refusals under this flag's name, ahead of them
             algo &= ~FJ_ALGO_AGG_MERGE;
             if (many || left || anti || full || allc || po || bo)
@@ -723,7 +741,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (many || left || anti || full || allc || po || bo)
             return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
                            many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
-        if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
+        if (!pagg && (d_pk || np)) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
         if (aall) {                                         // four aggregates in four planes of d_out_vals; any out_capacity >= 1 (g is checked after the device work)
             if (amin || amax) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_AGG_%s (it holds both the minimum and the maximum)", amin ? "MIN" : "MAX");
             if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the four aggregates)", rid ? "ROW_IDS" : "INVERSE");
@@ -754,7 +772,7 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
             if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_INVERSE needs d_out_keys and d_out_vals (the g distinct keys and the nb group ids that index them)");
         }
         if (kpair) {                                        // a two-column key: the group ids as above, d_out_keys the row index of every group's first occurrence
-            if (!inv) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing)");
+            if (!inv && !pagg) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing) or FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL (the pairs with four aggregates of a third column)");
             if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR needs d_build_vals (the second key column, nb words)");
             if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
             if ((uintptr_t)d_bv & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
@@ -906,6 +924,14 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
         if (timings) *timings = t;
         last_timings() = t;
         return 0;
+    }
+    if (pagg) {                                             // ... under a two-column key with four aggregates of d_kv; g beyond the capacity fails with *out_count = g
+        const int rc = group_by_pair_agg(c, use_radix, d_bk, d_kb, d_kv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
+                                         afloat ? 2 : asigned ? 1 : 0);
+        if (out_count) *out_count = count;
+        if (timings) *timings = t;
+        last_timings() = t;
+        return rc;
     }
     if (amerge) {                                           // ... of partial rows: the four planes of the rows of one key combined; g beyond the capacity as below
         const int rc = group_by_merge(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,

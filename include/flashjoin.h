@@ -320,7 +320,9 @@ extern "C" {
  * malloc'ed array of g words, *out_vals one of 4 * g words, plane-major with stride g; both pointers are required.
  * Refused up front, before any device work, in addition to what FJ_ALGO_GROUP_BY refuses: combined with FJ_ALGO_AGG_MIN or
  * FJ_ALGO_AGG_MAX (it holds both), with FJ_ALGO_ROW_IDS or FJ_ALGO_INVERSE, with FJ_ALGO_AGG_SIGNED and FJ_ALGO_AGG_FLOAT together;
- * materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity == 0 (and nb > 0); a misaligned output. */
+ * materialize = 0; d_build_vals, d_out_keys or d_out_vals == NULL (and nb > 0); out_capacity == 0 (and nb > 0); a misaligned output.
+ * With FJ_ALGO_KEY_PAIR beside it (and without FJ_ALGO_INVERSE) the key is a PAIR of columns and d_out_vals holds FIVE planes: the
+ * form FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL, described under FJ_ALGO_KEY_PAIR. */
 #define FJ_ALGO_AGG_ALL    0x4000000
 /* EXTENSION: a modifier of FJ_ALGO_GROUP_BY (without it an unknown algo; csrc/fj_groupby_arg.hip): the ROW that holds each group's
  * minimum or maximum - pandas idxmin / idxmax, SQL arg_min / arg_max - so that the caller can gather the row's other columns.  OR it
@@ -372,7 +374,8 @@ extern "C" {
  * FJ_ALGO_INVERSE, FJ_ALGO_AGG_SIGNED with FJ_ALGO_AGG_FLOAT, materialize = 0, a NULL d_build_vals, d_out_keys or d_out_vals with
  * nb > 0, out_capacity == 0 with nb > 0, a misaligned buffer), FJ_ALGO_AGG_ARG beside it, and whatever FJ_ALGO_GROUP_BY refuses. */
 #define FJ_ALGO_AGG_MERGE  0x10000000
-/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (in every other combination refused; csrc/fj_groupby_pair.hip): the key of
+/* EXTENSION: a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE, or of FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL (the second form, below; in every
+ * other combination refused; csrc/fj_groupby_pair.hip): the key of
  * the group-by is a PAIR of columns - (customer, day), (src, dst), (tenant, user).  OR it into `algo` together with FJ_ALGO_GROUP_BY,
  * FJ_ALGO_INVERSE and a base value (ADAPTIVE, SCALAR or RADIX), materialize = 1:
  *   d_build_keys       column A, nb words.
@@ -392,8 +395,35 @@ extern "C" {
  * distinct combined words, or two pairs on one word).
  * fj_join_host: build_vals is column B; *out_keys is a malloc'ed array of exactly g row indices, *out_vals one of exactly nb ids; a
  * NULL pointer drops that output.
- * Refused up front, before any device work: the flag without FJ_ALGO_GROUP_BY (an unknown algo); with it but without FJ_ALGO_INVERSE;
- * everything FJ_ALGO_INVERSE and FJ_ALGO_GROUP_BY refuse; a NULL d_build_vals with nb > 0; nb > 2^40. */
+ * Refused up front, before any device work: the flag without FJ_ALGO_GROUP_BY (an unknown algo); with it but without FJ_ALGO_INVERSE
+ * or FJ_ALGO_AGG_ALL (the form below); everything FJ_ALGO_INVERSE and FJ_ALGO_GROUP_BY refuse; a NULL d_build_vals with nb > 0; nb > 2^40.
+ *
+ * FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL (csrc/fj_groupby_pair_agg.hip): the pairs themselves with FOUR aggregates of a third column -
+ * SELECT a, b, COUNT(*), SUM(v), MIN(v), MAX(v) ... GROUP BY a, b - in ONE call, without the group ids.  OR both into `algo` together
+ * with FJ_ALGO_GROUP_BY and a base value (ADAPTIVE, SCALAR or RADIX), optionally with FJ_ALGO_AGG_SIGNED or with FJ_ALGO_AGG_FLOAT,
+ * WITHOUT FJ_ALGO_INVERSE, materialize = 1:
+ *   d_build_keys       column A, nb words.
+ *   d_build_vals       column B, nb words: a KEY column.
+ *   d_probe_keys       the VALUE column V, nb words, and np == nb: the one form of FJ_ALGO_GROUP_BY that takes a third column.
+ *                      All three are required (nb > 0) and 16-byte aligned.  nb <= 2^40.
+ *   d_out_keys[r]      for r < g: A of group r.
+ *   d_out_vals         FIVE planes of out_capacity words each, row r of every plane belonging to group r -
+ *                        plane 0  B of group r
+ *                        planes 1 .. 4  the row count, the sum, the minimum and the maximum of V over the group's rows: planes 0 .. 3 of
+ *                                 FJ_ALGO_AGG_ALL, with its semantics, kinds, NaN and signed-zero rules
+ * *out_count = g; the order of the groups is unspecified.  out_capacity may be ANY value >= 1; g > out_capacity fails AFTER the device
+ * work with an error that states g, with *out_count = g, and the context stays usable.  nb == 0: g = 0, nothing is written, no buffer
+ * is needed.  bloom is ignored.  Never a pending result.  Exact for every input: a table slot keeps the smallest and the largest b it
+ * met, two pairs on one combined word differ in b, and where that shows the call runs again on an HBM table that compares pairs.
+ * fj_timings as for FJ_ALGO_AGG_ALL: the combined words and the passes in build_phase_ms, the aggregation in join_ms ==
+ * probe_phase_ms, emit_ms = 0; fell_back = 1 when the call ran again on the HBM table (a final partition of more than 1920 distinct
+ * combined words, or two pairs on one word).
+ * fj_join_host: the same roles - probe_keys is V, np == nb; *out_keys is a malloc'ed array of g words, *out_vals one of 5 * g words,
+ * plane-major with stride g; both pointers are required.
+ * Refused up front, before any device work: combined with FJ_ALGO_AGG_MIN, FJ_ALGO_AGG_MAX, FJ_ALGO_ROW_IDS, FJ_ALGO_AGG_ARG,
+ * FJ_ALGO_AGG_MERGE or FJ_ALGO_GROUP_ROWS (with FJ_ALGO_INVERSE: FJ_ALGO_AGG_ALL's refusal of it); FJ_ALGO_AGG_SIGNED and
+ * FJ_ALGO_AGG_FLOAT together; materialize = 0; a NULL A, B, V, d_out_keys or d_out_vals with nb > 0; np != nb; out_capacity == 0 with
+ * nb > 0; nb > 2^40; a misaligned buffer; and whatever FJ_ALGO_GROUP_BY refuses but the probe side. */
 #define FJ_ALGO_KEY_PAIR   0x20000000
 /* EXTENSION: a modifier of FJ_ALGO_GROUP_BY alone (without it an unknown algo; csrc/fj_groupby_rows.hip): the ROWS of every group - the
  * relation's row indices in group-contiguous order and the offset at which every group starts, a CSR of row indices.  What pandas

@@ -20,7 +20,8 @@ form, appended to --out:
 Workloads: u1m = 100M rows over 1M distinct keys, uniform; distinct = 100M rows, all distinct; b1g = 1B rows over 100M distinct keys;
 hot = 100M rows over 1M keys of which one owns every tenth row.  Two-column keys (not in the default list): p1k = 100M rows over
 1000 x 1000 values, p10k = 100M rows over 10 000 x 10 000 values - the lines factorize_columns and "factorize x3 + multiply-add", its
-composition from the single-key entry (_pair_workload).  Times of (a) are device times (core_duration_sec, HIP events); (b) is
+composition from the single-key entry (_pair_workload), and group_by_agg_columns beside "factorize_columns + group_by_agg + 2
+gathers", the composition it replaces, the two alternating step by step (_pair_agg_lines).  Times of (a) are device times (core_duration_sec, HIP events); (b) is
 torch kernels, so its figure is wall time around a synchronised region, and (a) is reported that way too ("wall_median_ms") so that
 the two compare like with like.  "timings" of (a) carry the split: build_phase_ms = the relation's passes, join_ms = the kernel - for
 the hot workload the kernel's time is the one long work item's (the hot key's partition)."""
@@ -86,6 +87,71 @@ def _pair_workload(flash_join, torch, wl, args, out):
         out.write(line + "\n")
         out.flush()
         torch.cuda.empty_cache()
+    _pair_agg_lines(flash_join, torch, wl, a, b, args, out)
+
+
+def _by_pair(torch, ga, gb, *cols):
+    """the columns in (a, b) order: a stable sort by b, then by a"""
+    o = torch.argsort(gb, stable=True)
+    o = o[torch.argsort(ga[o], stable=True)]
+    return [c[o] for c in (ga, gb) + cols]
+
+
+def _pair_agg_lines(flash_join, torch, wl, a, b, args, out):
+    """four aggregates per pair (FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL): group_by_agg_columns next to the composition it replaces -
+    factorize_columns, group_by_agg over the codes and the two gathers through first_index.  The two results are compared, aligned
+    by pair, before anything is timed; then the forms ALTERNATE step by step in this one process.  device_median_ms is the library's
+    own time (the composition: the sum of its two calls; its gathers are torch kernels and show in wall_median_ms only); "timings"
+    carries the split of every library call."""
+    names = ("group_by_agg_columns", "factorize_columns + group_by_agg + 2 gathers")
+    if args.names and not any(nm in args.names.split(",") for nm in names):
+        return
+    n = a.numel()
+    v = torch.randint(-2**63, 2**63 - 1, (n,), dtype=torch.int64, device=a.device)
+    split = {}
+
+    def fused():
+        g, sec, (ga, gb), cnt, sm, mn, mx = flash_join.group_by_agg_columns((a, b), v)
+        split[names[0]] = {k: flash_join.last_timings()[k] for k in KEEP}
+        return g, sec, ga, gb, cnt, sm, mn, mx
+
+    def composed():
+        g, s1, codes, first = flash_join.factorize_columns((a, b))
+        t1 = {k: flash_join.last_timings()[k] for k in KEEP}
+        g2, s2, gk, cnt, sm, mn, mx = flash_join.group_by_agg(codes, v)
+        split[names[1]] = {"factorize_columns": t1, "group_by_agg": {k: flash_join.last_timings()[k] for k in KEEP}}
+        rows = first[gk]
+        return g2, s1 + s2, a[rows], b[rows], cnt, sm, mn, mx
+
+    rf, rc = fused(), composed()
+    assert rf[0] == rc[0], (rf[0], rc[0])
+    for x, y in zip(_by_pair(torch, *rf[2:]), _by_pair(torch, *rc[2:])):
+        assert torch.equal(x, y), "group_by_agg_columns and its composition disagree"
+    g = rf[0]
+    del rf, rc, x, y
+    torch.cuda.empty_cache()
+    fns = (fused, composed)
+    dev, wall = ([], []), ([], [])
+    for i in range(args.warmup + args.steps):
+        for j, fn in enumerate(fns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            assert r[0] == g, (r[0], g)
+            if i >= args.warmup:
+                dev[j].append(r[1] * 1e3)
+                wall[j].append((t1 - t0) * 1e3)
+            del r
+    for j, name in enumerate(names):
+        line = json.dumps({"workload": wl, "rows": n, "distinct": g, "form": "a", "name": name, "alternating": True,
+                           "device_median_ms": round(statistics.median(dev[j]), 3), "device_min_ms": round(min(dev[j]), 3),
+                           "wall_median_ms": round(statistics.median(wall[j]), 3), "timings": split[name]})
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+    torch.cuda.empty_cache()
 
 
 def main():
