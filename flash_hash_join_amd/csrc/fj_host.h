@@ -3,6 +3,7 @@
 //   fj_joins.hip  one-shot joins (the reference's drivers, hash_join.cpp:315-594), emit, owner split, bloom export / prefilter
 //   fj_prepared.hip  a build side prepared once and probed many times (FJ_ALGO_RETAIN_BUILD / FJ_ALGO_REUSE_BUILD)
 //   fj_stream.hip joins whose relations arrive in pieces, the owner shuffle's pack / append side
+//   fj_entry.hip  the algo word decoded once and the one refusal list of fj_join_device and fj_join_host (fj_entry.h: not included here)
 //   fj_hostentry.hip  the NumPy (host-buffer) entry
 // (one file, fj_api.hip, until round 4).
 #pragma once

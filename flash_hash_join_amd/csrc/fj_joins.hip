@@ -2,6 +2,7 @@
 // materialize} and adaptive_hash_join_* (hash_join.cpp:315-594); emit, owner split, bloom export / prefilter.
 // (Split out of fj_api.hip in round 4; see fj_host.h for the map.)
 #include "fj_host.h"
+#include "fj_entry.h"
 
 namespace fjh {
 
@@ -665,411 +666,125 @@ int fj_join_device(fj_ctx* c, int algo, int bloom, int materialize,
                    const uint64_t* d_bk, const uint64_t* d_bv, size_t nb, const uint64_t* d_pk, size_t np,
                    void* stream, int hash_top_bits, uint64_t* out_count,
                    uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, fj_timings* timings) {
-    const bool many = algo >= 0 && (algo & FJ_ALGO_MANY_TO_MANY) != 0;
-    const bool left = algo >= 0 && (algo & FJ_ALGO_LEFT_OUTER) != 0, anti = algo >= 0 && (algo & FJ_ALGO_ANTI) != 0;
-    const bool rid = algo >= 0 && (algo & FJ_ALGO_ROW_IDS) != 0;
-    const bool full = algo >= 0 && (algo & FJ_ALGO_FULL_OUTER) != 0;
-    const bool allc = algo >= 0 && (algo & FJ_ALGO_ALL_COPIES) != 0;
-    const bool po = algo >= 0 && (algo & FJ_ALGO_PROBE_ORDER) != 0;
-    const bool bo = algo >= 0 && (algo & FJ_ALGO_BUILD_ORDER) != 0;
-    const bool gb = algo >= 0 && (algo & FJ_ALGO_GROUP_BY) != 0;
-    const bool inv = gb && (algo & FJ_ALGO_INVERSE) != 0;   // a modifier of FJ_ALGO_GROUP_BY: an unknown algo without it
-    const bool kpair = gb && (algo & FJ_ALGO_KEY_PAIR) != 0;   // a modifier of FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE: d_build_vals is a second KEY column (csrc/fj_groupby_pair.hip)
-    const uint64_t* d_kb = nullptr;                         // ... that column
-    const bool pagg = kpair && !inv && (algo & FJ_ALGO_AGG_ALL) != 0;   // ... or of FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL: the pairs and four aggregates of a THIRD column, d_probe_keys (csrc/fj_groupby_pair_agg.hip)
-    const uint64_t* d_kv = nullptr;                         // ... that column
-    const bool grows = gb && (algo & FJ_ALGO_GROUP_ROWS) != 0;   // another modifier of FJ_ALGO_GROUP_BY alone: the rows of every group, two planes of d_out_vals (csrc/fj_groupby_rows.hip)
-    const bool aall = gb && (algo & FJ_ALGO_AGG_ALL) != 0;  // another one: count, sum, min and max in four planes of d_out_vals (csrc/fj_groupby_multi.hip)
-    const bool aarg = gb && (algo & FJ_ALGO_AGG_ARG) != 0;  // and another: the row that holds the minimum or the maximum, two planes (csrc/fj_groupby_arg.hip)
-    const bool amerge = gb && aall && (algo & FJ_ALGO_AGG_MERGE) != 0;   // a modifier of that PAIR: the build side is partial rows with four planes (csrc/fj_groupby_merge.hip)
-    const bool retain = po && (algo & FJ_ALGO_RETAIN_BUILD) != 0, reuse = po && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // modifiers of FJ_ALGO_PROBE_ORDER: unknown algos without it
-    const bool bo_reuse = bo && (algo & FJ_ALGO_REUSE_BUILD) != 0;   // the aggregate join onto the prepared side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_RETAIN_BUILD stays unknown)
-    const bool accum = bo_reuse && (algo & FJ_ALGO_ACCUMULATE) != 0; // a modifier of that combination only: an unknown algo anywhere else
-    const uint64_t* d_rv = nullptr;                         // FJ_ALGO_RETAIN_BUILD: the caller's d_build_vals as given (null: a keys-only side)
-    const bool amin = (bo || gb) && (algo & FJ_ALGO_AGG_MIN) != 0, amax = (bo || gb) && (algo & FJ_ALGO_AGG_MAX) != 0,
-               asigned = (bo || gb) && (algo & FJ_ALGO_AGG_SIGNED) != 0, afloat = (bo || gb) && (algo & FJ_ALGO_AGG_FLOAT) != 0;
-    int agg = FJ_GJ_SUM;                                    // FJ_ALGO_BUILD_ORDER / FJ_ALGO_GROUP_BY: what d_out_vals receives
-    const int algo_word = algo;
-    if (algo >= 0 && (algo & FJ_ALGO_GROUP_ROWS) && !gb)
-        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_GROUP_ROWS modifies FJ_ALGO_GROUP_BY)", algo_word);
-    if (grows && (algo & (FJ_ALGO_INVERSE | FJ_ALGO_ROW_IDS | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_AGG_MERGE | FJ_ALGO_KEY_PAIR)))
-        return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the row indices and the groups' starts, and no value column is read)",
-                       (algo & FJ_ALGO_INVERSE) ? "INVERSE" : (algo & FJ_ALGO_ROW_IDS) ? "ROW_IDS" : (algo & FJ_ALGO_AGG_MIN) ? "AGG_MIN" : (algo & FJ_ALGO_AGG_MAX) ? "AGG_MAX" :
-                       (algo & FJ_ALGO_AGG_SIGNED) ? "AGG_SIGNED" : (algo & FJ_ALGO_AGG_FLOAT) ? "AGG_FLOAT" : (algo & FJ_ALGO_AGG_ALL) ? "AGG_ALL" : (algo & FJ_ALGO_AGG_ARG) ? "AGG_ARG" :
-                       (algo & FJ_ALGO_AGG_MERGE) ? "AGG_MERGE" : "KEY_PAIR");
-    if (algo >= 0 && (algo & FJ_ALGO_AGG_MERGE) && !amerge)
-        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_AGG_MERGE modifies FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL)", algo_word);
-    if (algo >= 0 && (algo & FJ_ALGO_KEY_PAIR) && !gb)
-        return set_err("fj_join_device: unknown algo %d (FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE)", algo_word);
-    if (many) algo &= ~FJ_ALGO_MANY_TO_MANY;
-    const uint64_t* d_pv = nullptr;                         // FJ_ALGO_BUILD_ORDER: d_build_vals is the PROBE side's value column
-    const uint64_t* d_gv = nullptr;                         // FJ_ALGO_GROUP_BY: d_build_vals is the relation's value column (null: the count form)
-    if (gb) {
-        // group-by on one relation (csrc/fj_groupby.hip): every check before any device work, so that it holds for a null context too.
-        // The relation is the build side; d_out_keys = the g distinct keys, d_out_vals = one aggregate per key.  The three aggregate
-        // flags modify this flag or FJ_ALGO_BUILD_ORDER: without either they are an unknown algo below
-        algo &= ~(FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT | FJ_ALGO_ROW_IDS | FJ_ALGO_INVERSE | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_ARG | FJ_ALGO_KEY_PAIR | FJ_ALGO_GROUP_ROWS);
-        if (pagg) {                                         // a two-column key with four aggregates: d_build_keys = A, d_build_vals = B, d_probe_keys = the value column V, np == nb
-            if (many || left || anti || full || allc || po || bo)
-                return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
-                               many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
-            if (amin || amax || rid || aarg || amerge)
-                return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (d_out_vals is taken by column B and the four aggregates of the value column)",
-                               amin ? "AGG_MIN" : amax ? "AGG_MAX" : rid ? "ROW_IDS" : aarg ? "AGG_ARG" : "AGG_MERGE");
-            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs materialize = 1 (the pairs and their aggregates are the result)");
-            if (nb && (!d_bk || !d_bv || !d_pk || !d_out_keys || !d_out_vals))
-                return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs d_build_keys, d_build_vals, d_probe_keys, d_out_keys and d_out_vals (the key columns A and B, the value column V, column A of the g groups and five planes of out_capacity words)");
-            if (np != nb) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs np == nb, got np = %zu and nb = %zu (d_probe_keys is the value column of the one relation)", np, nb);
-            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL needs an output capacity of at least 1 row (any bound on the number of groups will do)");
-            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
-            d_kv = d_pk;
-        }
-        if (amerge) {                                       // partial rows in, FJ_ALGO_AGG_ALL's outputs out: its refusals under this flag's name, ahead of them
-            algo &= ~FJ_ALGO_AGG_MERGE;
-            if (many || left || anti || full || allc || po || bo)
-                return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (it merges partial group-by rows: there is no join in it)",
-                               many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
-            if (d_pk || np) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE takes no probe side (d_probe_keys must be NULL and np 0: the partial rows are the build side)");
-            if (amin || amax) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_AGG_%s (it merges both the minima and the maxima)", amin ? "MIN" : "MAX");
-            if (rid || inv || aarg) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE cannot be combined with FJ_ALGO_%s (a partial row is no row of a relation)", rid ? "ROW_IDS" : inv ? "INVERSE" : "AGG_ARG");
-            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs materialize = 1 (the merged rows are the result)");
-            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs d_build_vals, d_out_keys and d_out_vals (four planes of nb words - count, sum, min, max -, the g distinct keys and four planes of out_capacity words)");
-            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_AGG_MERGE needs an output capacity of at least 1 row (any bound on the number of groups will do)");
-        }
-        if (many || left || anti || full || allc || po || bo)
-            return set_err("fj_join_device: FJ_ALGO_GROUP_BY cannot be combined with FJ_ALGO_%s (it groups one relation: there is no join in it)",
-                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : po ? "PROBE_ORDER" : "BUILD_ORDER");
-        if (!pagg && (d_pk || np)) return set_err("fj_join_device: FJ_ALGO_GROUP_BY takes no probe side (d_probe_keys must be NULL and np 0: the relation to group is the build side)");
-        if (aall) {                                         // four aggregates in four planes of d_out_vals; any out_capacity >= 1 (g is checked after the device work)
-            if (amin || amax) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_AGG_%s (it holds both the minimum and the maximum)", amin ? "MIN" : "MAX");
-            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_ALL cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the four aggregates)", rid ? "ROW_IDS" : "INVERSE");
-            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
-            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs d_build_vals, d_out_keys and d_out_vals (the value column, the g distinct keys and four planes of out_capacity words)");
-            if (nb && !out_capacity) return set_err("fj_join_device: FJ_ALGO_AGG_ALL needs an output capacity of at least 1 row (any bound on the number of groups will do)");
-        }
-        if (aarg) {                                         // the row of each group's extreme: d_out_vals is two planes, the row index and the extreme
-            if (aall) return set_err("fj_join_device: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_AGG_ALL (d_out_vals is taken by the four aggregates)");
-            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_ARG cannot be combined with FJ_ALGO_%s (d_out_vals is taken by the row indices and the extremes)", rid ? "ROW_IDS" : "INVERSE");
-            if (amin == amax) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs exactly one of FJ_ALGO_AGG_MIN and FJ_ALGO_AGG_MAX (%s)", amin ? "both are set: call twice" : "neither is set");
-            if (asigned && afloat) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
-            if (nb && (!d_bv || !d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_AGG_ARG needs d_build_vals, d_out_keys and d_out_vals (the value column, the g distinct keys and two planes of out_capacity words)");
-        }
-        if (afloat) {                                       // the value column and d_out_vals hold IEEE-754 doubles
-            if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (rid || inv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_%s (positions and group ids are integers)", rid ? "ROW_IDS" : "INVERSE");
-            if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_GROUP_BY needs d_build_vals (the float64 value column, nb words: the count form has no float form)");
-        }
-        if (inv) {                                          // the group id of every row (d_out_vals: nb words), no aggregate beside it
-            if (amin || amax || asigned)
-                return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_AGG_%s (the ids group the rows once: every aggregate is a pass of the caller's over them)",
-                               amin ? "MIN" : amax ? "MAX" : "SIGNED");
-            if (rid) return set_err("fj_join_device: FJ_ALGO_INVERSE cannot be combined with FJ_ALGO_ROW_IDS (d_out_vals is taken: one per-call output)");
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_INVERSE needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
-            if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_INVERSE needs d_out_keys and d_out_vals (the g distinct keys and the nb group ids that index them)");
-        }
-        if (kpair) {                                        // a two-column key: the group ids as above, d_out_keys the row index of every group's first occurrence
-            if (!inv && !pagg) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR modifies FJ_ALGO_GROUP_BY | FJ_ALGO_INVERSE (the group ids of a two-column key are its result: FJ_ALGO_INVERSE is missing) or FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL (the pairs with four aggregates of a third column)");
-            if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR needs d_build_vals (the second key column, nb words)");
-            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_KEY_PAIR takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
-            if ((uintptr_t)d_bv & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
-            d_kb = d_bv;
-        }
-        if (grows) {                                        // the rows of every group: d_out_vals is two planes, the nb row indices and the g starts (no other modifier: refused above)
-            if (!materialize) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
-            if (nb && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS needs d_out_keys and d_out_vals (the g distinct keys and two planes of out_capacity words: the nb row indices and the g starts)");
-            if ((uint64_t)nb > (1ull << 40)) return set_err("fj_join_device: FJ_ALGO_GROUP_ROWS takes at most 2^40 rows, got %zu (a row position is kept in 40 bits)", nb);
-        }
-        if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
-        if (asigned && !amin && !amax && !aall) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
-        if ((amin || amax) && nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_%s with FJ_ALGO_GROUP_BY needs d_build_vals (the value column, nb words)", amin ? "MIN" : "MAX");
-        if (rid && (amin || amax)) return set_err("fj_join_device: FJ_ALGO_ROW_IDS cannot be combined with FJ_ALGO_AGG_%s under FJ_ALGO_GROUP_BY (the first occurrence's position IS the aggregate)", amin ? "MIN" : "MAX");
-        if (rid && !materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS with FJ_ALGO_GROUP_BY needs materialize = 1 (materialize = 0 returns the number of distinct keys alone)");
-        if (materialize) {
-            if (nb && !d_out_keys) return set_err("fj_join_device: FJ_ALGO_GROUP_BY with materialize = 1 needs d_out_keys (d_out_vals is optional; materialize = 0 returns the number of distinct keys alone)");
-            if (!aall && out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu rows (FJ_ALGO_GROUP_BY: every row may be a group of its own)", out_capacity, nb);
-            if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
-        }
-        if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
-        if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
-        if (afloat) agg = amin ? FJ_GJ_MIN_F : amax ? FJ_GJ_MAX_F : FJ_GJ_SUM_F;
-        if (!amin && !amax && !d_bv) agg = FJ_GJ_COUNT;
-        d_gv = (rid || inv || grows) ? nullptr : d_bv;
-        if (!d_bv || rid || inv || grows) d_bv = d_bk;                      // (the count form and the positions read no value; the checks below want a pointer)
-    }
-    if (bo) {
-        // build-order aggregate join (csrc/fj_group.hip): every check before any device work, so that it holds for a null context too.
-        // d_out_keys = the counts, d_out_vals = the sums (FJ_ALGO_AGG_MIN / FJ_ALGO_AGG_MAX: the minima / maxima), nb words each.
-        // The three aggregate flags are modifiers of this one: without it they are an unknown algo below
-        algo &= ~(FJ_ALGO_BUILD_ORDER | FJ_ALGO_AGG_MIN | FJ_ALGO_AGG_MAX | FJ_ALGO_AGG_SIGNED | FJ_ALGO_AGG_FLOAT);
-        if (bo_reuse) algo &= ~(FJ_ALGO_REUSE_BUILD | FJ_ALGO_ACCUMULATE);
-        if (many || left || anti || rid || full || allc || po)
-            return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER cannot be combined with FJ_ALGO_%s (it has one row per build row, at the build row's position)",
-                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : rid ? "ROW_IDS" : full ? "FULL_OUTER" : allc ? "ALL_COPIES" : "PROBE_ORDER");
-        // onto the prepared build side (csrc/fj_prepared.hip): no build side in the call - d_build_vals is the PROBE side's value column
-        // here, so it is not looked at; the outputs hold NB words, the rows the side was prepared from (checked on the context)
-        if (afloat) {                                       // the probe side's value column and d_out_vals hold IEEE-754 doubles
-            if (asigned) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT cannot be combined with FJ_ALGO_AGG_SIGNED (a double carries its own sign)");
-            if (np && !d_bv) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs d_build_vals (here the probe side's float64 value column, np words: the count form has no float form)");
-            if ((nb || bo_reuse) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_FLOAT with FJ_ALGO_BUILD_ORDER needs d_out_vals (the float64 aggregates; the counts alone are the plain count form)");
-        }
-        if (bo_reuse && (d_bk || nb)) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD takes no build side (d_build_keys must be NULL and nb 0: the context's prepared side is aggregated onto; d_build_vals is the probe side's value column)");
-        if (amin && amax) return set_err("fj_join_device: FJ_ALGO_AGG_MIN cannot be combined with FJ_ALGO_AGG_MAX (one aggregate per call: call twice)");
-        if (asigned && !amin && !amax) return set_err("fj_join_device: FJ_ALGO_AGG_SIGNED modifies FJ_ALGO_AGG_MIN or FJ_ALGO_AGG_MAX (the sum is taken modulo 2^64 and has no sign)");
-        if (!materialize) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs materialize = 1 (its outputs are the result; P alone is the many-to-many counting join's)");
-        if ((nb || bo_reuse) && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER needs an output (the counts d_out_keys, the sums d_out_vals, or both)");
-        if ((nb || bo_reuse) && (amin || amax) && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_AGG_%s needs d_out_vals (the counts alone are the plain count form of FJ_ALGO_BUILD_ORDER)", amin ? "MIN" : "MAX");
-        if (out_capacity < nb) return set_err("fj_join_device: output capacity %zu < %zu build rows (FJ_ALGO_BUILD_ORDER writes every build row)", out_capacity, nb);
-        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
-        if (np && d_out_vals && !d_bv) return set_err("fj_join_device: FJ_ALGO_BUILD_ORDER with d_out_vals needs d_build_vals (here the probe side's value column, np words)");
-        if (amin) agg = asigned ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
-        if (amax) agg = asigned ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
-        if (afloat) agg = amin ? FJ_GJ_MIN_F : amax ? FJ_GJ_MAX_F : FJ_GJ_SUM_F;
-        d_pv = d_bv;
-        if (!d_bv) d_bv = d_bk;                             // the counts read no value (the checks below want a pointer)
-    }
-    if (po) {
-        // probe-order join (csrc/fj_aligned.hip): every check before any device work, so that it holds for a null context too.
-        // d_out_keys is the byte mask here: no alignment asked of it
-        algo &= ~(FJ_ALGO_PROBE_ORDER | FJ_ALGO_RETAIN_BUILD | FJ_ALGO_REUSE_BUILD);
-        if (many || left || anti || full || allc)
-            return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER cannot be combined with FJ_ALGO_%s (it has one row per probe row, at the probe row's position)",
-                           many ? "MANY_TO_MANY" : left ? "LEFT_OUTER" : anti ? "ANTI" : full ? "FULL_OUTER" : "ALL_COPIES");
-        if (!materialize) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER needs materialize = 1 (its match count is the counting join's)");
-        if (np && !d_out_keys && !d_out_vals) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER needs an output (d_out_vals, the byte mask d_out_keys, or both)");
-        if (out_capacity < np) return set_err("fj_join_device: output capacity %zu < %zu probe rows (FJ_ALGO_PROBE_ORDER writes every probe row)", out_capacity, np);
-        if ((uintptr_t)d_out_vals & 7) return set_err("fj_join_device: d_out_vals must be 8-byte aligned");
-        // the prepared build side (csrc/fj_prepared.hip): one call prepares OR reuses, and a reuse brings no build side of its own
-        if (retain && reuse) return set_err("fj_join_device: FJ_ALGO_RETAIN_BUILD cannot be combined with FJ_ALGO_REUSE_BUILD (a call prepares a build side or probes the prepared one)");
-        if (reuse && (d_bk || d_bv || nb)) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD takes no build side (d_build_keys and d_build_vals must be NULL and nb 0: the context's prepared side is probed)");
-        if (nb && d_out_vals && !rid && !d_bv) return set_err("fj_join_device: FJ_ALGO_PROBE_ORDER with d_out_vals needs d_build_vals (only FJ_ALGO_ROW_IDS and the mask alone read no build value)");
-        d_rv = d_bv;
-        if (!d_bv) d_bv = d_bk;                             // the mask alone reads no value (the checks below want a pointer)
-    }
-    if (rid && !gb) {
-        // row positions instead of keys and values: checked before any device work, so that it holds for a null context too
-        algo &= ~FJ_ALGO_ROW_IDS;
-        if (!materialize) return set_err("fj_join_device: FJ_ALGO_ROW_IDS needs materialize = 1 (it changes what the output rows hold)");
-        if (!d_bv) d_bv = d_bk;                             // never read: the build rows' positions are made on the device
-        bloom = 0;                                          // (the filter kernel moves no payload)
-    }
-    if (allc) {
-        // left / full outer join that keeps every copy of a duplicated build key (csrc/fj_many.hip): every check before any device
-        // work, so that it holds for a null context too.  The result's size is not known up front: no capacity check here, the
-        // two-phase rule of the materialising joins applies (count, then fj_emit_pairs - or both in this call)
-        algo &= ~(FJ_ALGO_ALL_COPIES | FJ_ALGO_LEFT_OUTER | FJ_ALGO_FULL_OUTER);
-        if (anti) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_ANTI (an anti join has no copies to keep)");
-        if (many) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES cannot be combined with FJ_ALGO_MANY_TO_MANY (that flag alone is the inner join that keeps every copy)");
-        if (!left && !full) return set_err("fj_join_device: unknown algo %d (FJ_ALGO_ALL_COPIES modifies FJ_ALGO_LEFT_OUTER or FJ_ALGO_FULL_OUTER; FJ_ALGO_MANY_TO_MANY is the inner form)", algo_word);
-        if (left && full) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_LEFT_OUTER");
-        if (!materialize) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs materialize = 1 (there is no counting-only form)");
-        if (!out_count) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs out_count (three words: pairs, unmatched build rows, unmatched probe rows)");
-        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
-        if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_ALL_COPIES needs d_build_vals (only FJ_ALGO_ROW_IDS reads no build value)");
-    }
-    if (full && !allc) {
-        // full outer join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
-        algo &= ~FJ_ALGO_FULL_OUTER;
-        if (left || anti) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_%s", left ? "LEFT_OUTER" : "ANTI");
-        if (many) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER cannot be combined with FJ_ALGO_MANY_TO_MANY");
-        if (!materialize) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs materialize = 1 (its match count is the counting join's)");
-        if ((np || nb) && (!d_out_keys || !d_out_vals)) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs output buffers (d_out_keys and d_out_vals)");
-        if (out_capacity < np || out_capacity - np < nb) return set_err("fj_join_device: output capacity %zu < %zu probe rows + %zu build rows (FJ_ALGO_FULL_OUTER may write every row of both sides)", out_capacity, np, nb);
-        if (((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
-        if (nb && !d_bv) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs d_build_vals (only FJ_ALGO_ROW_IDS reads no build value)");
-        if (!out_count) return set_err("fj_join_device: FJ_ALGO_FULL_OUTER needs out_count (two words: matched probe rows, unmatched build rows)");
-    }
-    if ((left || anti) && !allc) {
-        // left outer / anti join (csrc/fj_outer.hip): every check before any device work, so that it holds for a null context too
-        algo &= ~(FJ_ALGO_LEFT_OUTER | FJ_ALGO_ANTI);
-        if (left && anti) return set_err("fj_join_device: FJ_ALGO_LEFT_OUTER and FJ_ALGO_ANTI cannot be combined");
-        if (many) return set_err("fj_join_device: FJ_ALGO_%s cannot be combined with FJ_ALGO_MANY_TO_MANY", left ? "LEFT_OUTER" : "ANTI");
-        if (left && !materialize) return set_err("fj_join_device: FJ_ALGO_LEFT_OUTER needs materialize = 1 (its match count is the counting join's)");
-        if (materialize) {
-            if (np && (!d_out_keys || (left && !d_out_vals))) return set_err("fj_join_device: FJ_ALGO_%s needs output buffers (d_out_keys%s)", left ? "LEFT_OUTER" : "ANTI", left ? " and d_out_vals" : "");
-            if (out_capacity < np) return set_err("fj_join_device: output capacity %zu < %zu probe rows (FJ_ALGO_%s writes every probe row)", out_capacity, np, left ? "LEFT_OUTER" : "ANTI");
-            if (((uintptr_t)d_out_keys | (uintptr_t)(left ? d_out_vals : nullptr)) & 7) return set_err("fj_join_device: output buffers must be 8-byte aligned");
-        }
-        if (!left && !d_bv) d_bv = d_bk;                    // an anti join reads no value (the counting paths below want a pointer)
-    }
-    if (algo < 0 || algo > 2) return set_err("fj_join_device: unknown algo %d", algo);
-    if (hash_top_bits != 64 && hash_top_bits != 48) return set_err("fj_join_device: hash_top_bits must be 64 or 48");
-    if ((nb && (!d_bk || !d_bv)) || (np && !d_pk)) return set_err("fj_join_device: null input pointer");
-    if (((uintptr_t)d_bk | (uintptr_t)d_bv | (uintptr_t)d_pk) & 15) return set_err("fj_join_device: input pointers must be 16-byte aligned");
+    const AlgoForm f = decode_algo(algo);
+    EntryArgs ea{materialize, d_bk, d_bv, nb, d_pk, np, out_count, d_out_keys, d_out_vals};
+    ea.cap = out_capacity; ea.top_bits = hash_top_bits;
+    if (check_entry(f, DEVICE_ENTRY, ea)) return 1;         // every refusal that needs no context: it holds for a null one too
+    // d_build_vals as the call gave it: the relation's value column (FJ_ALGO_GROUP_BY; null: the count form), its second key column
+    // (FJ_ALGO_KEY_PAIR), the PROBE side's value column (FJ_ALGO_BUILD_ORDER), the side to prepare (FJ_ALGO_RETAIN_BUILD; null: keys only)
+    const uint64_t* d_col = d_bv;
+    const uint64_t* d_gv = (f.rid || f.inv || f.grows) ? nullptr : d_col;   // ... as a group-by reads it
+    int agg = f.agg;
+    if (f.gb && !f.amin && !f.amax && !d_bv) agg = FJ_GJ_COUNT;
+    if (build_vals_unread(f, d_bv != nullptr)) d_bv = d_bk;  // (never read: the paths below want a pointer)
+    if (f.rid && !f.gb) bloom = 0;                          // (the filter kernel moves no payload)
+    algo = f.base;
     FJ_ENTER(c);
     if (begin_step(c, "fj_join_device")) return 1;
     hipStream_t s = (hipStream_t)stream;
     fj_timings t; memset(&t, 0, sizeof t);
     t.sampled_hit_bp = -1;
-    u64 count = 0;
+    u64 counts[3] = {0, 0, 0};                              // what *out_count receives: one word, FJ_ALGO_FULL_OUTER two, FJ_ALGO_ALL_COPIES three
+    u64& count = counts[0];
+    const int ncounts = f.allc ? 3 : f.full ? 2 : 1;
     const Options& opt = options();
     bool use_radix = algo == FJ_ALGO_RADIX || (algo == FJ_ALGO_ADAPTIVE && nb >= opt.radix_threshold) ||
                      (algo == FJ_ALGO_SCALAR && !opt.scalar_hbm_table);
-    if (allc) {                                             // every copy of a duplicated build key: the many-to-many kernel's outer forms, always the partitioned plan
-        u64 c3[3] = {0, 0, 0};
+    u64 *const d_ok = (u64*)d_out_keys, *const d_ov = (u64*)d_out_vals;
+    // One branch per form; each leaves rc, the counts and the timings for the ONE epilogue below.  The forms whose g may exceed the
+    // capacity (FJ_ALGO_AGG_ALL and what modifies it) fail with *out_count = g and their timings published: publish_failed
+    int rc = 0;
+    bool publish_failed = false;
+    if (f.allc) {                                           // every copy of a duplicated build key: the many-to-many kernel's outer forms, always the partitioned plan
         if (nb == 0 || np == 0) {
             // an empty side needs no join: every row of the other side is unmatched (emit_pending copies them)
             if (clear_plan_scalars(c, s)) return 1;
-            c3[1] = (np == 0 && full) ? nb : 0; c3[2] = nb == 0 ? np : 0;
+            counts[1] = (np == 0 && f.full) ? nb : 0; counts[2] = nb == 0 ? np : 0;
             Pending& pd = c->pend;
-            pd.valid = true; pd.kind = Pending::MANY; pd.mm_outer = full ? FJ_MM_FULL : FJ_MM_LEFT; pd.mm_trivial = true;
-            pd.lds.row_ids = rid ? 1u : 0u; pd.bk = d_bk; pd.bv = d_bv; pd.mm_pk = d_pk;
-            pd.mm_P = 0; pd.mm_u = c3[2]; pd.mm_r = c3[1]; pd.count = c3[1] + c3[2];
-        } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, c3, rid, full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
-        out_count[0] = c3[0]; out_count[1] = c3[1]; out_count[2] = c3[2];
-        if (d_out_keys && d_out_vals && emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (pagg) {                                             // ... under a two-column key with four aggregates of d_kv; g beyond the capacity fails with *out_count = g
-        const int rc = group_by_pair_agg(c, use_radix, d_bk, d_kb, d_kv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
-                                         afloat ? 2 : asigned ? 1 : 0);
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return rc;
-    }
-    if (amerge) {                                           // ... of partial rows: the four planes of the rows of one key combined; g beyond the capacity as below
-        const int rc = group_by_merge(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
-                                      afloat ? 2 : asigned ? 1 : 0);
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return rc;
-    }
-    if (aall) {                                             // ... and four aggregates beside it; g beyond the capacity fails with *out_count = g
-        const int rc = group_by_all(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
-                                    afloat ? 2 : asigned ? 1 : 0);
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return rc;
-    }
-    if (aarg) {                                             // ... or the row index and the extreme beside it (out_capacity >= nb was checked)
-        if (group_by_arg(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity,
-                         afloat ? 2 : asigned ? 1 : 0, amax)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (grows) {                                            // ... or the rows of every group: nb row indices and g starts, never a pending result
-        if (group_rows(c, use_radix, d_bk, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (kpair) {                                            // ... under a two-column key: nb ids and g first rows, never a pending result
-        if (group_by_pair(c, use_radix, d_bk, d_kb, nb, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, out_capacity)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (gb) {                                               // one row per distinct key, never a pending result
-        if (group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? (u64*)d_out_keys : nullptr,
-                     materialize ? (u64*)d_out_vals : nullptr, out_capacity, agg, rid, inv)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (bo_reuse) {                                         // ... onto the build side the context keeps prepared (csrc/fj_prepared.hip)
+            pd.valid = true; pd.kind = Pending::MANY; pd.mm_outer = f.full ? FJ_MM_FULL : FJ_MM_LEFT; pd.mm_trivial = true;
+            pd.lds.row_ids = f.rid ? 1u : 0u; pd.bk = d_bk; pd.bv = d_bv; pd.mm_pk = d_pk;
+            pd.mm_P = 0; pd.mm_u = counts[2]; pd.mm_r = counts[1]; pd.count = counts[1] + counts[2];
+        } else if (join_many(c, 1, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, counts, f.rid, f.full ? FJ_MM_FULL : FJ_MM_LEFT)) return 1;
+        for (int i = 0; i < 3; ++i) out_count[i] = counts[i];                   // (the counts are the caller's before the emit: a capacity too small leaves the rows pending)
+        if (d_ok && d_ov && emit_pending(c, d_ok, d_ov, out_capacity, s, &t)) return 1;
+    } else if (f.pagg) {                                    // group-by under a two-column key with four aggregates of d_probe_keys (csrc/fj_groupby_pair_agg.hip)
+        rc = group_by_pair_agg(c, use_radix, d_bk, d_col, d_pk, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity, f.kind);
+        publish_failed = true;
+    } else if (f.amerge) {                                  // ... of partial rows: the four planes of the rows of one key combined (csrc/fj_groupby_merge.hip)
+        rc = group_by_merge(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity, f.kind);
+        publish_failed = true;
+    } else if (f.aall) {                                    // ... with four aggregates beside the keys (csrc/fj_groupby_multi.hip)
+        rc = group_by_all(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity, f.kind);
+        publish_failed = true;
+    } else if (f.aarg) {                                    // ... or the row index and the extreme beside them (csrc/fj_groupby_arg.hip; out_capacity >= nb was checked)
+        rc = group_by_arg(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity, f.kind, f.amax);
+    } else if (f.grows) {                                   // ... or the rows of every group: nb row indices and g starts (csrc/fj_groupby_rows.hip)
+        rc = group_rows(c, use_radix, d_bk, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity);
+    } else if (f.kpair) {                                   // ... under a two-column key: nb ids and g first rows (csrc/fj_groupby_pair.hip)
+        rc = group_by_pair(c, use_radix, d_bk, d_col, nb, hash_top_bits, s, &t, &count, d_ok, d_ov, out_capacity);
+    } else if (f.gb) {                                      // one row per distinct key (csrc/fj_groupby.hip)
+        rc = group_by(c, use_radix, d_bk, d_gv, nb, hash_top_bits, s, &t, &count, materialize ? d_ok : nullptr, materialize ? d_ov : nullptr, out_capacity, agg, f.rid, f.inv);
+    } else if (f.bo_reuse) {                                // the aggregate join onto the build side the context keeps prepared (csrc/fj_prepared.hip)
         if (!c->prep.valid) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD without a prepared build side on this context (FJ_ALGO_RETAIN_BUILD makes one)");
         if (hash_top_bits != c->prep.top_bits) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with hash_top_bits %d, the build side was prepared with %d", hash_top_bits, c->prep.top_bits);
         if (out_capacity < c->prep.nb) return set_err("fj_join_device: output capacity %zu < %zu rows of the prepared build side (FJ_ALGO_BUILD_ORDER | FJ_ALGO_REUSE_BUILD defines every one of them)", out_capacity, c->prep.nb);
-        if (prepared_group(c, d_pk, d_pv, np, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, agg, accum)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (bo) {                                               // one row per build row at its own position, never a pending result
-        if (join_group(c, use_radix, d_bk, nb, d_pk, d_pv, np, hash_top_bits, s, &t, &count, (u64*)d_out_keys, (u64*)d_out_vals, agg)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (po && (retain || reuse)) {                          // ... against a build side the context keeps prepared (csrc/fj_prepared.hip)
-        if (retain) {
-            if (prepared_retain(c, use_radix, d_bk, d_rv, nb, hash_top_bits, s, &t)) { prepared_free(c); return 1; }   // (a failed call leaves none)
+        rc = prepared_group(c, d_pk, d_col, np, s, &t, &count, d_ok, d_ov, agg, f.accum);
+    } else if (f.bo) {                                      // one row per build row at its own position (csrc/fj_group.hip)
+        rc = join_group(c, use_radix, d_bk, nb, d_pk, d_col, np, hash_top_bits, s, &t, &count, d_ok, d_ov, agg);
+    } else if (f.retain || f.reuse) {                       // the probe-order join against a build side the context keeps prepared (csrc/fj_prepared.hip)
+        if (f.retain) {
+            if (prepared_retain(c, use_radix, d_bk, d_col, nb, hash_top_bits, s, &t)) { prepared_free(c); return 1; }   // (a failed call leaves none)
             count = c->prep.g;                              // np == 0: the call only prepares, *out_count = the distinct build keys
         } else {
             if (!c->prep.valid) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD without a prepared build side on this context (FJ_ALGO_RETAIN_BUILD makes one)");
             if (hash_top_bits != c->prep.top_bits) return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with hash_top_bits %d, the build side was prepared with %d", hash_top_bits, c->prep.top_bits);
-            if (np && d_out_vals && !rid && !c->prep.has_vals)
+            if (np && d_out_vals && !f.rid && !c->prep.has_vals)
                 return set_err("fj_join_device: FJ_ALGO_REUSE_BUILD with d_out_vals needs a build side prepared with d_build_vals (this one has keys only: the mask and FJ_ALGO_ROW_IDS work)");
         }
-        if (np || reuse) {
+        if (np || f.reuse) {
             fj_timings tp; memset(&tp, 0, sizeof tp); tp.sampled_hit_bp = -1;
-            if (prepared_probe(c, d_pk, np, s, &tp, &count, (unsigned char*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
-            if (retain) { tp.build_phase_ms = t.build_phase_ms; tp.total_ms += t.total_ms; tp.fell_back = t.fell_back; }
+            if (prepared_probe(c, d_pk, np, s, &tp, &count, (unsigned char*)d_out_keys, d_ov, f.rid)) return 1;
+            if (f.retain) { tp.build_phase_ms = t.build_phase_ms; tp.total_ms += t.total_ms; tp.fell_back = t.fell_back; }
             t = tp;
         }
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (po) {                                               // one row per probe row at its own position, never a pending result
-        if (join_probe_order(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, (unsigned char*)d_out_keys,
-                             (u64*)d_out_vals, rid)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (full) {                                             // the left join and the unmatched build rows in one plan, never a pending result
-        u64 counts[2] = {0, 0};
-        if (join_full(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, counts, (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
-        out_count[0] = counts[0]; out_count[1] = counts[1];
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if ((left || anti) && materialize) {                    // one pass over the probe side, never a pending result
-        if (join_outer(c, left ? FJ_OJ_LEFT : FJ_OJ_ANTI, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count,
-                       (u64*)d_out_keys, (u64*)d_out_vals, rid)) return 1;
-        if (out_count) *out_count = count;
-        if (timings) *timings = t;
-        last_timings() = t;
-        return 0;
-    }
-    if (nb == 0 || np == 0) {                   // empty side: (0, t), hash_join.cpp behaviour for empty inputs
-        count = 0;
-    } else if (many) {
-        if (join_many(c, materialize, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, rid)) return 1;
-    } else if (use_radix) {
-        bool lds_full = false;
-        // adaptive_*: the precheck is decided from a sample of the probe side; *_bloom by name: always on; otherwise off
-        const int bloom_mode = rid ? 0 : algo == FJ_ALGO_ADAPTIVE ? (options().bloom_auto ? 2 : (bloom ? 1 : 0)) : (bloom ? 1 : 0);
-        SingleOut so;
-        so.keys = (u64*)d_out_keys; so.vals = (u64*)d_out_vals; so.cap = out_capacity;
-        const bool try_single = materialize && d_out_keys && d_out_vals && out_capacity >= np && options().mat_single_pass &&
-                                !(((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7);
-        if (join_radix(c, materialize, bloom_mode, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, &lds_full, try_single ? &so : nullptr, rid)) return 1;
-        if (lds_full) {
-            fj_timings t2; memset(&t2, 0, sizeof t2);
-            if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t2, &count, rid)) return 1;
-            t2.total_ms += t.total_ms; t2.fell_back = 1; t2.sampled_hit_bp = t.sampled_hit_bp; t = t2;
+    } else if (f.po) {                                      // one row per probe row at its own position (csrc/fj_aligned.hip)
+        rc = join_probe_order(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, (unsigned char*)d_out_keys, d_ov, f.rid);
+    } else if (f.full) {                                    // the left join and the unmatched build rows in one plan (csrc/fj_outer.hip)
+        rc = join_full(c, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, counts, d_ok, d_ov, f.rid);
+    } else if ((f.left || f.anti) && materialize) {         // one pass over the probe side (csrc/fj_outer.hip)
+        rc = join_outer(c, f.left ? FJ_OJ_LEFT : FJ_OJ_ANTI, use_radix, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, d_ok, d_ov, f.rid);
+    } else {                                                // the counting joins and the materialising inner joins: the only forms that leave a pending result
+        if (nb == 0 || np == 0) {                           // empty side: (0, t), hash_join.cpp behaviour for empty inputs
+            count = 0;
+        } else if (f.many) {
+            if (join_many(c, materialize, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, f.rid)) return 1;
+        } else if (use_radix) {
+            bool lds_full = false;
+            // adaptive_*: the precheck is decided from a sample of the probe side; *_bloom by name: always on; otherwise off
+            const int bloom_mode = f.rid ? 0 : algo == FJ_ALGO_ADAPTIVE ? (options().bloom_auto ? 2 : (bloom ? 1 : 0)) : (bloom ? 1 : 0);
+            SingleOut so;
+            so.keys = d_ok; so.vals = d_ov; so.cap = out_capacity;
+            const bool try_single = materialize && d_out_keys && d_out_vals && out_capacity >= np && options().mat_single_pass &&
+                                    !(((uintptr_t)d_out_keys | (uintptr_t)d_out_vals) & 7);
+            if (join_radix(c, materialize, bloom_mode, d_bk, d_bv, nb, d_pk, np, hash_top_bits, s, &t, &count, &lds_full, try_single ? &so : nullptr, f.rid)) return 1;
+            if (lds_full) {
+                fj_timings t2; memset(&t2, 0, sizeof t2);
+                if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t2, &count, f.rid)) return 1;
+                t2.total_ms += t.total_ms; t2.fell_back = 1; t2.sampled_hit_bp = t.sampled_hit_bp; t = t2;
+            }
+        } else {
+            if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t, &count, f.rid)) return 1;
         }
-    } else {
-        if (join_global(c, bloom, materialize, d_bk, d_bv, nb, d_pk, np, s, &t, &count, rid)) return 1;
+        if (f.anti) count = np - count;                     // counting anti join: the probe rows the N:1 count leaves out
+        if (out_count) *out_count = count;                  // (before the emit, as above)
+        if (materialize && d_out_keys && d_out_vals && c->pend.valid && emit_pending(c, d_ok, d_ov, out_capacity, s, &t)) return 1;
     }
-    if (anti) count = np - count;                           // counting anti join: the probe rows the N:1 count leaves out
-    if (out_count) *out_count = count;
-    if (materialize && d_out_keys && d_out_vals && c->pend.valid) {
-        if (emit_pending(c, d_out_keys, d_out_vals, out_capacity, s, &t)) return 1;
-    }
+    // the one epilogue: a failed form publishes nothing - but for the forms above that state g with their failure
+    if (rc && !publish_failed) return 1;
+    if (out_count) for (int i = 0; i < ncounts; ++i) out_count[i] = counts[i];
     if (timings) *timings = t;
     last_timings() = t;
-    return 0;
+    return rc;
 }
 
 int fj_emit_pairs(fj_ctx* c, uint64_t* d_out_keys, uint64_t* d_out_vals, size_t out_capacity, void* stream, fj_timings* timings) {
