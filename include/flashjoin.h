@@ -519,7 +519,7 @@ int fj_abi_version(void);
  *                        "bloom_auto_max_hit_bp" (default 2300 = 23 %; measured break-even 24 %) of them hit; 0: adaptive_*_bloom filter, adaptive_* do
  *                        not, as named.  The explicit hash_join*_bloom
  *                        functions always run the precheck when the plan has two or more passes; hash_join* never do.
- *   "bloom_variant"    - hash / bit layout of the filter, 0..2 (csrc/fj_bloom_dev.h; default 2).  Must be
+ *   "bloom_variant"    - hash / bit layout of the filter, 0..2 (csrc/fj_bloom_dev.h; default 0).  Must be
  *                        the same on every rank of a multi-GPU job (fj_bloom_prefilter checks it against the exporter's).
  *   "mat_single_pass"  - 1 (default): a materialising join whose output buffers hold >= np pairs runs single-pass (above);
  *                        0: always count, scan, emit.
