@@ -116,6 +116,16 @@ class LabEngine(HipEngine):
         """Filters of the final partitions this owner holds (build side complete), into the uint8 tensor `out`."""
         self._lib.check(self.L.fj_stream_export_part_filters(self.ctx, out.data_ptr(), self.torch.cuda.current_stream(self.index).cuda_stream))
 
+    def part_filter_sample(self, raw_keys, n: int, stride: int, filters, nb_total: int, world: int) -> int:
+        """How many of the n keys raw_keys[0], raw_keys[stride], ... some partition filter admits (fj_part_filter_sample; synchronous).
+        raw_keys must hold at least (n - 1) * stride + 1 keys."""
+        if n and raw_keys.numel() < (n - 1) * stride + 1:
+            raise ValueError(f"part_filter_sample: {n} keys at stride {stride} need {(n - 1) * stride + 1} keys, got {raw_keys.numel()}")
+        kept = ctypes.c_uint64(0)
+        self._lib.check(self.L.fj_part_filter_sample(self.ctx, raw_keys.data_ptr(), n, stride, filters.data_ptr(), nb_total, world,
+                                                     self.torch.cuda.current_stream(self.index).cuda_stream, ctypes.byref(kept)))
+        return int(kept.value)
+
     def shuffle_pack(self, keys, vals, nb_total: int, world: int, filters=None):
         """First pass of the global plan over local rows, rewritten for the wire (fj_shuffle_pack_begin / _counts / _finish).
         Returns (chunks, dir, used): per owner r a uint8 tensor of used[r] * shuffle_chunk_bytes() bytes (dense 256-key chunks
@@ -170,6 +180,13 @@ class LabEngine(HipEngine):
     # ---- build-broadcast form (csrc/fj_bcast.hip): probe rows never move, every rank's build rows travel as dense per-partition runs ----
     def bcast_region_bytes(self, nb_total: int, nkeys: int, with_vals: bool = False) -> int:
         return int(self.L.fj_bcast_region_bytes(nb_total, nkeys, int(with_vals)))
+
+    def bcast_piece_span(self, nb_total: int, nkeys: int, k_lo: int, k_hi: int, part: int):
+        """(offset, bytes) inside a region of nkeys keys of part `part` (0 offset table, 1 low words, 2 high-word plane, 3 values)
+        of the keys [k_lo, k_hi): what travels as one piece (fj_bcast_piece_span)."""
+        off, nbytes = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._lib.check(self.L.fj_bcast_piece_span(nb_total, nkeys, k_lo, k_hi, part, ctypes.byref(off), ctypes.byref(nbytes)))
+        return int(off.value), int(nbytes.value)
 
     def bcast_pack(self, keys, nb_total: int, region, pieces: int, vals=None) -> None:
         """Asynchronous: this rank's build keys (and values: a materialising step) -> `region` (a uint8 tensor view of
