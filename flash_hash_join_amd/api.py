@@ -171,75 +171,81 @@ def last_timings() -> Optional[dict]:
     return _last.as_dict() if _last is not None else None
 
 
-def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arrays: bool):
+def _take_host(ptr, rows: int, dtype=np.uint64) -> np.ndarray:
+    """`rows` elements of a library-owned host result, as a copy the caller keeps (fj_free_host takes the original); no rows: an
+    empty array of that dtype, whatever the pointer holds"""
+    if not rows:
+        return np.empty(0, dtype)
+    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(rows,)).copy()
+
+
+def _host_call(algo: int, bloom: int, materialize: int, a, b, rows_a: int, c, rows_c: int, want0: bool, want1: bool, read):
+    """ONE fj_join_host call on NumPy word columns (None: a null pointer): (count, seconds, what `read` returned).  count is the
+    three words the library may fill - a full outer join fills two (matched probe rows, unmatched build rows), ALL_COPIES three,
+    every other form the first.  The call's timings become last_timings().  want0 / want1: which of the two library-owned results
+    are asked for; `read(count, out0, out1)` copies what it needs of them with _take_host, and both are freed whatever it does.
+    read=None: no result is asked for, so there is nothing to free.  A failing call raises before anything is read or freed: the
+    library hands out no result then."""
     global _last
     L = _lib.load()
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    cnt, sec = (ctypes.c_uint64 * 3)(0, 0, 0), ctypes.c_double(0.0)
+    out0, out1 = ctypes.c_void_p(), ctypes.c_void_p()
+    check(L.fj_join_host(algo, bloom, materialize, ptr(a), ptr(b), rows_a, ptr(c), rows_c, cnt, ctypes.byref(sec),
+                         ctypes.byref(out0) if want0 else None, ctypes.byref(out1) if want1 else None))
+    t = FjTimings()
+    L.fj_last_timings(ctypes.byref(t))
+    _last = t
+    count = (int(cnt[0]), int(cnt[1]), int(cnt[2]))
+    if read is None:
+        return count, float(sec.value), None
+    try:
+        res = read(count, out0, out1)
+    finally:
+        L.fj_free_host(out0)
+        L.fj_free_host(out1)
+    return count, float(sec.value), res
+
+
+def _join_host(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arrays: bool):
     bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
     bv = _as_u64_host(bv, "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
     if bv is not None and bv.size < bk.size:
         raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
-    cnt = (ctypes.c_uint64 * 3)(0, 0, 0)                # (a full outer join fills two words: matched probe rows, unmatched build rows; ALL_COPIES three)
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
     want = bool(materialize and return_arrays)
-    check(L.fj_join_host(algo, bloom, materialize, bk.ctypes.data, bv.ctypes.data if bv is not None else None, bk.size, pk.ctypes.data, pk.size,
-                         cnt, ctypes.byref(sec),
-                         ctypes.byref(ok) if want else None, ctypes.byref(ov) if want else None))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    n = int(cnt[0])
-    if algo & ALGO_ALL_COPIES:          # P + u + r rows; the count is the triple (P, r, u)
-        c3 = (n, int(cnt[1]), int(cnt[2]))
-        if not want:
-            return c3, float(sec.value)
-        rows = sum(c3)
-        try:
-            arr = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
-                             else np.empty(0, np.uint64))
-            keys, vals = arr(ok), arr(ov)
-        finally:
-            L.fj_free_host(ok)
-            L.fj_free_host(ov)
-        return c3, float(sec.value), keys, vals
-    if algo & ALGO_FULL_OUTER:          # np + r rows; the count is the pair (m, r)
-        r = int(cnt[1])
-        if not want:
-            return (n, r), float(sec.value)
-        rows = pk.size + r
-        try:
-            arr = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
-                             else np.empty(0, np.uint64))
-            keys, vals = arr(ok), arr(ov)
-        finally:
-            L.fj_free_host(ok)
-            L.fj_free_host(ov)
-        return (n, r), float(sec.value), keys, vals
-    if not want:
-        return n, float(sec.value)
-    if algo & _OUTER:                   # left outer: np rows; anti: n keys and no values
-        rows = pk.size if algo & ALGO_LEFT_OUTER else n
-        try:
-            keys = (np.ctypeslib.as_array(ctypes.cast(ok, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
-                    else np.empty(0, np.uint64))
-            vals = None
-            if algo & ALGO_LEFT_OUTER:
-                vals = (np.ctypeslib.as_array(ctypes.cast(ov, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows
-                        else np.empty(0, np.uint64))
-        finally:
-            L.fj_free_host(ok)
-            L.fj_free_host(ov)
-        return n, float(sec.value), keys, vals
-    try:
-        if n:
-            keys = np.ctypeslib.as_array(ctypes.cast(ok, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy()
-            vals = np.ctypeslib.as_array(ctypes.cast(ov, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy()
-        else:
-            keys, vals = np.empty(0, np.uint64), np.empty(0, np.uint64)
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    return n, float(sec.value), keys, vals
+
+    def read(c, ok, ov):
+        if algo & ALGO_ALL_COPIES:          # P + u + r rows; the count is the triple (P, r, u)
+            rows = sum(c)
+        elif algo & ALGO_FULL_OUTER:        # np + r rows; the count is the pair (m, r)
+            rows = pk.size + c[1]
+        elif algo & ALGO_LEFT_OUTER:        # left outer: np rows
+            rows = pk.size
+        else:                               # inner: n pairs; anti: n keys and no values
+            rows = c[0]
+        keys_only = bool(algo & ALGO_ANTI) and not algo & (ALGO_ALL_COPIES | ALGO_FULL_OUTER | ALGO_LEFT_OUTER)
+        return _take_host(ok, rows), (None if keys_only else _take_host(ov, rows))
+    c, sec, arrays = _host_call(algo, bloom, materialize, bk, bv, bk.size, pk, pk.size, want, want, read if want else None)
+    n = c if algo & ALGO_ALL_COPIES else c[:2] if algo & ALGO_FULL_OUTER else c[0]
+    return (n, sec, *arrays) if want else (n, sec)
+
+
+def _device_index(t) -> int:
+    """the index of the ROCm device a tensor lives on (a device without an index: the current one)"""
+    if t.device.index is not None:
+        return t.device.index
+    import torch
+    return torch.cuda.current_device()
+
+
+def _trim(buf, g: int):
+    """The first g rows of a device buffer that was allocated with room for ANY result (the 3/4 rule).  A view of them would keep the
+    whole buffer alive for as long as the caller keeps the result - 16 bytes per PROBE row for the pairs of a join, 16 GB at config
+    3 for 8 GB of pairs.  So unless the rows fill most of it, hand back an exact-size copy (one device-to-device copy of g rows)
+    and let the big buffer go.  A (P, cap) buffer of planes is cut along cap: (P, g)."""
+    if buf is None:
+        return None
+    return buf[..., :g].clone() if g * 4 < buf.shape[-1] * 3 else buf[..., :g]
 
 
 def _dev_tensor(t, name: str):
@@ -278,7 +284,7 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
     bv = _dev_tensor(bv, "probe_values" if algo & ALGO_BUILD_ORDER else "build_values") if bv is not None else None      # (None: an anti join, which reads no value)
     if bv is not None and not algo & ALGO_BUILD_ORDER and bv.numel() < bk.numel():
         raise ValueError(f"build_values has {bv.numel()} elements, build_keys has {bk.numel()}")
-    dev = bk.device.index if bk.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(bk)
     ctx = context(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     cnt = ctypes.c_uint64(0)
@@ -345,12 +351,7 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
         _last = t
         if not return_arrays:
             return (m, r), t.total_ms * 1e-3
-        rows = n_p + r                      # exact size: copies unless the rows fill most of the buffers (the rule of the inner join below)
-        if rows * 4 < (n_p + n_b) * 3:
-            ok, ov = ok[:rows].clone(), ov[:rows].clone()
-        else:
-            ok, ov = ok[:rows], ov[:rows]
-        return (m, r), t.total_ms * 1e-3, ok, ov
+        return (m, r), t.total_ms * 1e-3, _trim(ok, n_p + r), _trim(ov, n_p + r)
     if (algo & _OUTER) and materialize:
         # left outer / anti join: np-row buffers always (a left join HAS np rows), one call, never a pending result to emit
         left = bool(algo & ALGO_LEFT_OUTER)
@@ -366,9 +367,7 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
             return n, t.total_ms * 1e-3
         if left:
             return n, t.total_ms * 1e-3, ok, ov
-        # anti: the first n rows; exact-size copy unless they fill most of the buffer (the rule of the inner join above)
-        ok = ok[:n].clone() if n * 4 < n_p * 3 else ok[:n]
-        return n, t.total_ms * 1e-3, ok, None
+        return n, t.total_ms * 1e-3, _trim(ok, n), None      # anti: the first n rows
     with _ctx_locks.setdefault(dev, threading.RLock()):      # count + emit are two calls on one context: keep other threads out
         out = None
         if (materialize and not (algo & (ALGO_MANY_TO_MANY | _OUTER)) and pk.numel() > 0 and bk.numel() > 0 and get_option("mat_single_pass")
@@ -382,14 +381,7 @@ def join_device(algo: int, bloom: int, materialize: int, bk, bv, pk, return_arra
             n = int(cnt.value)
             _last = t
             if return_arrays:
-                # the buffers hold room for ANY result; a view of their first n rows would keep 16 bytes per PROBE row alive for as
-                # long as the caller keeps the pairs (16 GB at config 3 for 8 GB of pairs).  Unless the result fills most of them,
-                # hand back exact-size copies (one device-to-device copy of n rows) and let the big buffers go.
-                if n * 4 < pk.numel() * 3:
-                    ok, ov = ok[:n].clone(), ov[:n].clone()
-                else:
-                    ok, ov = ok[:n], ov[:n]
-                return n, t.total_ms * 1e-3, ok, ov
+                return n, t.total_ms * 1e-3, _trim(ok, n), _trim(ov, n)
             return n, t.total_ms * 1e-3
         check(L.fj_join_device(ctx, algo, bloom, materialize, bk.data_ptr(), bv_ptr, bk.numel(), pk.data_ptr(),
                                pk.numel(), stream, hash_top_bits, ctypes.byref(cnt), None, None, 0, ctypes.byref(t)))
@@ -607,30 +599,14 @@ def semi_join_count(build_keys, probe_keys):
 
 # ---- extension: probe-order joins (one row per probe row, at the probe row's position; csrc/fj_aligned.hip) -------------------------
 def _probe_order_host(algo: int, bk, bv, pk, want_values: bool, want_mask: bool):
-    global _last
-    L = _lib.load()
     bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
     bv = _as_u64_host(bv, "build_values") if bv is not None else None
     if bv is not None and bv.size < bk.size:
         raise ValueError(f"build_values has {bv.size} elements, build_keys has {bk.size}")
-    cnt, sec = ctypes.c_uint64(0), ctypes.c_double(0.0)
-    om, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, bk.ctypes.data, bv.ctypes.data if bv is not None else None, bk.size, pk.ctypes.data, pk.size,
-                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(om) if want_mask else None, ctypes.byref(ov) if want_values else None))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    n = pk.size
-    try:
-        vals = mask = None
-        if want_values:
-            vals = (np.ctypeslib.as_array(ctypes.cast(ov, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy() if n else np.empty(0, np.uint64))
-        if want_mask:
-            mask = (np.ctypeslib.as_array(ctypes.cast(om, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy() if n else np.empty(0, np.uint8))
-    finally:
-        L.fj_free_host(om)
-        L.fj_free_host(ov)
-    return int(cnt.value), float(sec.value), vals, mask
+    n = pk.size                             # the mask comes back where a join's keys do: one byte per probe row
+    read = lambda c, om, ov: (_take_host(ov, n) if want_values else None, _take_host(om, n, np.uint8) if want_mask else None)
+    c, sec, (vals, mask) = _host_call(algo, 0, 1, bk, bv, bk.size, pk, n, want_mask, want_values, read)
+    return c[0], sec, vals, mask
 
 
 def _probe_order(algo: int, build_keys, build_values, probe_keys, want_values: bool, want_mask: bool):
@@ -772,7 +748,7 @@ class Index:
         if _is_torch_tensor(pk) and pk.is_cuda:
             import torch
             pk = _dev_tensor(pk, "probe_keys")
-            dev = pk.device.index if pk.device.index is not None else torch.cuda.current_device()
+            dev = _device_index(pk)
             if dev != self.device:
                 raise ValueError(f"probe_keys live on device {dev}, the index on device {self.device}")
             n_p = pk.numel()
@@ -847,7 +823,7 @@ class Index:
             import torch
             if buf.dtype != torch.int64:
                 raise TypeError(f"{name}: {what} must be int64, got {buf.dtype}")
-            if not buf.is_cuda or (buf.device.index if buf.device.index is not None else torch.cuda.current_device()) != self.device:
+            if not buf.is_cuda or _device_index(buf) != self.device:
                 raise ValueError(f"{name}: {what} lives on {buf.device}, the index on device {self.device}")
             if buf.dim() != 1 or buf.numel() != self.num_rows:
                 raise ValueError(f"{name}: {what} has shape {tuple(buf.shape)}, the index has {self.num_rows} rows")
@@ -890,7 +866,7 @@ class Index:
         if on_device:
             import torch
             pk = _dev_tensor(pk, "probe_keys")
-            dev = pk.device.index if pk.device.index is not None else torch.cuda.current_device()
+            dev = _device_index(pk)
             if dev != self.device:
                 raise ValueError(f"probe_keys live on device {dev}, the index on device {self.device}")
             n_p = pk.numel()
@@ -985,20 +961,8 @@ class Index:
     def _group_minmax(self, name: str, flag: int, probe_keys, probe_values, out, return_counts, counts_out, signed, float64: bool = False):
         if probe_values is None:
             raise ValueError(f"{name}: probe_values is required (group_count takes none)")
-        if float64:
-            pv = _float_words(name, "probe_values", probe_values, signed)
-            m, sec, vals, counts = self._group(name, probe_keys, pv, flag | ALGO_AGG_FLOAT, out, counts_out, return_counts, float64=True)
-            return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
-        if signed is not None and not isinstance(signed, (bool, np.bool_)):
-            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
-        probe_values = _from_dlpack_if_device(probe_values)
-        if _is_torch_tensor(probe_values):                       # the sign of the container, as in group_join_min
-            unsigned_in = str(probe_values.dtype) == "torch.uint64"
-        else:
-            probe_values = np.asarray(probe_values)
-            unsigned_in = probe_values.dtype == np.uint64
-        signed = (not unsigned_in) if signed is None else bool(signed)
-        m, sec, vals, counts = self._group(name, probe_keys, probe_values, flag | (ALGO_AGG_SIGNED if signed else 0), out, counts_out, return_counts)
+        pv, signed, _ = _word_column(name, "probe_values", probe_values, signed, float64, integers_only=False)      # the sign of the container, as in group_join_min
+        m, sec, vals, counts = self._group(name, probe_keys, pv, flag | _agg_flags(signed, float64), out, counts_out, return_counts, float64=float64)
         return (m, sec, vals, counts) if counts is not None else (m, sec, vals)
 
     def group_min(self, probe_keys, probe_values, out=None, return_counts: bool = False, counts_out=None, signed=None, float64: bool = False):
@@ -1042,7 +1006,7 @@ def build_index(build_keys, build_values=None, device: Optional[int] = None) -> 
         bk = _dev_tensor(bk, "build_keys")
         bv = _dev_tensor(bv, "build_values") if bv is not None else None
         n_b, n_v = bk.numel(), (bv.numel() if bv is not None else 0)
-        dev = bk.device.index if bk.device.index is not None else torch.cuda.current_device()
+        dev = _device_index(bk)
         if bv is not None and (not bv.is_cuda or bv.device != bk.device):
             raise ValueError("build_values must live on the device of build_keys")
     else:
@@ -1081,28 +1045,14 @@ def build_index(build_keys, build_values=None, device: Optional[int] = None) -> 
 
 # ---- extension: build-order aggregate joins (one word per build row, at the build row's position; csrc/fj_group.hip) -----------------
 def _group_host(algo: int, bk, pk, pv, want_counts: bool):
-    global _last
-    L = _lib.load()
     bk, pk = _as_u64_host(bk, "build_keys"), _as_u64_host(pk, "probe_keys")
     pv = _as_u64_host(pv, "probe_values") if pv is not None else None
     if pv is not None and pv.size != pk.size:
         raise ValueError(f"probe_values has {pv.size} elements, probe_keys has {pk.size}")
-    cnt, sec = ctypes.c_uint64(0), ctypes.c_double(0.0)
-    oc, osum = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, bk.ctypes.data, pv.ctypes.data if pv is not None else None, bk.size, pk.ctypes.data, pk.size,
-                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(oc) if want_counts else None, ctypes.byref(osum) if pv is not None else None))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    n = bk.size
-    try:
-        take = lambda p: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(n,)).copy() if n else np.empty(0, np.uint64)).view(np.int64)
-        counts = take(oc) if want_counts else None
-        sums = take(osum) if pv is not None else None
-    finally:
-        L.fj_free_host(oc)
-        L.fj_free_host(osum)
-    return int(cnt.value), float(sec.value), counts, sums
+    n, want_sums = bk.size, pv is not None  # the probe side's value column goes where a join takes its build values
+    read = lambda c, oc, osum: (_take_host(oc, n).view(np.int64) if want_counts else None, _take_host(osum, n).view(np.int64) if want_sums else None)
+    c, sec, (counts, sums) = _host_call(algo, 0, 1, bk, pv, n, pk, pk.size, want_counts, want_sums, read)
+    return c[0], sec, counts, sums
 
 
 def _group(build_keys, probe_keys, probe_values, want_counts: bool, agg: int = 0):
@@ -1148,23 +1098,9 @@ def group_join_sum(build_keys, probe_keys, probe_values, return_counts: bool = F
 def _group_minmax(name: str, flag: int, build_keys, probe_keys, probe_values, return_counts: bool, signed, float64: bool = False):
     if probe_values is None:
         raise ValueError(f"{name}: probe_values is required (group_join_count takes none)")
-    if float64:
-        pv = _float_words(name, "probe_values", probe_values, signed)
-        P, sec, counts, vals = _group(build_keys, probe_keys, pv, bool(return_counts), flag | ALGO_AGG_FLOAT)
-        return (P, sec, _as_float64(vals), counts) if return_counts else (P, sec, _as_float64(vals))
-    if signed is not None and not isinstance(signed, (bool, np.bool_)):
-        raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
-    # the sign of the container: a NumPy uint64 column (a torch.uint64 tensor) compares unsigned, everything else signed
-    probe_values = _from_dlpack_if_device(probe_values)      # (a device array of another library: a torch tensor from here on)
-    if _is_torch_tensor(probe_values):
-        unsigned_in = str(probe_values.dtype) == "torch.uint64"
-    else:
-        probe_values = np.asarray(probe_values)
-        unsigned_in = probe_values.dtype == np.uint64
-    signed = (not unsigned_in) if signed is None else bool(signed)
-    P, sec, counts, vals = _group(build_keys, probe_keys, probe_values, bool(return_counts), flag | (ALGO_AGG_SIGNED if signed else 0))
-    if unsigned_in and not signed and isinstance(vals, np.ndarray):
-        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
+    pv, signed, unsigned_in = _word_column(name, "probe_values", probe_values, signed, float64, integers_only=False)
+    P, sec, counts, vals = _group(build_keys, probe_keys, pv, bool(return_counts), flag | _agg_flags(signed, float64))
+    vals = _agg_values(vals, signed, unsigned_in, float64)
     return (P, sec, vals, counts) if return_counts else (P, sec, vals)
 
 
@@ -1194,68 +1130,81 @@ def group_join_max(build_keys, probe_keys, probe_values, return_counts: bool = F
 
 
 # ---- extension: group-by on one relation (the distinct keys and one aggregate per key; csrc/fj_groupby.hip) ----------------------------
-def _trim(buf, g: int):
-    """the first g rows of an n-row device buffer: an exact-size copy unless they fill most of it (the 3/4 rule of join_device)"""
-    if buf is None:
-        return None
-    return buf[:g].clone() if g * 4 < buf.shape[0] * 3 else buf[:g]
+def _group_columns(keys, values=None):
+    """(k, v, n): the key column and the value column (None: none) of a group-by on one relation as word columns of n rows where the
+    keys live - torch.int64 on the keys' device, or NumPy uint64"""
+    keys, values = (_from_dlpack_if_device(x) if x is not None else None for x in (keys, values))
+    if _is_torch_tensor(keys) and keys.is_cuda:
+        k = _dev_tensor(keys, "keys")
+        v = _dev_tensor(values, "values") if values is not None else None
+    else:
+        keys, values = (x.numpy() if _is_torch_tensor(x) else x for x in (keys, values))
+        k = _as_u64_host(keys, "keys")
+        v = _as_u64_host(values, "values") if values is not None else None
+    if v is not None and v.shape[0] != k.shape[0]:
+        raise ValueError(f"values has {v.shape[0]} elements, keys has {k.shape[0]}")
+    return k, v, k.shape[0]
+
+
+def _group_by_call(algo: int, a, b, c, n: int, vals, want_keys: bool = True, max_groups: Optional[int] = None, overflow: Optional[str] = None):
+    """ONE FJ_ALGO_GROUP_BY call where the inputs live: (g, seconds, group_keys or None, values or None).  a, b, c: up to three word
+    columns of n rows (None: none), all contiguous torch.int64 on one device - read in place on that device's current stream, under
+    its context and the context's lock - or all NumPy uint64; c travels as the probe side.  The outputs are torch.int64 tensors on
+    that device, or NumPy uint64 keys and int64 words.  vals is the layout of the values output:
+      None      none is wanted
+      "groups"  one word per group: g words
+      "rows"    one word per input row (ALGO_INVERSE): n words, never trimmed to g
+      "csr"     ALGO_GROUP_ROWS: the n row indices and then the g starts, n + g words (the device buffer holds two planes of n)
+      an int P  P planes: (P, g)
+    want_keys=False: nothing is materialised.  The device buffers hold n rows; those of the plane forms max(1, min(n, max_groups)) rows
+    (max_groups None: n).  overflow: the text, around {g}, of the ValueError for a result beyond max_groups."""
+    global _last
+    planes = vals if isinstance(vals, int) else 0
+    if not _is_torch_tensor(a):
+        def read(count, ok, ov):
+            g = count[0]
+            gk = _take_host(ok, g) if want_keys else None
+            if vals is None:
+                return gk, None
+            words = _take_host(ov, planes * g if planes else n if vals == "rows" else n + g if vals == "csr" else g).view(np.int64)
+            return gk, (words.reshape(planes, g) if planes else words)
+        count, sec, (gk, gv) = _host_call(algo, 0, int(want_keys), a, b, n, c, n if c is not None else 0, want_keys, vals is not None, read)
+        if overflow and max_groups is not None and count[0] > max_groups:      # (host arrays are sized by the library: the bound is checked all the same)
+            raise ValueError(overflow.format(g=count[0]))
+        return count[0], sec, gk, gv
+    import torch
+    L = _lib.load()
+    dev = _device_index(a)
+    ctx = context(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cap = max(1, n if max_groups is None else min(n, max_groups)) if planes else (n if want_keys else 0)
+    empty = lambda *shape: torch.empty(shape, dtype=torch.int64, device=a.device)
+    ok = empty(cap) if want_keys else None
+    ov = None if vals is None else empty(planes, cap) if planes else empty(2 * n if vals == "csr" else cap)
+    src = lambda x: x.data_ptr() if x is not None and n else None             # (no rows: null input pointers)
+    dst = lambda x: x.data_ptr() if x is not None else None
+    cnt, t = ctypes.c_uint64(0), FjTimings()
+    with _ctx_locks.setdefault(dev, threading.RLock()):
+        rc = L.fj_join_device(ctx, algo, 0, int(want_keys), src(a), src(b), n, src(c), n if c is not None else 0, stream, 64,
+                              ctypes.byref(cnt), dst(ok), dst(ov), cap, ctypes.byref(t))
+        g = int(cnt.value)
+        if rc and overflow and g > cap:                      # (the device work is done and the context usable: the buffers were too small)
+            raise ValueError(overflow.format(g=g))
+        check(rc)
+    _last = t
+    return g, t.total_ms * 1e-3, _trim(ok, g), (ov if vals in ("rows", "csr") else _trim(ov, g))
 
 
 def _group_by(keys, values, flags: int, materialize: bool = True, want_vals: bool = True):
     """(g, seconds, group_keys or None, aggregates or None), where the inputs live: NumPy uint64 keys and int64 words (the storage of
     the uint64 aggregates), or torch.int64 tensors on the inputs' device.  values=None: the count form (or ALGO_ROW_IDS in flags).
     ALGO_INVERSE in flags: the fourth item is the group id of every row instead - len(keys) int64 in [0, g), never trimmed to g."""
-    global _last
-    keys, values = (_from_dlpack_if_device(x) if x is not None else None for x in (keys, values))
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | flags
     inverse = bool(flags & ALGO_INVERSE)
     if inverse and not (materialize and want_vals):
         raise ValueError("ALGO_INVERSE: the group ids are the values output (materialize and want_vals)")
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
-    if _is_torch_tensor(keys) and keys.is_cuda:
-        import torch
-        k = _dev_tensor(keys, "keys")
-        v = _dev_tensor(values, "values") if values is not None else None
-        if v is not None and v.numel() != k.numel():
-            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
-        n = k.numel()
-        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(n, dtype=torch.int64, device=k.device) if materialize else None
-        ov = torch.empty(n, dtype=torch.int64, device=k.device) if materialize and want_vals else None
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            check(L.fj_join_device(ctx, algo, 0, int(materialize), k.data_ptr(), v.data_ptr() if v is not None else None, n, None, 0, stream, 64,
-                                   ctypes.byref(cnt), ok.data_ptr() if ok is not None else None, ov.data_ptr() if ov is not None else None,
-                                   n if materialize else 0, ctypes.byref(t)))
-        _last = t
-        g = int(cnt.value)
-        return g, t.total_ms * 1e-3, _trim(ok, g), ov if inverse else _trim(ov, g)
-    if _is_torch_tensor(keys):
-        keys, values = (x.numpy() if x is not None else None for x in (keys, values))
-    k = _as_u64_host(keys, "keys")
-    v = _as_u64_host(values, "values") if values is not None else None
-    if v is not None and v.size != k.size:
-        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, int(materialize), k.ctypes.data, v.ctypes.data if v is not None else None, k.size, None, 0,
-                         ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok) if materialize else None,
-                         ctypes.byref(ov) if materialize and want_vals else None))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        gk = take(ok, g) if materialize else None
-        gv = take(ov, k.size if inverse else g).view(np.int64) if materialize and want_vals else None
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    return g, float(sec.value), gk, gv
+    k, v, n = _group_columns(keys, values)
+    vals = ("rows" if inverse else "groups") if materialize and want_vals else None
+    return _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | flags, k, v, None, n, vals, want_keys=materialize)
 
 
 def _align_by_key(keys_a, keys_b, vals_b):
@@ -1303,51 +1252,13 @@ def factorize(keys):
 def _group_rows(keys):
     """(g, seconds, group_keys, offsets, row_index) of ALGO_GROUP_BY | ALGO_GROUP_ROWS, where the keys live: the two planes of the
     values output come back as row_index (the first len(keys) words of plane 0) and offsets (the g starts of plane 1 and len(keys))"""
-    global _last
-    keys = _from_dlpack_if_device(keys)
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_GROUP_ROWS
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
-    if _is_torch_tensor(keys) and keys.is_cuda:
-        import torch
-        k = _dev_tensor(keys, "keys")
-        n = k.numel()
-        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(n, dtype=torch.int64, device=k.device)
-        ov = torch.empty(2 * n, dtype=torch.int64, device=k.device)           # two planes of n words: the rows, the starts
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            check(L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), None, n, None, 0, stream, 64,
-                                   ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(), n, ctypes.byref(t)))
-        _last = t
-        g = int(cnt.value)
-        offsets = torch.empty(g + 1, dtype=torch.int64, device=k.device)
-        offsets[:g] = ov[n:n + g]
-        offsets[g] = n
-        return g, t.total_ms * 1e-3, _trim(ok, g), offsets, ov[:n]
-    if _is_torch_tensor(keys):
-        keys = keys.numpy()
-    k = _as_u64_host(keys, "keys")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, None, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        gk = take(ok, g)
-        words = take(ov, k.size + g).view(np.int64)                           # the nb row indices, then the g starts
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    offsets = np.empty(g + 1, np.int64)
-    offsets[:g] = words[k.size:]
-    offsets[g] = k.size
-    return g, float(sec.value), gk, offsets, words[:k.size].copy()
+    k, _, n = _group_columns(keys)
+    g, sec, gk, words = _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_GROUP_ROWS, k, None, None, n, "csr")
+    on_device = _is_torch_tensor(words)
+    offsets = words.new_empty(g + 1) if on_device else np.empty(g + 1, np.int64)
+    offsets[:g] = words[n:n + g]
+    offsets[g] = n
+    return g, sec, gk, offsets, (words[:n] if on_device else words[:n].copy())       # (NumPy: a copy, not a view of the n + g words)
 
 
 def group_rows(keys):
@@ -1530,26 +1441,9 @@ def group_by_sum(keys, values, float64: bool = False):
 def _group_by_minmax(name: str, flag: int, keys, values, signed, float64: bool = False):
     if values is None:
         raise ValueError(f"{name}: values is required")
-    if float64:
-        g, sec, gk, vals = _group_by(keys, _float_words(name, "values", values, signed), flag | ALGO_AGG_FLOAT)
-        return g, sec, gk, _as_float64(vals)
-    if signed is not None and not isinstance(signed, (bool, np.bool_)):
-        raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
-    values = _from_dlpack_if_device(values)
-    if _is_torch_tensor(values):
-        if values.dtype.is_floating_point:
-            raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-        unsigned_in = str(values.dtype) == "torch.uint64"
-    else:
-        values = np.asarray(values)
-        if values.dtype.kind not in "iub":
-            raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-        unsigned_in = values.dtype == np.uint64
-    signed = (not unsigned_in) if signed is None else bool(signed)
-    g, sec, gk, vals = _group_by(keys, values, flag | (ALGO_AGG_SIGNED if signed else 0))
-    if unsigned_in and not signed and isinstance(vals, np.ndarray):
-        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
-    return g, sec, gk, vals
+    values, signed, unsigned_in = _word_column(name, "values", values, signed, float64)
+    g, sec, gk, vals = _group_by(keys, values, flag | _agg_flags(signed, float64))
+    return g, sec, gk, _agg_values(vals, signed, unsigned_in, float64)
 
 
 def group_by_min(keys, values, signed=None, float64: bool = False):
@@ -1573,56 +1467,9 @@ def _group_by_all(keys, values, flags: int, max_groups: Optional[int] = None):
     int64 words where the inputs live - row counts, sums, minima, maxima - each row aligned with group_keys.  flags: a base value
     (ALGO_SCALAR, ALGO_RADIX), ALGO_AGG_SIGNED or ALGO_AGG_FLOAT.  max_groups: the rows the device buffers hold (None: len(keys));
     a result beyond it is a ValueError that names g."""
-    global _last
-    keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | flags
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
-    if _is_torch_tensor(keys) and keys.is_cuda:
-        import torch
-        k, v = _dev_tensor(keys, "keys"), _dev_tensor(values, "values")
-        if v.numel() != k.numel():
-            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
-        n = k.numel()
-        cap = max(1, n if max_groups is None else min(n, max_groups))
-        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-        ov = torch.empty((4, cap), dtype=torch.int64, device=k.device)
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            rc = L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), v.data_ptr(), n, None, 0, stream, 64, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(),
-                                  cap, ctypes.byref(t))
-            g = int(cnt.value)
-            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
-                raise ValueError(f"group_by_agg: the relation has g = {g} distinct keys, max_groups = {max_groups}")
-            check(rc)
-        _last = t
-        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
-    if _is_torch_tensor(keys):
-        keys = keys.numpy()
-    if _is_torch_tensor(values):
-        values = values.numpy()
-    k, v = _as_u64_host(keys, "keys"), _as_u64_host(values, "values")
-    if v.size != k.size:
-        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        gk, planes = take(ok, g), take(ov, 4 * g).view(np.int64).reshape(4, g)
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
-        raise ValueError(f"group_by_agg: the relation has g = {g} distinct keys, max_groups = {max_groups}")
-    return g, float(sec.value), gk, planes
+    k, v, n = _group_columns(keys, values)
+    return _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | flags, k, v, None, n, 4, max_groups=max_groups,
+                          overflow=f"group_by_agg: the relation has g = {{g}} distinct keys, max_groups = {max_groups}")
 
 
 _AGG_NAMES = ("count", "sum", "min", "max", "mean")
@@ -1691,28 +1538,9 @@ def group_by_agg(keys, values, aggs=("count", "sum", "min", "max"), signed=None,
     max_groups = _check_max_groups("group_by_agg", max_groups)
     if values is None:
         raise ValueError("group_by_agg: values is required (group_by_count takes none)")
-    unsigned_out = False
-    if float64:
-        flags = ALGO_AGG_FLOAT
-        values = _float_words("group_by_agg", "values", values, signed)
-    else:
-        if signed is not None and not isinstance(signed, (bool, np.bool_)):
-            raise TypeError(f"group_by_agg: signed must be None, True or False, got {type(signed).__name__}")
-        values = _from_dlpack_if_device(values)
-        if _is_torch_tensor(values):
-            if values.dtype.is_floating_point:
-                raise TypeError(f"group_by_agg: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = str(values.dtype) == "torch.uint64"
-        else:
-            values = np.asarray(values)
-            if values.dtype.kind not in "iub":
-                raise TypeError(f"group_by_agg: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = values.dtype == np.uint64
-        signed = (not unsigned_in) if signed is None else bool(signed)
-        flags = ALGO_AGG_SIGNED if signed else 0
-        unsigned_out = unsigned_in and not signed
-    g, sec, gk, planes = _group_by_all(keys, values, flags, max_groups)
-    return (g, sec, gk, *_agg_columns(planes, aggs, float64, unsigned_out))
+    values, signed, unsigned_in = _word_column("group_by_agg", "values", values, signed, float64)
+    g, sec, gk, planes = _group_by_all(keys, values, _agg_flags(signed, float64), max_groups)
+    return (g, sec, gk, *_agg_columns(planes, aggs, float64, unsigned_in and not signed))
 
 
 # ---- extension: GROUP BY a, b with four aggregates in one call (csrc/fj_groupby_pair_agg.hip) ---------------------------------------------
@@ -1720,55 +1548,18 @@ def _group_by_pair_all(a, b, values, flags: int, max_groups: Optional[int] = Non
     """(g, seconds, group_a, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL | flags, over word columns
     as `_key_columns` returns them.  planes is a (5, g) array of int64 words where the inputs live - column B of every group, then row
     counts, sums, minima, maxima - each row aligned with group_a.  flags and max_groups as for `_group_by_all`."""
-    global _last
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_KEY_PAIR | ALGO_AGG_ALL | flags
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
     n = a.shape[0]
     if _is_torch_tensor(a):
-        import torch
         v = _dev_tensor(_from_dlpack_if_device(values), "values")
-        if v.numel() != n:
-            raise ValueError(f"values has {v.numel()} elements, the key columns have {n}")
-        if v.device != a.device:
-            raise ValueError(f"group_by_agg_columns: values lives on {v.device}, the key columns on {a.device}")
-        cap = max(1, n if max_groups is None else min(n, max_groups))
-        dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(cap, dtype=torch.int64, device=a.device)
-        ov = torch.empty((5, cap), dtype=torch.int64, device=a.device)
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            rc = L.fj_join_device(ctx, algo, 0, 1, a.data_ptr(), b.data_ptr(), n, v.data_ptr(), n, stream, 64, ctypes.byref(cnt), ok.data_ptr(),
-                                  ov.data_ptr(), cap, ctypes.byref(t))
-            g = int(cnt.value)
-            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
-                raise ValueError(f"group_by_agg_columns: the relation has g = {g} distinct key tuples, max_groups = {max_groups}")
-            check(rc)
-        _last = t
-        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
-    if _is_torch_tensor(values):
-        values = values.numpy()
-    v = _as_u64_host(values, "values")
-    if v.size != n:
-        raise ValueError(f"values has {v.size} elements, the key columns have {n}")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, a.ctypes.data, b.ctypes.data, n, v.ctypes.data, n, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        ga, planes = take(ok, g), take(ov, 5 * g).view(np.int64).reshape(5, g)
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
-        raise ValueError(f"group_by_agg_columns: the relation has g = {g} distinct key tuples, max_groups = {max_groups}")
-    return g, float(sec.value), ga, planes
+    else:
+        v = _as_u64_host(values.numpy() if _is_torch_tensor(values) else values, "values")
+    if v.shape[0] != n:
+        raise ValueError(f"values has {v.shape[0]} elements, the key columns have {n}")
+    if _is_torch_tensor(a) and v.device != a.device:
+        raise ValueError(f"group_by_agg_columns: values lives on {v.device}, the key columns on {a.device}")
+    # (the value column and its rows go where a join takes its probe side)
+    return _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_KEY_PAIR | ALGO_AGG_ALL | flags, a, b, v, n, 5, max_groups=max_groups,
+                          overflow=f"group_by_agg_columns: the relation has g = {{g}} distinct key tuples, max_groups = {max_groups}")
 
 
 def group_by_agg_columns(columns, values, aggs=("count", "sum", "min", "max"), signed=None, float64: bool = False, max_groups: Optional[int] = None):
@@ -1798,26 +1589,8 @@ def group_by_agg_columns(columns, values, aggs=("count", "sum", "min", "max"), s
     if len(cols) == 1:
         g, sec, gk, *out = group_by_agg(cols[0], values, aggs, signed, float64, max_groups)
         return (g, sec, (gk,), *out)
-    unsigned_out = False
-    if float64:
-        flags = ALGO_AGG_FLOAT
-        values = _float_words(name, "values", values, signed)
-    else:
-        if signed is not None and not isinstance(signed, (bool, np.bool_)):
-            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
-        values = _from_dlpack_if_device(values)
-        if _is_torch_tensor(values):
-            if values.dtype.is_floating_point:
-                raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = str(values.dtype) == "torch.uint64"
-        else:
-            values = np.asarray(values)
-            if values.dtype.kind not in "iub":
-                raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = values.dtype == np.uint64
-        signed = (not unsigned_in) if signed is None else bool(signed)
-        flags = ALGO_AGG_SIGNED if signed else 0
-        unsigned_out = unsigned_in and not signed
+    values, signed, unsigned_in = _word_column(name, "values", values, signed, float64)
+    flags, unsigned_out = _agg_flags(signed, float64), unsigned_in and not signed
     if _is_torch_tensor(values) and not values.is_cuda:
         values = values.numpy()                              # (as _key_columns takes host tensors)
     if _is_torch_tensor(cols[0]) != _is_torch_tensor(values):
@@ -1845,85 +1618,18 @@ def _group_by_arg(keys, values, flags: int):
     """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ARG | flags.  planes is a (2, g) array of int64
     words where the inputs live - the row indices and the extremes - each row aligned with group_keys.  flags: ALGO_AGG_MIN or
     ALGO_AGG_MAX, a base value (ALGO_SCALAR, ALGO_RADIX), ALGO_AGG_SIGNED or ALGO_AGG_FLOAT."""
-    global _last
-    keys, values = _from_dlpack_if_device(keys), _from_dlpack_if_device(values)
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ARG | flags
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
-    if _is_torch_tensor(keys) and keys.is_cuda:
-        import torch
-        k, v = _dev_tensor(keys, "keys"), _dev_tensor(values, "values")
-        if v.numel() != k.numel():
-            raise ValueError(f"values has {v.numel()} elements, keys has {k.numel()}")
-        n = k.numel()
-        cap = max(1, n)
-        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-        ov = torch.empty((2, cap), dtype=torch.int64, device=k.device)
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            check(L.fj_join_device(ctx, algo, 0, 1, k.data_ptr(), v.data_ptr(), n, None, 0, stream, 64, ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(),
-                                   cap, ctypes.byref(t)))
-        _last = t
-        g = int(cnt.value)
-        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
-    if _is_torch_tensor(keys):
-        keys = keys.numpy()
-    if _is_torch_tensor(values):
-        values = values.numpy()
-    k, v = _as_u64_host(keys, "keys"), _as_u64_host(values, "values")
-    if v.size != k.size:
-        raise ValueError(f"values has {v.size} elements, keys has {k.size}")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, k.size, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        gk, planes = take(ok, g), take(ov, 2 * g).view(np.int64).reshape(2, g)
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    return g, float(sec.value), gk, planes
+    k, v, n = _group_columns(keys, values)
+    return _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ARG | flags, k, v, None, n, 2)
 
 
 def _group_by_argext(name: str, flag: int, keys, values, signed, float64: bool, return_values: bool):
     if values is None:
         raise ValueError(f"{name}: values is required")
-    unsigned_out = False
-    if float64:
-        flags = flag | ALGO_AGG_FLOAT
-        values = _float_words(name, "values", values, signed)
-    else:
-        if signed is not None and not isinstance(signed, (bool, np.bool_)):
-            raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
-        values = _from_dlpack_if_device(values)
-        if _is_torch_tensor(values):
-            if values.dtype.is_floating_point:
-                raise TypeError(f"{name}: values must be 64-bit integers, got {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = str(values.dtype) == "torch.uint64"
-        else:
-            values = np.asarray(values)
-            if values.dtype.kind not in "iub":
-                raise TypeError(f"{name}: values must be integers, got dtype {values.dtype} (the words are compared as integers{_FLOAT64_HINT})")
-            unsigned_in = values.dtype == np.uint64
-        signed = (not unsigned_in) if signed is None else bool(signed)
-        flags = flag | (ALGO_AGG_SIGNED if signed else 0)
-        unsigned_out = unsigned_in and not signed
-    g, sec, gk, planes = _group_by_arg(keys, values, flags)
+    values, signed, unsigned_in = _word_column(name, "values", values, signed, float64)
+    g, sec, gk, planes = _group_by_arg(keys, values, flag | _agg_flags(signed, float64))
     if not return_values:
         return g, sec, gk, planes[0]
-    vals = planes[1]
-    if float64:
-        vals = _as_float64(vals)
-    elif unsigned_out and isinstance(vals, np.ndarray):
-        vals = vals.view(np.uint64)                          # the column's own dtype; otherwise int64 storage of the words
-    return g, sec, gk, planes[0], vals
+    return g, sec, gk, planes[0], _agg_values(planes[1], signed, unsigned_in, float64)
 
 
 def group_by_argmin(keys, values, signed=None, float64: bool = False, return_values: bool = False):
@@ -1953,51 +1659,17 @@ def _group_by_merge(k, planes, flags: int, max_groups: Optional[int] = None):
     """(g, seconds, group_keys, planes): ONE library call, FJ_ALGO_GROUP_BY | FJ_ALGO_AGG_ALL | FJ_ALGO_AGG_MERGE | flags.  k: the n keys
     of the partial rows, planes: their (4, n) words - counts, sums, minima, maxima - both NumPy (uint64) or both contiguous torch.int64
     on one device.  Returns what _group_by_all returns.  flags: a base value, ALGO_AGG_SIGNED or ALGO_AGG_FLOAT."""
-    global _last
-    algo = ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | ALGO_AGG_MERGE | flags
-    L = _lib.load()
-    cnt = ctypes.c_uint64(0)
     if _is_torch_tensor(k):
-        import torch
         n = k.numel()
         if tuple(planes.shape) != (4, n) or not planes.is_contiguous() or planes.device != k.device:
             raise ValueError(f"_group_by_merge: planes must be a contiguous (4, {n}) tensor on the keys' device")
-        cap = max(1, n if max_groups is None else min(n, max_groups))
-        dev = k.device.index if k.device.index is not None else torch.cuda.current_device()
-        ctx = context(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ok = torch.empty(cap, dtype=torch.int64, device=k.device)
-        ov = torch.empty((4, cap), dtype=torch.int64, device=k.device)
-        t = FjTimings()
-        with _ctx_locks.setdefault(dev, threading.RLock()):
-            rc = L.fj_join_device(ctx, algo, 0, 1, k.data_ptr() if n else None, planes.data_ptr() if n else None, n, None, 0, stream, 64,
-                                  ctypes.byref(cnt), ok.data_ptr(), ov.data_ptr(), cap, ctypes.byref(t))
-            g = int(cnt.value)
-            if rc and g > cap:                               # (the device work is done and the context usable: the buffers were too small)
-                raise ValueError(f"group_by_merge: the partial rows hold g = {g} distinct keys, max_groups = {max_groups}")
-            check(rc)
-        _last = t
-        return g, t.total_ms * 1e-3, _trim(ok, g), (ov[:, :g].clone() if g * 4 < cap * 3 else ov[:, :g])
-    n = k.size
-    if planes.shape != (4, n):
-        raise ValueError(f"_group_by_merge: planes must be a (4, {n}) array")
-    k, v = _as_u64_host(k, "keys"), _as_u64_host(planes, "planes")
-    sec = ctypes.c_double(0.0)
-    ok, ov = ctypes.c_void_p(), ctypes.c_void_p()
-    check(L.fj_join_host(algo, 0, 1, k.ctypes.data, v.ctypes.data, n, None, 0, ctypes.byref(cnt), ctypes.byref(sec), ctypes.byref(ok), ctypes.byref(ov)))
-    t = FjTimings()
-    L.fj_last_timings(ctypes.byref(t))
-    _last = t
-    g = int(cnt.value)
-    try:
-        take = lambda p, rows: (np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(rows,)).copy() if rows else np.empty(0, np.uint64))
-        gk, out = take(ok, g), take(ov, 4 * g).view(np.int64).reshape(4, g)
-    finally:
-        L.fj_free_host(ok)
-        L.fj_free_host(ov)
-    if max_groups is not None and g > max_groups:            # (host arrays are sized by the library: the bound is checked all the same)
-        raise ValueError(f"group_by_merge: the partial rows hold g = {g} distinct keys, max_groups = {max_groups}")
-    return g, float(sec.value), gk, out
+    else:
+        n = k.size
+        if planes.shape != (4, n):
+            raise ValueError(f"_group_by_merge: planes must be a (4, {n}) array")
+        k, planes = _as_u64_host(k, "keys"), _as_u64_host(planes, "planes")
+    return _group_by_call(ALGO_ADAPTIVE | ALGO_GROUP_BY | ALGO_AGG_ALL | ALGO_AGG_MERGE | flags, k, planes, None, n, 4, max_groups=max_groups,
+                          overflow=f"group_by_merge: the partial rows hold g = {{g}} distinct keys, max_groups = {max_groups}")
 
 
 def _is_array(x: Any) -> bool:
@@ -2014,8 +1686,7 @@ def _parts(x: Any) -> list:
 def _container(x: Any):
     """where an array lives: "numpy", or ("device", index).  A torch tensor in host memory counts as NumPy, as everywhere"""
     if _is_torch_tensor(x) and x.is_cuda:
-        import torch
-        return ("device", x.device.index if x.device.index is not None else torch.cuda.current_device())
+        return ("device", _device_index(x))
     return "numpy"
 
 
@@ -2030,23 +1701,46 @@ def _same_container(name: str, arrays, want=None):
     return want or "numpy"
 
 
-def _word_column(name: str, what: str, col: Any, signed: Any, float64: bool):
-    """(words, signed, unsigned_in): a sum / min / max column as 8-byte words in its container, under the rules of group_by_min -
-    signed=None takes the sign from the container - and of float64=True"""
-    if float64:
-        return _float_words(name, what, col, signed), False, False
+def _check_signed(name: str, signed: Any) -> None:
     if signed is not None and not isinstance(signed, (bool, np.bool_)):
         raise TypeError(f"{name}: signed must be None, True or False, got {type(signed).__name__}")
+
+
+def _word_column(name: str, what: str, col: Any, signed: Any, float64: bool, integers_only: bool = True):
+    """(words, signed, unsigned_in): a sum / min / max column as 8-byte words in its container, under the rules of group_by_min -
+    signed=None takes the sign from the container: a NumPy uint64 column (a torch.uint64 tensor) compares unsigned, everything else
+    signed - and of float64=True.  A device array of another library is a torch tensor from here on.  integers_only=False (the
+    group_join_* and Index.group_* forms): a column that is not of integers is not refused here - a NumPy float column is value-cast
+    to words, as ever, and a torch float tensor is refused where the device tensors are checked"""
+    if float64:
+        return _float_words(name, what, col, signed), False, False
+    _check_signed(name, signed)
+    col = _from_dlpack_if_device(col)
     if _is_torch_tensor(col):
-        if col.dtype.is_floating_point:
+        if integers_only and col.dtype.is_floating_point:
             raise TypeError(f"{name}: {what} must be 64-bit integers, got {col.dtype} (the words are compared as integers{_FLOAT64_HINT})")
         unsigned_in = str(col.dtype) == "torch.uint64"
     else:
         col = np.asarray(col)
-        if col.dtype.kind not in "iub":
+        if integers_only and col.dtype.kind not in "iub":
             raise TypeError(f"{name}: {what} must be integers, got dtype {col.dtype} (the words are compared as integers{_FLOAT64_HINT})")
         unsigned_in = col.dtype == np.uint64
     return col, ((not unsigned_in) if signed is None else bool(signed)), unsigned_in
+
+
+def _agg_flags(signed: bool, float64: bool) -> int:
+    """how the words of a value column compare and add: as float64, as two's-complement int64, or as uint64"""
+    return ALGO_AGG_FLOAT if float64 else (ALGO_AGG_SIGNED if signed else 0)
+
+
+def _agg_values(words, signed: bool, unsigned_in: bool, float64: bool):
+    """a column of minima / maxima with the dtype the single forms return: float64; the column's own dtype for a NumPy uint64 column
+    compared unsigned; otherwise the int64 storage of the words"""
+    if float64:
+        return _as_float64(words)
+    if unsigned_in and not signed and isinstance(words, np.ndarray):
+        return words.view(np.uint64)
+    return words
 
 
 def _count_column(name: str, col: Any):
@@ -2129,11 +1823,10 @@ def group_by_merge(keys, counts, sums, mins, maxs, signed=None, float64: bool = 
     max_groups = _check_max_groups("group_by_merge", max_groups)
     parts, container, signed, unsigned_out = _partial_words("group_by_merge", keys, counts, sums, mins, maxs, signed, float64)
     k, planes = _pack_partials("group_by_merge", parts, container)
-    flags = ALGO_AGG_FLOAT if float64 else (ALGO_AGG_SIGNED if signed else 0)
     if k.shape[0] == 0:
         g, sec, gk, out = 0, 0.0, k, (planes.view(np.int64) if container == "numpy" else planes)
     else:
-        g, sec, gk, out = _group_by_merge(k, planes, flags, max_groups)
+        g, sec, gk, out = _group_by_merge(k, planes, _agg_flags(signed, float64), max_groups)
     return (g, sec, gk, *_agg_columns(out, ("count", "sum", "min", "max"), float64, unsigned_out))
 
 
@@ -2158,8 +1851,7 @@ class GroupByAccumulator:
     def __init__(self, signed=None, float64: bool = False, max_groups: Optional[int] = None, compact_at: int = 65536):
         if float64 and signed is not None:
             raise TypeError(f"GroupByAccumulator: signed must be None with float64=True (a float64 carries its own sign), got {signed!r}")
-        if signed is not None and not isinstance(signed, (bool, np.bool_)):
-            raise TypeError(f"GroupByAccumulator: signed must be None, True or False, got {type(signed).__name__}")
+        _check_signed("GroupByAccumulator", signed)
         if isinstance(compact_at, (bool, np.bool_)) or not isinstance(compact_at, (int, np.integer)) or compact_at < 1:
             raise ValueError(f"GroupByAccumulator: compact_at must be an integer >= 1, got {compact_at!r}")
         self._signed_arg, self._float64 = signed, bool(float64)
@@ -2231,8 +1923,7 @@ class GroupByAccumulator:
         k, planes = _pack_partials("GroupByAccumulator", self._partials(), self._container)
         sec = 0.0
         if k.shape[0]:
-            flags = ALGO_AGG_FLOAT if self._float64 else (ALGO_AGG_SIGNED if self._signed else 0)
-            g, sec, k, planes = _group_by_merge(k, planes, flags, self._max_groups)
+            g, sec, k, planes = _group_by_merge(k, planes, _agg_flags(self._signed, self._float64), self._max_groups)
             self._merges += 1
         self._state = (k, planes)
         self._pending, self._pending_rows = [], 0
@@ -2388,7 +2079,7 @@ EXTENSIONS = ["inner_join", "inner_join_count", "left_join", "anti_join", "anti_
 # multi-column keys: compositions over the entries above (`_group_by`, `factorize`), whose caller-context rows
 # (tests/test_caller_context_cpu.py walks EXTENSIONS) cover the path they take; their own suite is tests/test_factorize_columns.py.
 # group_by_agg_columns is NOT such a composition: it has a library entry of its own (`_group_by_pair_all`: ALGO_KEY_PAIR | ALGO_AGG_ALL,
-# with its own context lookup, per-device lock and stream), as group_rows below has.  Like ROW_EXTENSIONS it is exempt from the
+# through `_group_by_call`'s context lookup, per-device lock and stream), as group_rows below has.  Like ROW_EXTENSIONS it is exempt from the
 # caller-context walk, which reads EXTENSIONS only; what covers its caller context is its own suite, tests/test_group_by_agg_columns.py
 # (device tensors in place, a side stream, a strided view, the inputs' device)
 KEY_EXTENSIONS = ["factorize_columns", "encode_keys", "group_by_agg_columns"]
