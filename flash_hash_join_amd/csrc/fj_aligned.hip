@@ -212,68 +212,35 @@ int join_probe_order(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, si
     *out_count = 0;
     if (np == 0) return 0;
     if (nb == 0) {                                           // no probe row has a partner
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (vals) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
-        if (d_mask) HIPCHK(hipMemsetAsync(d_mask, 0, np, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, [&]() -> int {
+                if (vals) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
+                if (d_mask) HIPCHK(hipMemsetAsync(d_mask, 0, np, s));
+                return 0;
+            })) return 1;
+        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ms;
         return 0;
     }
     if (!use_radix) return join_probe_order_global(c, bk, bv, nb, pk, np, s, t, out_count, d_mask, d_ov, rid);
 
-    const Plan plan = make_plan(nb, top_bits, false);
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;                  // (total = the hits, expected = the misses)
+    // (total = the hits, expected = the misses; the probe rows' positions travel through the passes)
+    PairAttempt a;
+    if (pair_open(c, make_plan(nb, top_bits, false), {!vals ? REL_KEYS_ONLY : rid ? REL_POSITIONS : REL_VALUES, REL_POSITIONS}, bk, bv, nb, pk, nullptr, np, top_bits, s, &a)) return 1;
     FjLdsJoinArgs ja{};
-    PassIter bit, pit;
-    pass_init(bit, 0, vals, nb, plan, top_bits);
-    bit.vals_pos = rid;
-    int evc = 0;
-    if (run_passes(c, bit, bk, (vals && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    pass_init(pit, 1, true, np, plan, top_bits);             // the probe rows' positions travel through the passes
-    pit.vals_pos = true;
-    pit.want_items = true;
-    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
-    void* p;
-    if (ja.probe.list) {
-        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
-    } else {                                                 // zero-pass plan: slices of the flat probe side
-        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
-    }
+    ja.build = a.build; ja.probe = a.probe; ja.nparts = a.nparts;
+    pair_items(a, np, &ja.items, &ja.nitems_dev, &ja.items_cap, &ja.nsplit);
     ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
     ja.out_capacity = np; ja.out_vals = d_ov;
     ja.row_ids = rid ? 1u : 0u;
     HIPCHK(fj_launch_probe_order_join(ja, rid, np, &c->d_sc->expected, d_mask, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-    end_plan(c);
+    if (pair_close(c, a, s, t)) return 1;
     if (vals && !rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and every row stored again
-        if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
-        u64* rowidx = (u64*)p;
-        HIPCHK(fj_launch_iota(rowidx, nb, s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both counters
-        HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
-        PassIter bit2;
-        pass_init(bit2, 0, true, nb, plan, top_bits);
-        begin_plan(c);
-        if (run_passes(c, bit2, bk, rowidx, s, &ja.build, nullptr)) return 1;
-        end_plan(c);
-        ja.orig_vals = bv;
+        if (pair_rerun_build_with_row_ids(c, &a, bk, nb, top_bits, nullptr, s)) return 1;
+        ja.build = a.build; ja.orig_vals = bv;
         HIPCHK(fj_launch_probe_order_join(ja, true, np, &c->d_sc->expected, d_mask, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
+        if (pair_close(c, a, s, t)) return 1;
     }
-    plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return join_probe_order_global(c, bk, bv, nb, pk, np, s, g, out_count, d_mask, d_ov, rid); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a probe row's position lies beyond the probe side");

@@ -230,8 +230,8 @@ __global__ __launch_bounds__(256) void fj_fill64_kernel(u64* __restrict__ out, u
 }  // namespace
 
 u64 fj_group_identity(int agg) {
-    return agg == FJ_GJ_MIN_U ? ~0ull : agg == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : agg == FJ_GJ_MAX_S ? 0x8000000000000000ull :
-           agg == FJ_GJ_MIN_F ? 0x7FF0000000000000ull : agg == FJ_GJ_MAX_F ? 0xFFF0000000000000ull : 0ull;      // (+inf, -inf; the float sum: +0.0)
+    if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST) return 0;
+    return fjh::for_agg(agg, [](auto A) { return gj_identity<FJ_V(A)>(); });
 }
 
 hipError_t fj_launch_group_fill(u64* out, u64 n, int agg, hipStream_t s) {
@@ -250,12 +250,7 @@ hipError_t fj_launch_group_join(const FjLdsJoinArgs& a, int agg, u64* out, u64 n
     if (!a.err || (!out && (vals || !a.total))) return hipErrorInvalidValue;
     if (vals && !a.probe.vals) return hipErrorInvalidValue;                       // the probe side carries the values
     const u32 lds = (u32)sizeof(GjHdr) + GJ_TS * 16u;
-    void (*kern)(FjLdsJoinArgs, u64*, u64) =
-        agg == FJ_GJ_COUNT ? fj_group_join_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_group_join_kernel<FJ_GJ_SUM> :
-        agg == FJ_GJ_MIN_U ? fj_group_join_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_group_join_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_group_join_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_group_join_kernel<FJ_GJ_MAX_S> :
-        agg == FJ_GJ_SUM_F ? fj_group_join_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_group_join_kernel<FJ_GJ_MIN_F> :
-        fj_group_join_kernel<FJ_GJ_MAX_F>;
+    void (*kern)(FjLdsJoinArgs, u64*, u64) = fjh::for_agg(agg, [](auto A) { return fj_group_join_kernel<FJ_V(A)>; });
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(GJ_NT), lds, s, a, out, nb);
@@ -267,11 +262,7 @@ hipError_t fj_launch_gt_group(const FjGtArgs& a, int agg, const u64* pv, unsigne
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_sum && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     if (a.np) {
         void (*probe)(FjGtArgs, const u64*, unsigned long long*, unsigned long long*) =
-            agg == FJ_GJ_MIN_U ? fj_gt_group_probe_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_probe_kernel<FJ_GJ_MIN_S> :
-            agg == FJ_GJ_MAX_U ? fj_gt_group_probe_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_probe_kernel<FJ_GJ_MAX_S> :
-            agg == FJ_GJ_SUM_F ? fj_gt_group_probe_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_probe_kernel<FJ_GJ_MIN_F> :
-            agg == FJ_GJ_MAX_F ? fj_gt_group_probe_kernel<FJ_GJ_MAX_F> :
-            fj_gt_group_probe_kernel<FJ_GJ_SUM>;                                  // (the count form: sum == nullptr)
+            fjh::for_value_agg(agg, [](auto A) { return fj_gt_group_probe_kernel<FJ_V(A)>; });     // (the count form: sum == nullptr)
         hipLaunchKernelGGL(probe, dim3(fjh::gt_grid(a.np)), dim3(1024), 0, s, a, pv, cnt, out_sum ? sum : nullptr);
     }
     if (a.nb) hipLaunchKernelGGL(fj_gt_group_flush_kernel, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, cnt, sum, out_cnt, out_sum);
@@ -314,38 +305,23 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
     *out_count = 0;
     if (nb == 0) return 0;
     if (np == 0) {                                           // no build row has a partner
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
-        if (d_sum) HIPCHK(fj_launch_group_fill(d_sum, nb, agg, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, [&]() -> int {
+                if (d_cnt) HIPCHK(hipMemsetAsync(d_cnt, 0, nb * 8, s));
+                if (d_sum) HIPCHK(fj_launch_group_fill(d_sum, nb, agg, s));
+                return 0;
+            })) return 1;
+        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ms;
         return 0;
     }
     if (!use_radix) return join_group_global(c, bk, nb, pk, pv, np, s, t, out_count, d_cnt, d_sum, agg);
 
-    const Plan plan = make_plan(nb, top_bits, false);
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    // the build rows' positions travel through the passes; the count form alone: the probe side's keys-only pass
+    PairAttempt a;
+    if (pair_open(c, make_plan(nb, top_bits, false), {REL_POSITIONS, d_sum ? REL_VALUES : REL_KEYS_ONLY}, bk, nullptr, nb, pk, pv, np, top_bits, s, &a)) return 1;
     FjLdsJoinArgs ja{};
-    PassIter bit, pit;
-    pass_init(bit, 0, true, nb, plan, top_bits);             // the build rows' positions travel through the passes
-    bit.vals_pos = true;
-    int evc = 0;
-    if (run_passes(c, bit, bk, nullptr, s, &ja.build, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    pass_init(pit, 1, d_sum != nullptr, np, plan, top_bits); // the count form alone: the keys-only pass
-    pit.want_items = true;
-    if (run_passes(c, pit, pk, d_sum ? pv : nullptr, s, &ja.probe, &evc)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
-    if (ja.probe.list) {
-        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
-    } else {                                                 // zero-pass plan: slices of the flat probe side
-        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
-    }
+    ja.build = a.build; ja.probe = a.probe; ja.nparts = a.nparts;
+    pair_items(a, np, &ja.items, &ja.nitems_dev, &ja.items_cap, &ja.nsplit);
     ja.err = &c->d_sc->err;
     if (d_cnt) {
         ja.total = &c->d_sc->total;
@@ -357,19 +333,14 @@ int join_group(fj_ctx* c, bool use_radix, const u64* bk, size_t nb, const u64* p
         HIPCHK(fj_launch_group_fill(d_sum, nb, agg, s));
         HIPCHK(fj_launch_group_join(ja, agg, d_sum, nb, s));
     }
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-    end_plan(c);
+    if (pair_close(c, a, s, t)) return 1;
     if (!d_cnt && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // sums (minima, maxima) alone over duplicated build keys: the hits are not P.  The count form once, without an output, for P
         HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, sizeof(unsigned long long), s));
         ja.total = &c->d_sc->total;
         HIPCHK(fj_launch_group_join(ja, FJ_GJ_COUNT, nullptr, nb, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        if (read_scalars(c, s)) return 1;
+        if (pair_close(c, a, s, t)) return 1;
     }
-    plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return join_group_global(c, bk, nb, pk, pv, np, s, g, out_count, d_cnt, d_sum, agg); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a build row's position lies beyond the build side");

@@ -1,6 +1,7 @@
 // fj_group_dev.h -- device-side pieces shared by the two users of the 8192-slot LDS table with one 8-byte accumulator per slot:
 // the build-order aggregate joins (csrc/fj_group.hip) and the group-by on one relation (csrc/fj_groupby.hip).  The table itself -
-// home slot, probing, insert and find - is csrc/fj_lds_table_dev.h's; here are the aggregates.
+// home slot, probing, what an insert and a find may assume - is STATED in csrc/fj_lds_table_dev.h; the insert and find loops
+// are written out in each kernel (that header says why).  Here are the aggregates.
 #pragma once
 #include "fj_lds_table_dev.h"
 
@@ -14,7 +15,7 @@ __device__ __forceinline__ u64 gj_wave_sum64(u64 v) {
 }
 
 // the aggregate's identity: what an accumulator holds before its first hit and a build row without a partner receives
-template <int AGG> __device__ __forceinline__ constexpr u64 gj_identity() {
+template <int AGG> __host__ __device__ __forceinline__ constexpr u64 gj_identity() {
     return AGG == FJ_GJ_MIN_U ? ~0ull : AGG == FJ_GJ_MIN_S ? 0x7FFFFFFFFFFFFFFFull : AGG == FJ_GJ_MAX_S ? 0x8000000000000000ull :
            AGG == FJ_GJ_MIN_F ? 0x7FF0000000000000ull : AGG == FJ_GJ_MAX_F ? 0xFFF0000000000000ull : 0ull;      // (+inf, -inf; the float sum: +0.0)
 }

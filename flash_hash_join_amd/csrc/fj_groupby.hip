@@ -6,7 +6,8 @@
 // The relation goes through the build side's partition passes (keys only for the distinct and count forms, with the value column or
 // the rows' positions otherwise).  One work item is one WHOLE final partition - two slices of a partition would each emit the same
 // key - and the kernel builds its table from the stream it aggregates: every row inserts or finds its key in the 8192-slot LDS table
-// (CAS, linear probing) and combines into the slot's 8-byte accumulator with one LDS atomic (gj_combine, csrc/fj_group_dev.h).  Then
+// (CAS, linear probing: the table csrc/fj_lds_table_dev.h states, its insert-or-find loop written out in the kernel) and combines
+// into the slot's 8-byte accumulator with one LDS atomic (gj_combine, csrc/fj_group_dev.h).  Then
 // the workgroup reserves its g_p output rows on the call's cursor with ONE global atomic and sweeps the table: occupied slots take
 // ranks inside the range by wave ballot + popcount on an LDS cursor.  The emit is the only phase that writes to HBM; the order of
 // the groups is whatever the cursor and the slots make it.
@@ -323,12 +324,7 @@ __global__ __launch_bounds__(1024) void fj_gt_group_by_inverse_kernel(FjGtArgs a
 template <bool EMIT> hipError_t launch_lds(const FjGroupByArgs& a, int agg, hipStream_t s) {
     const u32 lds = (u32)sizeof(GbHdr) + GJ_TS * 16u;
     void (*kern)(FjGroupByArgs);
-    if constexpr (EMIT)
-        kern = agg == FJ_GJ_COUNT ? fj_group_by_kernel<FJ_GJ_COUNT, true> : agg == FJ_GJ_SUM ? fj_group_by_kernel<FJ_GJ_SUM, true> :
-               agg == FJ_GJ_MIN_U ? fj_group_by_kernel<FJ_GJ_MIN_U, true> : agg == FJ_GJ_MIN_S ? fj_group_by_kernel<FJ_GJ_MIN_S, true> :
-               agg == FJ_GJ_MAX_U ? fj_group_by_kernel<FJ_GJ_MAX_U, true> : agg == FJ_GJ_MAX_S ? fj_group_by_kernel<FJ_GJ_MAX_S, true> :
-               agg == FJ_GJ_SUM_F ? fj_group_by_kernel<FJ_GJ_SUM_F, true> : agg == FJ_GJ_MIN_F ? fj_group_by_kernel<FJ_GJ_MIN_F, true> :
-               fj_group_by_kernel<FJ_GJ_MAX_F, true>;
+    if constexpr (EMIT) kern = fjh::for_agg(agg, [](auto A) { return fj_group_by_kernel<FJ_V(A), true>; });
     else kern = fj_group_by_kernel<FJ_GJ_COUNT, false>;
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -357,12 +353,7 @@ hipError_t fj_launch_group_by_inverse(const FjGroupByArgs& a, hipStream_t s) {
 hipError_t fj_launch_gt_group_by_combine(const FjGtArgs& a, int agg, const u64* vals, u64* acc, hipStream_t s) {
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || !acc || (agg != FJ_GJ_COUNT && !vals)) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    void (*kern)(FjGtArgs, const u64*, u64*) =
-        agg == FJ_GJ_COUNT ? fj_gt_group_by_combine_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM> :
-        agg == FJ_GJ_MIN_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_gt_group_by_combine_kernel<FJ_GJ_MAX_S> :
-        agg == FJ_GJ_SUM_F ? fj_gt_group_by_combine_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_gt_group_by_combine_kernel<FJ_GJ_MIN_F> :
-        fj_gt_group_by_combine_kernel<FJ_GJ_MAX_F>;
+    void (*kern)(FjGtArgs, const u64*, u64*) = fjh::for_agg(agg, [](auto A) { return fj_gt_group_by_combine_kernel<FJ_V(A)>; });
     hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, acc);
     return hipGetLastError();
 }

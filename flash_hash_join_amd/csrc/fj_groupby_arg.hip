@@ -43,7 +43,7 @@
 namespace {
 
 constexpr u32 GR_TS = 4096, GR_LIMIT = GR_TS - GR_TS / 16;
-enum { GR_UNSIGNED = 0, GR_SIGNED = 1, GR_FLOAT = 2 };
+using fjh::KIND_UNSIGNED; using fjh::KIND_SIGNED; using fjh::KIND_FLOAT;        // the `kind` of the value column (fj_host.h)
 
 // 64 B: the key slots behind it stay 16-byte aligned.  empty_*: the marker key's value and position words
 struct GrHdr { u32 full, has_empty, nkeys, cursor; u64 empty_val, empty_pos, base; u64 pad[3]; };
@@ -53,13 +53,13 @@ static_assert(GR_LDS == 98368u && GR_LDS <= 163840u, "the table must fit one wor
 static_assert(GR_TS % GJ_NT == 0, "the emit sweeps whole waves");
 
 template <int KIND, bool IS_MAX> struct GrAgg {
-    static constexpr int AGG = KIND == GR_FLOAT ? (IS_MAX ? FJ_GJ_MAX_F : FJ_GJ_MIN_F) :
-                               KIND == GR_SIGNED ? (IS_MAX ? FJ_GJ_MAX_S : FJ_GJ_MIN_S) : (IS_MAX ? FJ_GJ_MAX_U : FJ_GJ_MIN_U);
+    static constexpr int AGG = KIND == KIND_FLOAT ? (IS_MAX ? FJ_GJ_MAX_F : FJ_GJ_MIN_F) :
+                               KIND == KIND_SIGNED ? (IS_MAX ? FJ_GJ_MAX_S : FJ_GJ_MIN_S) : (IS_MAX ? FJ_GJ_MAX_U : FJ_GJ_MIN_U);
 };
 
 // does the row's value equal the group's extreme?  Integers by bits; floats as numbers (both zeros tie, a NaN equals nothing)
 template <int KIND> __device__ __forceinline__ bool gr_same(u64 v, u64 ext) {
-    if constexpr (KIND == GR_FLOAT) return __longlong_as_double((long long)v) == __longlong_as_double((long long)ext);
+    if constexpr (KIND == KIND_FLOAT) return __longlong_as_double((long long)v) == __longlong_as_double((long long)ext);
     else return v == ext;
 }
 
@@ -271,11 +271,11 @@ template <int KIND> void (*gr_kernel(bool is_max))(FjGroupByArgs, const u64*, u6
 }  // namespace
 
 hipError_t fj_launch_group_by_arg(const FjGroupByArgs& a, const u64* vals, u64 nrows, int kind, bool is_max, hipStream_t s) {
-    if (kind < GR_UNSIGNED || kind > GR_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !vals) return hipErrorInvalidValue;
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !vals) return hipErrorInvalidValue;
     if (a.out_capacity < nrows) return hipErrorInvalidValue;                       // (every row may be a group of its own)
     if (!a.rel.list ? a.rel.n_flat > nrows : !a.rel.vals) return hipErrorInvalidValue;      // (a chunk pool without positions has nothing to gather by)
-    void (*kern)(FjGroupByArgs, const u64*, u64) = kind == GR_UNSIGNED ? gr_kernel<GR_UNSIGNED>(is_max) :
-                                                   kind == GR_SIGNED ? gr_kernel<GR_SIGNED>(is_max) : gr_kernel<GR_FLOAT>(is_max);
+    void (*kern)(FjGroupByArgs, const u64*, u64) = kind == KIND_UNSIGNED ? gr_kernel<KIND_UNSIGNED>(is_max) :
+                                                   kind == KIND_SIGNED ? gr_kernel<KIND_SIGNED>(is_max) : gr_kernel<KIND_FLOAT>(is_max);
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), GR_LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.nparts), dim3(GJ_NT), GR_LDS, s, a, vals, nrows);
@@ -283,9 +283,9 @@ hipError_t fj_launch_group_by_arg(const FjGroupByArgs& a, const u64* vals, u64 n
 }
 
 hipError_t fj_launch_gt_group_by_arg_resolve(const FjGtArgs& a, int kind, const u64* vals, const u64* ext, u64* pos, hipStream_t s) {
-    if (kind < GR_UNSIGNED || kind > GR_FLOAT || !vals || !ext || !pos) return hipErrorInvalidValue;
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !vals || !ext || !pos) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    hipLaunchKernelGGL(kind == GR_FLOAT ? fj_gt_group_by_arg_resolve_kernel<GR_FLOAT> : fj_gt_group_by_arg_resolve_kernel<GR_UNSIGNED>,
+    hipLaunchKernelGGL(kind == KIND_FLOAT ? fj_gt_group_by_arg_resolve_kernel<KIND_FLOAT> : fj_gt_group_by_arg_resolve_kernel<KIND_UNSIGNED>,
                        dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, ext, pos);      // (signed words compare equal by bits too)
     return hipGetLastError();
 }
@@ -299,8 +299,6 @@ hipError_t fj_launch_gt_group_by_arg_sweep(const FjGtArgs& a, const u64* ext, co
 }
 
 namespace fjh {
-
-static_assert(GR_UNSIGNED == KIND_UNSIGNED && GR_SIGNED == KIND_SIGNED && GR_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
 
 // the global-table form (fj_host.h): a plane of extremes and a plane of positions, capacity + 1 words each.  Every kernel on the one
 // stream

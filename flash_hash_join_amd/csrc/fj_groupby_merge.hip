@@ -33,7 +33,7 @@
 namespace {
 
 constexpr u32 GM_TS = 2048, GM_LIMIT = GM_TS - GM_TS / 16;
-enum { GM_UNSIGNED = 0, GM_SIGNED = 1, GM_FLOAT = 2 };
+using fjh::KIND_UNSIGNED; using fjh::KIND_SIGNED; using fjh::KIND_FLOAT;        // the `kind` of the value column (fj_host.h)
 
 // 64 B: the key slots behind it stay 16-byte aligned.  empty_*: the marker key's accumulators
 struct GmHdr { u32 full, has_empty, nkeys, cursor; u64 empty_cnt, empty_sum, empty_min, empty_max, base, pad; };
@@ -43,9 +43,9 @@ static_assert(GM_LDS == 81984u && GM_LDS <= 163840u, "the table must fit one wor
 static_assert(GM_TS % GJ_NT == 0, "the emit sweeps whole waves");
 
 template <int KIND> struct GmAgg {
-    static constexpr int SUM = KIND == GM_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
-    static constexpr int MIN = KIND == GM_FLOAT ? FJ_GJ_MIN_F : KIND == GM_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
-    static constexpr int MAX = KIND == GM_FLOAT ? FJ_GJ_MAX_F : KIND == GM_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+    static constexpr int SUM = KIND == KIND_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
+    static constexpr int MIN = KIND == KIND_FLOAT ? FJ_GJ_MIN_F : KIND == KIND_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
+    static constexpr int MAX = KIND == KIND_FLOAT ? FJ_GJ_MAX_F : KIND == KIND_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
 };
 
 // Rounds of FOUR rows per thread, as in fj_group_by_arg_kernel: a row in flight is its key, its position and FOUR gathered words, and
@@ -213,11 +213,10 @@ __global__ __launch_bounds__(1024) void fj_gt_group_by_merge_combine_kernel(FjGt
 }  // namespace
 
 hipError_t fj_launch_group_by_merge(const FjGroupByArgs& a, const u64* planes, u64 nrows, int kind, hipStream_t s) {
-    if (kind < GM_UNSIGNED || kind > GM_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity || !planes)
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity || !planes)
         return hipErrorInvalidValue;
     if (!a.rel.list ? a.rel.n_flat > nrows : !a.rel.vals) return hipErrorInvalidValue;      // (a chunk pool without positions has nothing to gather by)
-    void (*kern)(FjGroupByArgs, const u64*, u64) = kind == GM_UNSIGNED ? fj_group_by_merge_kernel<GM_UNSIGNED> :
-                                                   kind == GM_SIGNED ? fj_group_by_merge_kernel<GM_SIGNED> : fj_group_by_merge_kernel<GM_FLOAT>;
+    void (*kern)(FjGroupByArgs, const u64*, u64) = fjh::for_kind(kind, [](auto K) { return fj_group_by_merge_kernel<FJ_V(K)>; });
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), GM_LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.nparts), dim3(GJ_NT), GM_LDS, s, a, planes, nrows);
@@ -225,10 +224,9 @@ hipError_t fj_launch_group_by_merge(const FjGroupByArgs& a, const u64* planes, u
 }
 
 hipError_t fj_launch_gt_group_by_merge_combine(const FjGtArgs& a, int kind, const u64* planes, u64* acc, hipStream_t s) {
-    if (kind < GM_UNSIGNED || kind > GM_FLOAT || !acc || !planes) return hipErrorInvalidValue;
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !acc || !planes) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    void (*kern)(FjGtArgs, const u64*, u64*) = kind == GM_UNSIGNED ? fj_gt_group_by_merge_combine_kernel<GM_UNSIGNED> :
-                                               kind == GM_SIGNED ? fj_gt_group_by_merge_combine_kernel<GM_SIGNED> : fj_gt_group_by_merge_combine_kernel<GM_FLOAT>;
+    void (*kern)(FjGtArgs, const u64*, u64*) = fjh::for_kind(kind, [](auto K) { return fj_gt_group_by_merge_combine_kernel<FJ_V(K)>; });
     hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, planes, acc);
     return hipGetLastError();
 }
@@ -239,8 +237,6 @@ static int merge_outcap_error(u64 g, size_t cap_out) {
     return set_err("fj_join_device: FJ_ALGO_AGG_MERGE found g = %llu distinct keys, output capacity %zu rows (the outputs hold no complete result; call again with room for g)",
                    (unsigned long long)g, cap_out);
 }
-
-static_assert(GM_UNSIGNED == KIND_UNSIGNED && GM_SIGNED == KIND_SIGNED && GM_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
 
 // the global-table form (fj_host.h): group_by_all's accumulator planes and sweep behind this file's combine kernel
 static int group_by_merge_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,

@@ -35,7 +35,7 @@
 namespace {
 
 constexpr u32 GA_TS = 4096, GA_LIMIT = GA_TS - GA_TS / 16;
-enum { GA_UNSIGNED = 0, GA_SIGNED = 1, GA_FLOAT = 2 };
+using fjh::KIND_UNSIGNED; using fjh::KIND_SIGNED; using fjh::KIND_FLOAT;        // the `kind` of the value column (fj_host.h)
 
 // 64 B: the key slots behind it stay 16-byte aligned.  empty_*: the marker key's accumulators
 struct GaHdr { u32 full, has_empty, nkeys, cursor; u32 empty_cnt, pad; u64 empty_sum, empty_min, empty_max, base, pad2; };
@@ -45,9 +45,9 @@ static_assert(GA_LDS <= 163840u, "the table must fit one workgroup's LDS");
 static_assert(GA_TS % GJ_NT == 0, "the emit sweeps whole waves");
 
 template <int KIND> struct GaAgg {
-    static constexpr int SUM = KIND == GA_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
-    static constexpr int MIN = KIND == GA_FLOAT ? FJ_GJ_MIN_F : KIND == GA_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
-    static constexpr int MAX = KIND == GA_FLOAT ? FJ_GJ_MAX_F : KIND == GA_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+    static constexpr int SUM = KIND == KIND_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
+    static constexpr int MIN = KIND == KIND_FLOAT ? FJ_GJ_MIN_F : KIND == KIND_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
+    static constexpr int MAX = KIND == KIND_FLOAT ? FJ_GJ_MAX_F : KIND == KIND_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
 };
 
 // a.out_vals: four planes of a.out_capacity words - count, sum, min, max
@@ -199,11 +199,10 @@ __global__ __launch_bounds__(1024) void fj_gt_group_by_all_sweep_kernel(FjGtArgs
 }  // namespace
 
 hipError_t fj_launch_group_by_all(const FjGroupByArgs& a, int kind, hipStream_t s) {
-    if (kind < GA_UNSIGNED || kind > GA_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity)
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity)
         return hipErrorInvalidValue;
     if (!a.rel.list && (!a.rel.vals || a.rel.n_flat > 0xFFFFFFFFull)) return hipErrorInvalidValue;      // (the value column; the u32 counts)
-    void (*kern)(FjGroupByArgs) = kind == GA_UNSIGNED ? fj_group_by_all_kernel<GA_UNSIGNED> :
-                                  kind == GA_SIGNED ? fj_group_by_all_kernel<GA_SIGNED> : fj_group_by_all_kernel<GA_FLOAT>;
+    void (*kern)(FjGroupByArgs) = fjh::for_kind(kind, [](auto K) { return fj_group_by_all_kernel<FJ_V(K)>; });
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), GA_LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.nparts), dim3(GJ_NT), GA_LDS, s, a);
@@ -211,10 +210,9 @@ hipError_t fj_launch_group_by_all(const FjGroupByArgs& a, int kind, hipStream_t 
 }
 
 hipError_t fj_launch_gt_group_by_all_combine(const FjGtArgs& a, int kind, const u64* vals, u64* acc, hipStream_t s) {
-    if (kind < GA_UNSIGNED || kind > GA_FLOAT || !acc || !vals) return hipErrorInvalidValue;
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !acc || !vals) return hipErrorInvalidValue;
     if (!a.nb) return hipSuccess;
-    void (*kern)(FjGtArgs, const u64*, u64*) = kind == GA_UNSIGNED ? fj_gt_group_by_all_combine_kernel<GA_UNSIGNED> :
-                                               kind == GA_SIGNED ? fj_gt_group_by_all_combine_kernel<GA_SIGNED> : fj_gt_group_by_all_combine_kernel<GA_FLOAT>;
+    void (*kern)(FjGtArgs, const u64*, u64*) = fjh::for_kind(kind, [](auto K) { return fj_gt_group_by_all_combine_kernel<FJ_V(K)>; });
     hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.nb)), dim3(1024), 0, s, a, vals, acc);
     return hipGetLastError();
 }
@@ -233,8 +231,6 @@ static int outcap_error(u64 g, size_t cap_out) {
     return set_err("fj_join_device: FJ_ALGO_AGG_ALL found g = %llu distinct keys, output capacity %zu rows (the outputs hold no complete result; call again with room for g)",
                    (unsigned long long)g, cap_out);
 }
-
-static_assert(GA_UNSIGNED == KIND_UNSIGNED && GA_SIGNED == KIND_SIGNED && GA_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
 
 // the global-table form (fj_host.h); also what a relation of 2^32 rows or more takes.  Four accumulator planes of capacity + 1 words
 static int group_by_all_global(fj_ctx* c, const u64* bk, const u64* bv, size_t nb, hipStream_t s, fj_timings* t, u64* out_count,

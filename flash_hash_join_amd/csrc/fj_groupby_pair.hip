@@ -317,26 +317,19 @@ int group_by_pair(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, size_
     if (nb == 0) return 0;
     if (!use_radix) return group_by_pair_global(c, ka, kb, nb, s, t, out_count, d_ok, d_ov, cap_out);
 
-    const Plan plan = make_plan(nb, top_bits, false);        // factorize's plan: the table is its 8192 slots
     void* p;
     if (get_buf(c, W_PAIR_WORDS, nb * 8, &p)) return 1;
     u64* words = (u64*)p;
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
-    HIPCHK(fj_launch_pair_combine(ka, kb, words, (u64)nb, s));
+    RelAttempt r;                                            // factorize's plan: the table is its 8192 slots
+    if (rel_begin(c, nb, top_bits, 0, s, &r)) return 1;
+    HIPCHK(fj_launch_pair_combine(ka, kb, words, (u64)nb, s));           // (inside build_phase_ms)
+    if (rel_passes(c, words, REL_POSITIONS, nullptr, nb, top_bits, s, &r)) return 1;   // the rows' positions travel through the passes; the kernel gathers the pairs
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    it.vals_pos = true;                                      // the rows' positions travel through the passes; the kernel gathers the pairs
-    if (run_passes(c, it, words, nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(launch_pair_lds(ga, ka, kb, nb, s));
-    if (rel_close(c, plan, ga.nparts, s, t)) return 1;
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
     if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_PAIR_COLLISION))        // a partition beyond the LDS table, or two pairs on one word: the whole call on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return group_by_pair_global(c, ka, kb, nb, s, g, out_count, d_ok, d_ov, cap_out); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: group-by met a row position beyond the relation, or more distinct pairs than rows");

@@ -11,7 +11,8 @@
 // columns itself.
 //
 // fj_group_by_pair_agg_kernel is fj_group_by_merge_kernel's shape (csrc/fj_groupby_merge.hip): one workgroup of 1024 threads per WHOLE
-// final partition, the LDS table of csrc/fj_lds_table_dev.h over the mixed words, the marker word out of band in the header.  Per row:
+// final partition, the LDS table that csrc/fj_lds_table_dev.h STATES over the mixed words (the insert loop is written out in the kernel,
+// as that header says every kernel's is), the marker word out of band in the header.  Per row:
 // gather B[position] and V[position], find or insert the word, and six LDS atomics behind the slot - a 64-bit minimum of b into bmin
 // (all ones at rest), a 64-bit maximum of b into bmax (0 at rest), a u32 add for the count and three gj_combine of V's kind.
 //
@@ -43,7 +44,7 @@
 namespace {
 
 constexpr u32 GQ_TS = 2048, GQ_LIMIT = GQ_TS - GQ_TS / 16;
-enum { GQ_UNSIGNED = 0, GQ_SIGNED = 1, GQ_FLOAT = 2 };
+using fjh::KIND_UNSIGNED; using fjh::KIND_SIGNED; using fjh::KIND_FLOAT;        // the `kind` of the value column (fj_host.h)
 
 // 128 B: the key slots behind it stay 16-byte aligned.  empty_*: the marker word's b evidence and accumulators
 struct GqHdr { u32 full, has_empty, nkeys, cursor; u32 empty_cnt, collided; u64 empty_bmin, empty_bmax, empty_sum, empty_min, empty_max, base; u64 pad[7]; };
@@ -53,9 +54,9 @@ static_assert(GQ_LDS == 106624u && GQ_LDS <= 163840u, "the table must fit one wo
 static_assert(GQ_TS % GJ_NT == 0, "the verification and the emit sweep whole waves");
 
 template <int KIND> struct GqAgg {
-    static constexpr int SUM = KIND == GQ_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
-    static constexpr int MIN = KIND == GQ_FLOAT ? FJ_GJ_MIN_F : KIND == GQ_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
-    static constexpr int MAX = KIND == GQ_FLOAT ? FJ_GJ_MAX_F : KIND == GQ_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
+    static constexpr int SUM = KIND == KIND_FLOAT ? FJ_GJ_SUM_F : FJ_GJ_SUM;
+    static constexpr int MIN = KIND == KIND_FLOAT ? FJ_GJ_MIN_F : KIND == KIND_SIGNED ? FJ_GJ_MIN_S : FJ_GJ_MIN_U;
+    static constexpr int MAX = KIND == KIND_FLOAT ? FJ_GJ_MAX_F : KIND == KIND_SIGNED ? FJ_GJ_MAX_S : FJ_GJ_MAX_U;
 };
 
 // Rounds of FOUR rows per thread, as in fj_group_by_merge_kernel: a row in flight is its word, its position and the two gathered
@@ -276,12 +277,11 @@ __global__ __launch_bounds__(1024) void fj_gt_pair_agg_sweep_kernel(const u64* _
 }
 
 hipError_t launch_pair_agg_lds(const FjGroupByArgs& a, const u64* B, const u64* V, u64 nrows, int kind, hipStream_t s) {
-    if (kind < GQ_UNSIGNED || kind > GQ_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity || !B || !V)
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !a.cursor || !a.err || !a.nparts || !a.out_keys || !a.out_vals || !a.out_capacity || !B || !V)
         return hipErrorInvalidValue;
     if (!a.rel.list ? a.rel.n_flat > nrows : !a.rel.vals) return hipErrorInvalidValue;      // (a chunk pool without positions has nothing to gather by)
     if (nrows > 0xFFFFFFFFull) return hipErrorInvalidValue;                                 // (the u32 counts)
-    void (*kern)(FjGroupByArgs, const u64*, const u64*, u64) = kind == GQ_UNSIGNED ? fj_group_by_pair_agg_kernel<GQ_UNSIGNED> :
-                                                               kind == GQ_SIGNED ? fj_group_by_pair_agg_kernel<GQ_SIGNED> : fj_group_by_pair_agg_kernel<GQ_FLOAT>;
+    void (*kern)(FjGroupByArgs, const u64*, const u64*, u64) = fjh::for_kind(kind, [](auto K) { return fj_group_by_pair_agg_kernel<FJ_V(K)>; });
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), GQ_LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.nparts), dim3(GJ_NT), GQ_LDS, s, a, B, V, nrows);
@@ -289,10 +289,10 @@ hipError_t launch_pair_agg_lds(const FjGroupByArgs& a, const u64* B, const u64* 
 }
 
 hipError_t launch_gt_pair_agg_combine(const u64* A, const u64* B, const u64* V, u64 nb, const u64* tab, u64 cap_mask, u64* acc, int kind, hipStream_t s) {
-    if (kind < GQ_UNSIGNED || kind > GQ_FLOAT || !A || !B || !V || !tab || !acc) return hipErrorInvalidValue;
+    if (kind < KIND_UNSIGNED || kind > KIND_FLOAT || !A || !B || !V || !tab || !acc) return hipErrorInvalidValue;
     if (!nb) return hipSuccess;
     void (*kern)(const u64*, const u64*, const u64*, u64, const u64*, u64, u64*) =
-        kind == GQ_UNSIGNED ? fj_gt_pair_agg_combine_kernel<GQ_UNSIGNED> : kind == GQ_SIGNED ? fj_gt_pair_agg_combine_kernel<GQ_SIGNED> : fj_gt_pair_agg_combine_kernel<GQ_FLOAT>;
+        fjh::for_kind(kind, [](auto K) { return fj_gt_pair_agg_combine_kernel<FJ_V(K)>; });
     hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(nb)), dim3(1024), 0, s, A, B, V, nb, tab, cap_mask, acc);
     return hipGetLastError();
 }
@@ -305,8 +305,6 @@ static int pair_outcap_error(u64 g, size_t cap_out) {
     return set_err("fj_join_device: FJ_ALGO_KEY_PAIR | FJ_ALGO_AGG_ALL found g = %llu distinct pairs, output capacity %zu rows (the outputs hold no complete result; call again with room for g)",
                    (unsigned long long)g, cap_out);
 }
-
-static_assert(GQ_UNSIGNED == KIND_UNSIGNED && GQ_SIGNED == KIND_SIGNED && GQ_FLOAT == KIND_FLOAT, "kind_agg reads `kind` by these values");
 
 // the global-table form (fj_host.h); also what a relation of 2^32 rows or more takes, and the fallback of two pairs on one word
 static int group_by_pair_agg_global(fj_ctx* c, const u64* ka, const u64* kb, const u64* kv, size_t nb, hipStream_t s, fj_timings* t,
@@ -342,26 +340,19 @@ int group_by_pair_agg(fj_ctx* c, bool use_radix, const u64* ka, const u64* kb, c
     if ((u64)nb >> 32) use_radix = false;                    // (the LDS table counts in u32)
     if (!use_radix) return group_by_pair_agg_global(c, ka, kb, kv, nb, s, t, out_count, d_ok, d_ov, cap_out, kind);
 
-    const Plan plan = make_plan(nb, top_bits, false, GQ_TS / 2);         // aim at half of the table's 2048 slots per partition
     void* p;
     if (get_buf(c, W_PAIR_WORDS, nb * 8, &p)) return 1;
     u64* words = (u64*)p;
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
-    HIPCHK(fj_launch_pair_combine(ka, kb, words, (u64)nb, s));
+    RelAttempt r;
+    if (rel_begin(c, nb, top_bits, GQ_TS / 2, s, &r)) return 1;          // aim at half of the table's 2048 slots per partition
+    HIPCHK(fj_launch_pair_combine(ka, kb, words, (u64)nb, s));           // (inside build_phase_ms)
+    if (rel_passes(c, words, REL_POSITIONS, nullptr, nb, top_bits, s, &r)) return 1;   // the rows' positions travel through the passes; the kernel gathers B and V
     FjGroupByArgs ga{};
-    PassIter it;
-    pass_init(it, 0, true, nb, plan, top_bits);
-    it.vals_pos = true;                                      // the rows' positions travel through the passes; the kernel gathers B and V
-    if (run_passes(c, it, words, nullptr, s, &ga.rel, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ga.nparts = ga.rel.list ? ga.rel.nb : 1u;
+    ga.rel = r.rel; ga.nparts = r.nparts;
     ga.out_keys = d_ok; ga.out_vals = d_ov; ga.out_capacity = cap_out;
     ga.cursor = &c->d_sc->total; ga.err = &c->d_sc->err;
     HIPCHK(launch_pair_agg_lds(ga, kb, kv, nb, kind, s));
-    if (rel_close(c, plan, ga.nparts, s, t)) return 1;
+    if (rel_close(c, r.plan, r.nparts, s, t)) return 1;
     if (c->h_sc->err & (FJ_ERR_LDS_FULL | FJ_ERR_PAIR_COLLISION))        // a partition beyond the LDS table, or two pairs on one word: the whole call on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return group_by_pair_agg_global(c, ka, kb, kv, nb, s, g, out_count, d_ok, d_ov, cap_out, kind); });
     *out_count = c->h_sc->total;

@@ -345,13 +345,97 @@ template <class F> int gt_fallback(fj_timings* t, F&& global_form) {
 int kind_agg(int kind, int plane);
 
 // ---- the partitioned attempt on ONE relation (fj_groupby*.hip).  rel_open: make_plan (target: make_plan's override, 0 = none) ..
-// E_PPART - the relation's passes, with `beside` travelling beside the keys (vals is read for REL_VALUES only).  rel_close: E_JOIN ..
-// plan_timings behind the form's kernel, the pool check included; probe_phase_ms = join_ms (there is no second relation) ----
+// E_PPART - the relation's passes, with `beside` travelling beside the keys (vals is read for REL_VALUES only).  It is rel_begin
+// (make_plan .. clear_plan_scalars) + rel_passes (the passes .. E_PPART): a form whose input is made on the stream takes the two
+// halves and launches in between, inside build_phase_ms (fj_groupby_pair*.hip).  rel_close: E_JOIN .. plan_timings behind the
+// form's kernel, the pool check included; probe_phase_ms = join_ms (there is no second relation) ----
 enum RelBeside { REL_KEYS_ONLY, REL_VALUES, REL_POSITIONS };      // nothing / the value column / the rows' positions, made by the first pass
 struct RelAttempt { Plan plan; FjChunkSet rel{}; u32 nparts = 0; };
+int rel_begin(fj_ctx* c, size_t n, int top_bits, u64 target, hipStream_t s, RelAttempt* r);
+int rel_passes(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, hipStream_t s, RelAttempt* r);
 int rel_open(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, u64 target, hipStream_t s,
              RelAttempt* r);
 int rel_close(fj_ctx* c, const Plan& plan, u32 nparts, hipStream_t s, fj_timings* t);
+
+// ---- the partitioned attempt on TWO relations (fj_aligned, fj_group, fj_outer, fj_prepared, join_many) ----
+// pair_open: the caller's plan (make_plan; join_many's has a target of its own), then begin_plan .. E_PPART - the build relation's
+//   passes with spec.build beside its keys, E_BUILD, the probe relation's with spec.probe and the join's item table, E_PPART.
+// pair_open_probe_only: the probe half against a stored plan (fj_prepared.hip); E_BUILD stands right behind clear_plan_scalars and
+//   a.build stays empty.
+// pair_items: the join's work items - the probe side's item table, or slices of a flat probe side (a zero-pass plan) - into the four
+//   fields of that name of the kernel's arguments.
+// pair_close: E_JOIN, then pair_read: the scalars read back, the pool error returned BEFORE end_plan (plan_in_flight then stays set
+//   and get_zeroed_buf re-zeroes), end_plan, plan_timings.  The caller tests FJ_ERR_LDS_FULL behind it - plan_timings first, so that
+//   gt_fallback adds the abandoned attempt's total_ms.
+// pair_rerun_build_with_row_ids: duplicate build keys - the build side once more with row indices as payload (W_ROWIDX); the
+//   counters, `also` (a further scalar of the form, or null), the error word and the allocators are cleared, and the passes stand
+//   between a begin_plan / end_plan of their own.  The caller sets orig_vals, launches again and closes AGAIN.
+// Closing again (behind a rerun's relaunch; join_group: behind the count launch for P): the second pair_close / pair_read records
+//   the second E_JOIN and reads back again; its end_plan finds the plan ended already, its pool check reads a bit the first close has
+//   ruled out unless a rerun's passes raised it, and its plan_timings assigns every field anew - the first close's timings are
+//   discarded, and the call reports the intervals up to the second E_JOIN.
+// trivial_done: an empty side - E_START, fill(), E_JOIN, synchronise; *ms = the interval, which the caller assigns as its form
+//   reports it.
+struct PairSpec { RelBeside build, probe; };
+struct PairAttempt { Plan plan; PassIter bit, pit; FjChunkSet build{}, probe{}; u32 nparts = 0; int evc = 0; };
+int pair_open(fj_ctx* c, const Plan& plan, const PairSpec& spec, const u64* bk, const u64* bv, size_t nb, const u64* pk, const u64* pv,
+              size_t np, int top_bits, hipStream_t s, PairAttempt* a);
+int pair_open_probe_only(fj_ctx* c, const Plan& plan, int top_bits, RelBeside probe, const u64* pk, const u64* pv, size_t np,
+                         hipStream_t s, PairAttempt* a);
+void pair_items(const PairAttempt& a, size_t np, const uint4** items, const u32** nitems_dev, u32* items_cap, u32* nsplit);
+int pair_read(fj_ctx* c, const PairAttempt& a, hipStream_t s, fj_timings* t);
+int pair_close(fj_ctx* c, const PairAttempt& a, hipStream_t s, fj_timings* t);
+int pair_rerun_build_with_row_ids(fj_ctx* c, PairAttempt* a, const u64* bk, size_t nb, int top_bits, unsigned long long* also,
+                                  hipStream_t s);
+template <class F> int trivial_done(fj_ctx* c, hipStream_t s, float* ms, F&& fill) {
+    HIPCHK(hipEventRecord(c->ev[E_START], s));
+    if (fill()) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    HIPCHK(hipStreamSynchronize(s));
+    *ms = ev_ms(c, E_START, E_JOIN);
+    return 0;
+}
+
+// ---- one dispatch per enum: a runtime `agg` (FJ_GJ_COUNT .. FJ_GJ_LAST) or `kind` (ValueKind) handed to f as a compile-time constant,
+// so that `for_agg(agg, [](auto A) { return kernel<FJ_V(A)>; })` names the instantiation to launch.  for_value_agg: the eight forms
+// that read a value - FJ_GJ_COUNT takes FJ_GJ_SUM's, and no FJ_GJ_COUNT instantiation is made.  Out of range (the launchers refuse
+// it first) falls where the chains `agg == FJ_GJ_COUNT ? kernel<FJ_GJ_COUNT> : ...` these replace let it fall: their last
+// alternative ----
+template <int V> using IntC = std::integral_constant<int, V>;
+#define FJ_V(A) decltype(A)::value
+template <class F> auto for_agg(int agg, F&& f) -> decltype(f(IntC<FJ_GJ_MIN_F>{})) {
+    // KEEP THIS ORDER OF THE CASES (and the form in the return type: the first of them).  The compiler emits a kernel's instantiations
+    // in the order in which they are named here, and this is the order the replaced chains gave (last alternative first); another
+    // order computes the same and reorders the kernels in the device objects, which profiles/host_scaffold_device_objects.txt
+    // compares byte for byte
+    switch (agg) {
+    case FJ_GJ_MIN_F: return f(IntC<FJ_GJ_MIN_F>{});
+    default: return f(IntC<FJ_GJ_MAX_F>{});
+    case FJ_GJ_SUM_F: return f(IntC<FJ_GJ_SUM_F>{});
+    case FJ_GJ_MAX_S: return f(IntC<FJ_GJ_MAX_S>{});
+    case FJ_GJ_MAX_U: return f(IntC<FJ_GJ_MAX_U>{});
+    case FJ_GJ_MIN_S: return f(IntC<FJ_GJ_MIN_S>{});
+    case FJ_GJ_MIN_U: return f(IntC<FJ_GJ_MIN_U>{});
+    case FJ_GJ_SUM: return f(IntC<FJ_GJ_SUM>{});
+    case FJ_GJ_COUNT: return f(IntC<FJ_GJ_COUNT>{});
+    }
+}
+template <class F> auto for_value_agg(int agg, F&& f) -> decltype(f(IntC<FJ_GJ_MAX_F>{})) {
+    // KEEP THIS ORDER OF THE CASES (for_agg says why)
+    switch (agg) {
+    case FJ_GJ_MAX_F: return f(IntC<FJ_GJ_MAX_F>{});
+    default: return f(IntC<FJ_GJ_SUM>{});                   // (FJ_GJ_SUM itself, and FJ_GJ_COUNT)
+    case FJ_GJ_MIN_F: return f(IntC<FJ_GJ_MIN_F>{});
+    case FJ_GJ_SUM_F: return f(IntC<FJ_GJ_SUM_F>{});
+    case FJ_GJ_MAX_S: return f(IntC<FJ_GJ_MAX_S>{});
+    case FJ_GJ_MAX_U: return f(IntC<FJ_GJ_MAX_U>{});
+    case FJ_GJ_MIN_S: return f(IntC<FJ_GJ_MIN_S>{});
+    case FJ_GJ_MIN_U: return f(IntC<FJ_GJ_MIN_U>{});
+    }
+}
+template <class F> auto for_kind(int kind, F&& f) -> decltype(f(IntC<KIND_SIGNED>{})) {      // (KEEP THIS ORDER too)
+    return kind == KIND_SIGNED ? f(IntC<KIND_SIGNED>{}) : kind == KIND_FLOAT ? f(IntC<KIND_FLOAT>{}) : f(IntC<KIND_UNSIGNED>{});
+}
 
 int stamps_begin(unsigned long long** dbg, hipStream_t s);
 int stamps_report(const char* label, const unsigned long long* dbg, u32 nitems, hipStream_t s);

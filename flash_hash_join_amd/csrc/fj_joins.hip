@@ -588,31 +588,22 @@ static int mm_tile_join(fj_ctx* c, const FjLdsJoinArgs& ja, u32 nitems, int mate
 // emit's sweep) and counts them: r = nb - marked.
 int join_many(fj_ctx* c, int materialize, const u64* bk, const u64* bv, size_t nb, const u64* pk, size_t np, int top_bits,
               hipStream_t s, fj_timings* t, u64* out_count, bool rid = false, int outer = FJ_MM_INNER) {
-    const Plan plan = make_plan(nb, top_bits, false, 2048);          // aim at half of the kernel's 4096 rows per partition
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
+    // the plan aims at half of the kernel's 4096 rows per partition; row ids: both sides' first passes make the positions
+    PairAttempt a;
+    if (pair_open(c, make_plan(nb, top_bits, false, 2048), {!materialize ? REL_KEYS_ONLY : rid ? REL_POSITIONS : REL_VALUES, rid ? REL_POSITIONS : REL_KEYS_ONLY},
+                  bk, bv, nb, pk, nullptr, np, top_bits, s, &a)) return 1;
+    const Plan& plan = a.plan;
+    const int evc = a.evc;
     FjLdsJoinArgs ja{};
-    PassIter bit, pit;
-    pass_init(bit, 0, materialize != 0, nb, plan, top_bits);
-    pass_init(pit, 1, rid, np, plan, top_bits);
-    bit.vals_pos = pit.vals_pos = rid;                               // (row ids: both sides' first passes make the positions)
-    pit.want_items = true;
-    int evc = 0;
     ja.row_ids = rid ? 1u : 0u;
-    if (run_passes(c, bit, bk, (materialize && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ja.nparts = 1u << plan.bits;
+    ja.build = a.build; ja.probe = a.probe; ja.nparts = a.nparts;
+    pair_items(a, np, &ja.items, &ja.nitems_dev, &ja.items_cap, &ja.nsplit);
     u32 nitems;
     void* p;
     if (ja.probe.list) {
-        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.part_count = pit.part_count; ja.nsplit = 1;
-        nitems = pit.items_cap;
+        ja.part_count = a.pit.part_count;
+        nitems = a.pit.items_cap;
     } else {
-        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
         nitems = ja.nparts * ja.nsplit;
         if (get_buf(c, W_PART_COUNT, (size_t)nitems * 4, &p)) return 1; ja.part_count = (u32*)p;
     }

@@ -373,70 +373,37 @@ int join_outer(fj_ctx* c, int mode, bool use_radix, const u64* bk, const u64* bv
     *out_count = 0;
     if (np == 0) return 0;
     if (nb == 0) {                                           // every probe row is unmatched
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (rid) HIPCHK(fj_launch_iota(d_ok, np, s));
-        else HIPCHK(hipMemcpyAsync(d_ok, pk, np * 8, hipMemcpyDeviceToDevice, s));
-        if (left) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, [&]() -> int {
+                if (rid) HIPCHK(fj_launch_iota(d_ok, np, s));
+                else HIPCHK(hipMemcpyAsync(d_ok, pk, np * 8, hipMemcpyDeviceToDevice, s));
+                if (left) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
+                return 0;
+            })) return 1;
+        t->path = use_radix ? 0 : 1; t->total_ms = t->join_ms = t->probe_phase_ms = ms;
         *out_count = left ? 0 : np;
         return 0;
     }
     if (!use_radix) return join_outer_global(c, mode, bk, bv, nb, pk, np, s, t, out_count, d_ok, d_ov, rid);
 
-    const Plan plan = make_plan(nb, top_bits, false);
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;                  // (total = the hit cursor, expected = the miss cursor)
+    // (total = the hit cursor, expected = the miss cursor)
+    PairAttempt a;
+    if (pair_open(c, make_plan(nb, top_bits, false), {!left ? REL_KEYS_ONLY : rid ? REL_POSITIONS : REL_VALUES, rid ? REL_POSITIONS : REL_KEYS_ONLY}, bk, bv, nb, pk, nullptr, np, top_bits, s, &a)) return 1;
     FjLdsJoinArgs ja{};
-    PassIter bit, pit;
-    pass_init(bit, 0, left, nb, plan, top_bits);
-    bit.vals_pos = rid;
-    int evc = 0;
-    if (run_passes(c, bit, bk, (left && !rid) ? bv : nullptr, s, &ja.build, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    pass_init(pit, 1, rid, np, plan, top_bits);
-    pit.vals_pos = rid;
-    pit.want_items = true;
-    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
-    void* p;
-    if (ja.probe.list) {
-        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
-    } else {                                                 // zero-pass plan: slices of the flat probe side
-        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
-    }
+    ja.build = a.build; ja.probe = a.probe; ja.nparts = a.nparts;
+    pair_items(a, np, &ja.items, &ja.nitems_dev, &ja.items_cap, &ja.nsplit);
     ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
     ja.out_cursor = &c->d_sc->total; ja.out_capacity = np; ja.out_keys = d_ok; ja.out_vals = left ? d_ov : nullptr;
     ja.row_ids = rid ? 1u : 0u;
     HIPCHK(fj_launch_outer_join(ja, (rid && left) ? FJ_OJ_LEFT_FIRST : mode, np, &c->d_sc->expected, s));
-    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-    if (read_scalars(c, s)) return 1;
-    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-    end_plan(c);
+    if (pair_close(c, a, s, t)) return 1;
     if (left && !rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
-        if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
-        u64* rowidx = (u64*)p;
-        HIPCHK(fj_launch_iota(rowidx, nb, s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both cursors
-        HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
-        PassIter bit2;
-        pass_init(bit2, 0, true, nb, plan, top_bits);
-        begin_plan(c);
-        if (run_passes(c, bit2, bk, rowidx, s, &ja.build, nullptr)) return 1;
-        end_plan(c);
-        ja.orig_vals = bv;
+        if (pair_rerun_build_with_row_ids(c, &a, bk, nb, top_bits, nullptr, s)) return 1;
+        ja.build = a.build; ja.orig_vals = bv;
         HIPCHK(fj_launch_outer_join(ja, FJ_OJ_LEFT_FIRST, np, &c->d_sc->expected, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
+        if (pair_close(c, a, s, t)) return 1;
     }
-    plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return join_outer_global(c, mode, bk, bv, nb, pk, np, s, g, out_count, d_ok, d_ov, rid); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the outer join kernel wrote out of its rows");
@@ -456,52 +423,36 @@ int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb
     out_counts[0] = out_counts[1] = 0;
     if (nb == 0) return join_outer(c, FJ_OJ_LEFT, use_radix, bk, bv, nb, pk, np, top_bits, s, t, &out_counts[0], d_ok, d_ov, rid);
     if (np == 0) {                                           // every build row is unmatched
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (rid) { HIPCHK(hipMemsetAsync(d_ok, 0xFF, nb * 8, s)); HIPCHK(fj_launch_iota(d_ov, nb, s)); }
-        else {
-            HIPCHK(hipMemcpyAsync(d_ok, bk, nb * 8, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(d_ov, bv, nb * 8, hipMemcpyDeviceToDevice, s));
-        }
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->path = use_radix ? 0 : 1; t->total_ms = t->emit_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, [&]() -> int {
+                if (rid) { HIPCHK(hipMemsetAsync(d_ok, 0xFF, nb * 8, s)); HIPCHK(fj_launch_iota(d_ov, nb, s)); }
+                else {
+                    HIPCHK(hipMemcpyAsync(d_ok, bk, nb * 8, hipMemcpyDeviceToDevice, s));
+                    HIPCHK(hipMemcpyAsync(d_ov, bv, nb * 8, hipMemcpyDeviceToDevice, s));
+                }
+                return 0;
+            })) return 1;
+        t->path = use_radix ? 0 : 1; t->total_ms = t->emit_ms = ms;
         out_counts[1] = nb;
         return 0;
     }
     if (!use_radix) return join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, t, &out_counts[0], d_ok, d_ov, rid, &out_counts[1]);
 
-    const Plan plan = make_plan(nb, top_bits, false);
-    begin_plan(c);
-    HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;                  // (total = the hit cursor, expected = the miss cursor, sample_hits = the sweep's)
+    // (total = the hit cursor, expected = the miss cursor, sample_hits = the sweep's)
+    PairAttempt a;
+    if (pair_open(c, make_plan(nb, top_bits, false), {rid ? REL_POSITIONS : REL_VALUES, rid ? REL_POSITIONS : REL_KEYS_ONLY}, bk, bv, nb, pk, nullptr, np, top_bits, s, &a)) return 1;
     FjLdsJoinArgs ja{};
-    PassIter bit, pit;
-    pass_init(bit, 0, true, nb, plan, top_bits);
-    bit.vals_pos = rid;
-    int evc = 0;
-    if (run_passes(c, bit, bk, rid ? nullptr : bv, s, &ja.build, nullptr)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
-    pass_init(pit, 1, rid, np, plan, top_bits);
-    pit.vals_pos = rid;
-    pit.want_items = true;
-    if (run_passes(c, pit, pk, nullptr, s, &ja.probe, &evc)) return 1;
-    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-    ja.nparts = ja.probe.list ? ja.probe.nb : 1u << plan.bits;
-    if (ja.probe.list) {
-        ja.items = pit.tiles; ja.nitems_dev = pit.ntiles; ja.items_cap = pit.items_cap; ja.nsplit = 1;
-    } else {                                                 // zero-pass plan: slices of the flat probe side
-        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-        ja.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); ja.items = nullptr; ja.nitems_dev = nullptr; ja.items_cap = 0;
-    }
+    ja.build = a.build; ja.probe = a.probe; ja.nparts = a.nparts;
+    pair_items(a, np, &ja.items, &ja.nitems_dev, &ja.items_cap, &ja.nsplit);
     ja.err = &c->d_sc->err; ja.total = &c->d_sc->total;
     ja.out_cursor = &c->d_sc->total; ja.out_capacity = np; ja.out_keys = d_ok; ja.out_vals = d_ov;
     ja.row_ids = rid ? 1u : 0u;
     const u64 out_cap = (u64)np + nb;
-    void* p;
     // the join, then the sweep behind it on the same stream: one read-back serves both (a join that reports duplicates or a partition
-    // beyond its table leaves rows behind row np that the rerun overwrites)
+    // beyond its table leaves rows behind row np that the rerun overwrites).  E_JOIN stands before the sweep: pair_close's second half
     auto join_and_sweep = [&](int mode) -> int {
         const size_t bit_bytes = (ja.build.list ? (size_t)ja.build.cap : (nb + FJ_CHUNK - 1) / FJ_CHUNK) * (FJ_CHUNK / 8);
+        void* p;
         if (get_buf(c, W_FULL_BITS, bit_bytes, &p)) return 1;
         u64* bits = (u64*)p;
         HIPCHK(hipMemsetAsync(bits, 0, bit_bytes, s));
@@ -510,30 +461,15 @@ int join_full(fj_ctx* c, bool use_radix, const u64* bk, const u64* bv, size_t nb
         HIPCHK(hipEventRecord(c->ev[E_EMIT0], s));
         HIPCHK(fj_launch_full_sweep(ja.build, bits, ja.orig_vals, ja.row_ids, d_ok, d_ov, np, out_cap, &c->d_sc->sample_hits, &c->d_sc->err, s));
         HIPCHK(hipEventRecord(c->ev[E_EMIT1], s));
-        if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-        return 0;
+        return pair_read(c, a, s, t);
     };
     if (join_and_sweep(rid ? FJ_OJ_LEFT_FIRST : FJ_OJ_LEFT)) return 1;
-    end_plan(c);
     if (!rid && !(c->h_sc->err & FJ_ERR_LDS_FULL) && (c->h_sc->err & FJ_STAT_DUPS)) {
         // duplicate build keys: the build side once more with row indices as payload, and the whole output rewritten
-        if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
-        u64* rowidx = (u64*)p;
-        HIPCHK(fj_launch_iota(rowidx, nb, s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both cursors
-        HIPCHK(hipMemsetAsync(&c->d_sc->sample_hits, 0, sizeof(unsigned long long), s));  // ... and the sweep's
-        HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
-        HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
-        PassIter bit2;
-        pass_init(bit2, 0, true, nb, plan, top_bits);
-        begin_plan(c);
-        if (run_passes(c, bit2, bk, rowidx, s, &ja.build, nullptr)) return 1;
-        end_plan(c);
-        ja.orig_vals = bv;
+        if (pair_rerun_build_with_row_ids(c, &a, bk, nb, top_bits, &c->d_sc->sample_hits, s)) return 1;
+        ja.build = a.build; ja.orig_vals = bv;
         if (join_and_sweep(FJ_OJ_LEFT_FIRST)) return 1;
     }
-    plan_timings(c, plan, ja.nparts, evc, t);
     if (c->h_sc->err & FJ_ERR_LDS_FULL)                      // a partition beyond the LDS table: the whole join on the HBM table
         return gt_fallback(t, [&](fj_timings* g) { return join_outer_global(c, FJ_OJ_LEFT, bk, bv, nb, pk, np, s, g, &out_counts[0], d_ok, d_ov, rid, &out_counts[1]); });
     if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: the full outer join wrote out of its rows");

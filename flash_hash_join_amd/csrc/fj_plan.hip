@@ -440,20 +440,39 @@ int kind_agg(int kind, int plane) {
     return forms[kind][plane];
 }
 
-int rel_open(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, u64 target, hipStream_t s,
-             RelAttempt* r) {
-    r->plan = make_plan(n, top_bits, false, target);
+// the opening every partitioned attempt shares: make_plan's result in hand, begin_plan, E_START, the scalars cleared
+static int plan_begin(fj_ctx* c, hipStream_t s) {
     begin_plan(c);
     HIPCHK(hipEventRecord(c->ev[E_START], s));
-    if (clear_plan_scalars(c, s)) return 1;
-    PassIter it;
-    pass_init(it, 0, beside != REL_KEYS_ONLY, n, r->plan, top_bits);
+    return clear_plan_scalars(c, s);
+}
+
+// one relation's passes with `beside` travelling beside its keys
+static int side_passes(fj_ctx* c, PassIter& it, int side, RelBeside beside, const u64* keys, const u64* vals, size_t n, const Plan& plan,
+                       int top_bits, bool want_items, hipStream_t s, FjChunkSet* out, int* evc) {
+    pass_init(it, side, beside != REL_KEYS_ONLY, n, plan, top_bits);
     it.vals_pos = beside == REL_POSITIONS;
-    if (run_passes(c, it, keys, beside == REL_VALUES ? vals : nullptr, s, &r->rel, nullptr)) return 1;
+    it.want_items = want_items;
+    return run_passes(c, it, keys, beside == REL_VALUES ? vals : nullptr, s, out, evc);
+}
+
+int rel_begin(fj_ctx* c, size_t n, int top_bits, u64 target, hipStream_t s, RelAttempt* r) {
+    r->plan = make_plan(n, top_bits, false, target);
+    return plan_begin(c, s);
+}
+
+int rel_passes(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, hipStream_t s, RelAttempt* r) {
+    PassIter it;
+    if (side_passes(c, it, 0, beside, keys, vals, n, r->plan, top_bits, false, s, &r->rel, nullptr)) return 1;
     HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
     HIPCHK(hipEventRecord(c->ev[E_PPART], s));
     r->nparts = r->rel.list ? r->rel.nb : 1u;
     return 0;
+}
+
+int rel_open(fj_ctx* c, const u64* keys, RelBeside beside, const u64* vals, size_t n, int top_bits, u64 target, hipStream_t s,
+             RelAttempt* r) {
+    return rel_begin(c, n, top_bits, target, s, r) || rel_passes(c, keys, beside, vals, n, top_bits, s, r);
 }
 
 int rel_close(fj_ctx* c, const Plan& plan, u32 nparts, hipStream_t s, fj_timings* t) {
@@ -463,6 +482,69 @@ int rel_close(fj_ctx* c, const Plan& plan, u32 nparts, hipStream_t s, fj_timings
     end_plan(c);
     plan_timings(c, plan, nparts, 0, t);
     t->probe_phase_ms = t->join_ms;                          // (there is no second relation: the form's kernels alone)
+    return 0;
+}
+
+// ---- the partitioned attempt on two relations (fj_host.h) ----
+static int pair_probe_half(fj_ctx* c, RelBeside probe, const u64* pk, const u64* pv, size_t np, int top_bits, hipStream_t s, PairAttempt* a) {
+    if (side_passes(c, a->pit, 1, probe, pk, pv, np, a->plan, top_bits, true, s, &a->probe, &a->evc)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_PPART], s));
+    a->nparts = a->probe.list ? a->probe.nb : 1u << a->plan.bits;
+    return 0;
+}
+
+int pair_open(fj_ctx* c, const Plan& plan, const PairSpec& spec, const u64* bk, const u64* bv, size_t nb, const u64* pk, const u64* pv,
+              size_t np, int top_bits, hipStream_t s, PairAttempt* a) {
+    a->plan = plan;
+    if (plan_begin(c, s)) return 1;
+    if (side_passes(c, a->bit, 0, spec.build, bk, bv, nb, a->plan, top_bits, false, s, &a->build, nullptr)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    return pair_probe_half(c, spec.probe, pk, pv, np, top_bits, s, a);
+}
+
+int pair_open_probe_only(fj_ctx* c, const Plan& plan, int top_bits, RelBeside probe, const u64* pk, const u64* pv, size_t np,
+                         hipStream_t s, PairAttempt* a) {
+    a->plan = plan;
+    if (plan_begin(c, s)) return 1;
+    HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+    return pair_probe_half(c, probe, pk, pv, np, top_bits, s, a);
+}
+
+void pair_items(const PairAttempt& a, size_t np, const uint4** items, const u32** nitems_dev, u32* items_cap, u32* nsplit) {
+    if (a.probe.list) {
+        *items = a.pit.tiles; *nitems_dev = a.pit.ntiles; *items_cap = a.pit.items_cap; *nsplit = 1;
+    } else {                                                 // zero-pass plan: slices of the flat probe side
+        const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
+        *nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32)); *items = nullptr; *nitems_dev = nullptr; *items_cap = 0;
+    }
+}
+
+int pair_read(fj_ctx* c, const PairAttempt& a, hipStream_t s, fj_timings* t) {
+    if (read_scalars(c, s)) return 1;
+    if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
+    end_plan(c);
+    plan_timings(c, a.plan, a.nparts, a.evc, t);
+    return 0;
+}
+
+int pair_close(fj_ctx* c, const PairAttempt& a, hipStream_t s, fj_timings* t) {
+    HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
+    return pair_read(c, a, s, t);
+}
+
+int pair_rerun_build_with_row_ids(fj_ctx* c, PairAttempt* a, const u64* bk, size_t nb, int top_bits, unsigned long long* also,
+                                  hipStream_t s) {
+    void* p;
+    if (get_buf(c, W_ROWIDX, nb * 8, &p)) return 1;
+    u64* rowidx = (u64*)p;
+    HIPCHK(fj_launch_iota(rowidx, nb, s));
+    HIPCHK(hipMemsetAsync(&c->d_sc->total, 0, 2 * sizeof(unsigned long long), s));    // both counters (total, expected)
+    if (also) HIPCHK(hipMemsetAsync(also, 0, sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(&c->d_sc->err, 0, sizeof(u32), s));
+    HIPCHK(hipMemsetAsync(&c->d_sc->alloc[0], 0, sizeof(c->d_sc->alloc) + sizeof(c->d_sc->seg_counter), s));   // the build side's passes run again
+    begin_plan(c);
+    if (side_passes(c, a->bit, 0, REL_VALUES, bk, rowidx, nb, a->plan, top_bits, false, s, &a->build, nullptr)) return 1;
+    end_plan(c);
     return 0;
 }
 

@@ -496,12 +496,7 @@ hipError_t fj_launch_prep_group(const FjPrepGroupArgs& a, int agg, hipStream_t s
     if (!a.err || !a.runs || !a.keys || !a.rows || !a.out || (a.total && !a.miss_total)) return hipErrorInvalidValue;
     if (agg != FJ_GJ_COUNT && !a.probe.vals) return hipErrorInvalidValue;         // the probe side carries the values
     const u32 lds = (u32)sizeof(PgHdr) + PP_TS * 16u;
-    void (*kern)(FjPrepGroupArgs) =
-        agg == FJ_GJ_COUNT ? fj_prep_group_kernel<FJ_GJ_COUNT> : agg == FJ_GJ_SUM ? fj_prep_group_kernel<FJ_GJ_SUM> :
-        agg == FJ_GJ_MIN_U ? fj_prep_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_group_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_prep_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_group_kernel<FJ_GJ_MAX_S> :
-        agg == FJ_GJ_SUM_F ? fj_prep_group_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_prep_group_kernel<FJ_GJ_MIN_F> :
-        fj_prep_group_kernel<FJ_GJ_MAX_F>;
+    void (*kern)(FjPrepGroupArgs) = fjh::for_agg(agg, [](auto A) { return fj_prep_group_kernel<FJ_V(A)>; });
     hipError_t e = fj_set_max_lds_once(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
     if (grid) hipLaunchKernelGGL(kern, dim3(grid), dim3(PP_NT), lds, s, a);
@@ -515,11 +510,7 @@ hipError_t fj_launch_prep_gt_group(const FjGtArgs& a, int agg, const u64* pv, u6
     if ((!out_cnt && !out_val) || (out_val && !pv)) return hipErrorInvalidValue;
     if (agg < FJ_GJ_COUNT || agg > FJ_GJ_LAST || (out_val && agg == FJ_GJ_COUNT)) return hipErrorInvalidValue;
     void (*kern)(FjGtArgs, const u64*, u64*, u64*, u64, unsigned long long*, u32*) =
-        agg == FJ_GJ_MIN_U ? fj_prep_gt_group_kernel<FJ_GJ_MIN_U> : agg == FJ_GJ_MIN_S ? fj_prep_gt_group_kernel<FJ_GJ_MIN_S> :
-        agg == FJ_GJ_MAX_U ? fj_prep_gt_group_kernel<FJ_GJ_MAX_U> : agg == FJ_GJ_MAX_S ? fj_prep_gt_group_kernel<FJ_GJ_MAX_S> :
-        agg == FJ_GJ_SUM_F ? fj_prep_gt_group_kernel<FJ_GJ_SUM_F> : agg == FJ_GJ_MIN_F ? fj_prep_gt_group_kernel<FJ_GJ_MIN_F> :
-        agg == FJ_GJ_MAX_F ? fj_prep_gt_group_kernel<FJ_GJ_MAX_F> :
-        fj_prep_gt_group_kernel<FJ_GJ_SUM>;                                       // (the counts alone: out_val == nullptr)
+        fjh::for_value_agg(agg, [](auto A) { return fj_prep_gt_group_kernel<FJ_V(A)>; });      // (the counts alone: out_val == nullptr)
     hipLaunchKernelGGL(kern, dim3(fjh::gt_grid(a.np)), dim3(1024), 0, s, a, pv, out_cnt, out_val, nb, miss_total, err);
     return hipGetLastError();
 }
@@ -639,12 +630,13 @@ int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timing
     t->build_phase_ms = 0;
     if (np == 0) return 0;
     if (P.form == Prepared::EMPTY) {                         // no probe row has a partner
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (vals) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
-        if (d_mask) HIPCHK(hipMemsetAsync(d_mask, 0, np, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, [&]() -> int {
+                if (vals) HIPCHK(hipMemsetAsync(d_ov, rid ? 0xFF : 0, np * 8, s));
+                if (d_mask) HIPCHK(hipMemsetAsync(d_mask, 0, np, s));
+                return 0;
+            })) return 1;
+        t->total_ms = t->join_ms = t->probe_phase_ms = ms;
         return 0;
     }
     if (P.form == Prepared::HBM) {
@@ -659,37 +651,20 @@ int prepared_probe(fj_ctx* c, const u64* pk, size_t np, hipStream_t s, fj_timing
         if (read_scalars(c, s)) return 1;
         t->join_ms = t->probe_phase_ms = t->total_ms = ev_ms(c, E_START, E_JOIN);
     } else {
-        begin_plan(c);
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (clear_plan_scalars(c, s)) return 1;              // (total = the hits, expected = the misses)
-        HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+        // (total = the hits, expected = the misses; the probe rows' positions travel through the passes)
+        PairAttempt a;
+        if (pair_open_probe_only(c, P.plan, P.top_bits, REL_POSITIONS, pk, nullptr, np, s, &a)) return 1;
         FjPrepProbeArgs pa{};
-        PassIter pit;
-        int evc = 0;
-        pass_init(pit, 1, true, np, P.plan, P.top_bits);     // the probe rows' positions travel through the passes
-        pit.vals_pos = true;
-        pit.want_items = true;
-        if (run_passes(c, pit, pk, nullptr, s, &pa.probe, &evc)) return 1;
-        HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-        pa.nparts = P.nparts;
-        if (pa.probe.list) {
-            if (pa.probe.nb != P.nparts) return set_err("internal error: the probe side has %u partitions, the prepared build side %u", pa.probe.nb, P.nparts);
-            pa.items = pit.tiles; pa.nitems_dev = pit.ntiles; pa.items_cap = pit.items_cap; pa.nsplit = 1;
-        } else {                                             // zero-pass plan: slices of the flat probe side
-            if (P.nparts != 1) return set_err("internal error: a flat probe side against %u prepared partitions", P.nparts);
-            const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-            pa.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32));
-        }
+        pa.probe = a.probe; pa.nparts = P.nparts;
+        if (pa.probe.list && pa.probe.nb != P.nparts) return set_err("internal error: the probe side has %u partitions, the prepared build side %u", pa.probe.nb, P.nparts);
+        if (!pa.probe.list && P.nparts != 1) return set_err("internal error: a flat probe side against %u prepared partitions", P.nparts);
+        pair_items(a, np, &pa.items, &pa.nitems_dev, &pa.items_cap, &pa.nsplit);
         pa.keys = P.keys; pa.plane = vals ? (rid ? P.rows : P.vals) : nullptr; pa.runs = (const FjPrepRun*)P.aux; pa.nkeys = P.g;
         pa.miss_word = rid ? ~0ull : 0ull;
         pa.out_vals = d_ov; pa.mask = d_mask; pa.np = np;
         pa.total = &c->d_sc->total; pa.miss_total = &c->d_sc->expected; pa.err = &c->d_sc->err;
         HIPCHK(fj_launch_prep_probe(pa, s));
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-        end_plan(c);
-        plan_timings(c, P.plan, P.nparts, evc, t);
+        if (pair_close(c, a, s, t)) return 1;
         t->build_phase_ms = 0;                               // (nothing touched the build relation: its passes ran when it was prepared)
         if (c->h_sc->err & FJ_ERR_LDS_FULL) return set_err("internal error: a run of the prepared build side does not fit the LDS table");
         if (c->h_sc->err & FJ_ERR_OUTCAP) return set_err("internal error: a probe row's position lies beyond the probe side");
@@ -723,11 +698,9 @@ int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream
         return 0;
     };
     if (np == 0) {                                           // no build row has a partner
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (fill()) return 1;
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->total_ms = t->join_ms = t->probe_phase_ms = ev_ms(c, E_START, E_JOIN);
+        float ms;
+        if (trivial_done(c, s, &ms, fill)) return 1;
+        t->total_ms = t->join_ms = t->probe_phase_ms = ms;
         return 0;
     }
     if (P.form == Prepared::HBM) {
@@ -742,26 +715,14 @@ int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream
         if (read_scalars(c, s)) return 1;
         t->join_ms = t->probe_phase_ms = t->total_ms = ev_ms(c, E_START, E_JOIN);
     } else {
-        begin_plan(c);
-        HIPCHK(hipEventRecord(c->ev[E_START], s));
-        if (clear_plan_scalars(c, s)) return 1;              // (total = the hits, expected = the misses)
-        HIPCHK(hipEventRecord(c->ev[E_BUILD], s));
+        // (total = the hits, expected = the misses; the counts alone: the keys-only pass)
+        PairAttempt a;
+        if (pair_open_probe_only(c, P.plan, P.top_bits, d_val ? REL_VALUES : REL_KEYS_ONLY, pk, pv, np, s, &a)) return 1;
         FjPrepGroupArgs ga{};
-        PassIter pit;
-        int evc = 0;
-        pass_init(pit, 1, d_val != nullptr, np, P.plan, P.top_bits);             // the counts alone: the keys-only pass
-        pit.want_items = true;
-        if (run_passes(c, pit, pk, d_val ? pv : nullptr, s, &ga.probe, &evc)) return 1;
-        HIPCHK(hipEventRecord(c->ev[E_PPART], s));
-        ga.nparts = P.nparts;
-        if (ga.probe.list) {
-            if (ga.probe.nb != P.nparts) return set_err("internal error: the probe side has %u partitions, the prepared build side %u", ga.probe.nb, P.nparts);
-            ga.items = pit.tiles; ga.nitems_dev = pit.ntiles; ga.items_cap = pit.items_cap; ga.nsplit = 1;
-        } else {                                             // zero-pass plan: slices of the flat probe side
-            if (P.nparts != 1) return set_err("internal error: a flat probe side against %u prepared partitions", P.nparts);
-            const u64 pchunks = (np + FJ_CHUNK - 1) / FJ_CHUNK;
-            ga.nsplit = (u32)std::min<u64>(2048, std::max<u64>(1, pchunks / 32));
-        }
+        ga.probe = a.probe; ga.nparts = P.nparts;
+        if (ga.probe.list && ga.probe.nb != P.nparts) return set_err("internal error: the probe side has %u partitions, the prepared build side %u", ga.probe.nb, P.nparts);
+        if (!ga.probe.list && P.nparts != 1) return set_err("internal error: a flat probe side against %u prepared partitions", P.nparts);
+        pair_items(a, np, &ga.items, &ga.nitems_dev, &ga.items_cap, &ga.nsplit);
         ga.keys = P.keys; ga.rows = P.rows; ga.runs = (const FjPrepRun*)P.aux; ga.nkeys = P.g; ga.nb = nb;
         ga.err = &c->d_sc->err;
         if (fill()) return 1;
@@ -773,11 +734,7 @@ int prepared_group(fj_ctx* c, const u64* pk, const u64* pv, size_t np, hipStream
             ga.out = d_val; ga.total = d_cnt ? nullptr : &c->d_sc->total; ga.miss_total = d_cnt ? nullptr : &c->d_sc->expected;   // (the count launch has them)
             HIPCHK(fj_launch_prep_group(ga, agg, s));
         }
-        HIPCHK(hipEventRecord(c->ev[E_JOIN], s));
-        if (read_scalars(c, s)) return 1;
-        if (c->h_sc->err & FJ_ERR_POOL) return pool_error();
-        end_plan(c);
-        plan_timings(c, P.plan, P.nparts, evc, t);
+        if (pair_close(c, a, s, t)) return 1;
         t->build_phase_ms = 0;                               // (nothing touched the build relation: its passes ran when it was prepared)
         if (c->h_sc->err & FJ_ERR_LDS_FULL) return set_err("internal error: a run of the prepared build side does not fit the LDS table");
     }
